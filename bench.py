@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: frames/s of uPIT BLSTM TRAINING on WSJ0-2mix-shaped synthetic data.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,16 +15,30 @@ The features are produced before the timed region by the STFT kernel from synthe
 U(24 000, 64 000) samples from a fixed seed, 32 utterances per step, a DIFFERENT batch every step, frames = the valid
 frames only; not the headline line (that stays the T = 400 configuration BASELINE.json quotes the metric on).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
-  roofline      the dominant kernel (fp32 MFMA GEMM): algorithmic FLOP / HIP-event time, live in the timed region
-  cpu_baseline  the CPU oracle's train step (torch-CPU port of the reference loop) on a bounded sample
-  secondary     (default run on one GPU only) the other one-GPU BASELINE configurations, timed in the same process after the
+Rank 0 prints ONE JSON line: metric, value (frames/s), unit, higher_is_better, dtype, ms_per_step (one timed step), the
+workload under `config`, `library`, and for N > 1 `distributed`.  A plain run does only that: set-up, W warm-up steps, K timed
+steps, the outputs if asked for, the line.
+
+--dump-outputs DIR: after the timed steps, what the last of them handed its caller, as DIR/<name>.npy (float32): `loss` and `norm`
+(compute_loss's return), `optimizer_scalars` (ClipAdam.step()'s [grad norm, clip coefficient, skipped, skipped so far]),
+`parameters` (the weights it left) and `gradients` (the ones it computed) -- for a model of more than DUMP_SAMPLE weights the same
+fixed, seeded sample of DUMP_SAMPLE positions of the flat buffers (32 MB in all).  Inputs, initial weights and h0/c0 are seeded:
+the same arguments give the same inputs in every run, so two builds can be compared output for output.
+
+--full adds everything else the benchmark measures (what every run measured before this option existed), as extra objects on
+the same line:
+  roofline      the dominant kernel (fp32 MFMA GEMM): algorithmic FLOP / HIP-event time, live in the timed region (per-kernel
+                HIP events in the timed steps; `standalone` from an untimed extra pass)
+  cpu_baseline  (one GPU only) the CPU oracle's train step (torch-CPU port of the reference loop) on a bounded sample
+  secondary     (headline workload on one GPU only) the other one-GPU BASELINE configurations, timed in the same process after the
                 headline's timed region: the variable-length set in fp32 and bf16, bf16 3-speaker, RSH 4-speaker, the headline
                 workload on the fp32-MFMA kernels throughout (the reference's literal arithmetic) and the reference's own default
                 model and batch size, 2 x 600 / 100 utterances (SECONDARY)
-  aux           (default run on one GPU only) the HBM-bound kernels `north_star` names -- STFT, mask-apply + iSTFT, PIT loss forward
-                and backward: us per launch, GB/s of algorithmic bytes, fraction of the HBM peak
-  library       which libsepkern.so ran and its sk_build_flags() (0 = the product build; a diagnostic build needs --diagnostic)
+  aux           (headline workload on one GPU, or --aux) the HBM-bound kernels `north_star` names -- STFT, mask-apply + iSTFT, PIT
+                loss forward and backward: us per launch, GB/s of algorithmic bytes, fraction of the HBM peak
+  power_note    (headline workload on one GPU) under `roofline`: a sustained run of the dominant GEMM class with the power sensors
+The --no-* switches leave out parts of --full.  `library` (every run): which libsepkern.so ran and its sk_build_flags() (0 = the
+product build; a diagnostic build needs --diagnostic).
 """
 import argparse
 import json
@@ -75,8 +89,8 @@ def parse(argv=None):
                          "(the r03 layout's cost) instead of the packed rows; frames still count the valid ones")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-events", action="store_true")
-    ap.add_argument("--aux", action="store_true", help="time the streaming kernels (STFT, mask-iSTFT, PIT forward / backward) "
-                                                       "also on a non-default run (the default run on one GPU always does)")
+    ap.add_argument("--aux", action="store_true", help="with --full: time the streaming kernels (STFT, mask-iSTFT, PIT forward / "
+                                                       "backward) also for another workload (--full of the headline on one GPU always does)")
     ap.add_argument("--no-aux", action="store_true")
     ap.add_argument("--diagnostic", action="store_true",
                     help="accept a library whose sk_build_flags() is not 0 (a timing-only / ablation build named by SEPKERN_LIB, "
@@ -85,11 +99,20 @@ def parse(argv=None):
     ap.add_argument("--arch", choices=["upit", "rsh"], default="upit",
                     help="rsh: the recurrent-selective-hearing arch (BASELINE configs[4]); not the headline metric")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="default run on one GPU only: skip the secondary BASELINE configurations (ragged set, bf16 3-spk, "
+                    help="--full of the headline on one GPU: skip the secondary BASELINE configurations (ragged set, bf16 3-spk, "
                          "bf16 ragged, RSH 4-spk) that are timed after the headline and reported under \"secondary\"")
     ap.add_argument("--secondary-only", type=str, default="",
                     help="comma-separated names from SECONDARY: time only these (diagnostics)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline figure: per-kernel HIP events and the roofline, and on one GPU "
+                         "aux, the power probe, the secondary configurations and the CPU baseline (the --no-* switches leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, norm, optimizer scalars, weights and gradients, sampled "
+                         "above DUMP_SAMPLE weights) to DIR/<name>.npy")
+    a = ap.parse_args(argv)
+    if not a.full and (a.aux or a.secondary_only):
+        ap.error("--aux and --secondary-only choose what --full measures: add --full")
+    return a
 
 
 def make_batch(torch, ops, synth, B, T, S, first_utt, nsamp=None, padded_rows=False):
@@ -221,7 +244,7 @@ def launch_ranks(n):
 def measure(args, env, standalone_pass=True):
     """One workload (model, optimizer, resident batches) timed as the module docstring says: W warm-up steps, K timed
     steps between barrier + synchronize pairs, max over ranks.  Returns (the JSON line's dict without `cpu_baseline` /
-    `aux` / `secondary`, what aux_kernels() needs).  Called once for the headline and -- default run on one GPU -- once
+    `aux` / `secondary`, what aux_kernels() needs).  Called once for the headline and -- --full on one GPU -- once
     per secondary BASELINE configuration, in the same process."""
     torch, dist, skdist = env.torch, env.dist, env.skdist
     world, rank, local = env.world, env.rank, env.local
@@ -265,6 +288,7 @@ def measure(args, env, standalone_pass=True):
         (len(pool), B, "/".join(str(b[2].R) for b in pool[:4]) + ("/..." if len(pool) > 4 else "")))
     loss_acc = torch.zeros(2, device="cuda")
     counters = {"i": 0, "frames": 0, "T": 0}
+    last = {}                                             # what the latest step returned (--dump-outputs)
 
     if args.arch == "rsh":
         lens = torch.full((B,), T, dtype=torch.int32, device="cuda")
@@ -284,7 +308,7 @@ def measure(args, env, standalone_pass=True):
         loss_acc[0] += loss.detach() * norm               # epoch loss bookkeeping stays on the device
         loss_acc[1] += norm
         loss.backward()
-        opt.step()
+        last.update(loss=loss.detach(), norm=norm, optimizer_scalars=opt.step())
 
     def warm_up():
         for i in range(args.warmup):
@@ -314,7 +338,8 @@ def measure(args, env, standalone_pass=True):
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    if not args.no_kernel_events:
+    events = args.full and not args.no_kernel_events      # per-kernel HIP events in the timed steps: --full only
+    if events:
         ops.PROF = {}
     if world > 1:
         skdist.TIMING = []
@@ -329,12 +354,14 @@ def measure(args, env, standalone_pass=True):
     dt = time.perf_counter() - t0
     frames_timed, T_mean = counters["frames"], counters["T"] / float(args.steps)     # this rank's valid frames in the timed region
     log("timed region done: %.3f ms/step" % (1000.0 * dt / args.steps))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, last)
     prof = ops.prof_summary()
     ops.PROF = None
     # Untimed extra pass for the roofline's "standalone" figure: the same step with the engine's co-scheduling of
     # weight-gradient GEMMs and recurrences switched off, so every launch has the device to itself.
     prof_alone = None
-    if standalone_pass and not args.no_kernel_events and model._engine is not None and model._engine.overlap:
+    if standalone_pass and events and model._engine is not None and model._engine.overlap:
         model._engine.overlap = False
         step()
         torch.cuda.synchronize()
@@ -504,6 +531,28 @@ def measure(args, env, standalone_pass=True):
     return res, (pcms, T_mean)
 
 
+DUMP_SAMPLE = 1 << 22      # --dump-outputs: weights / gradients beyond this many are sampled (2 x 16 MB in fp32)
+
+
+def dump_outputs(path, model, last):
+    """--dump-outputs: the last timed step's return values and the weights and gradients it left in the flat buffers, as
+    float32 .npy files.  Above DUMP_SAMPLE weights (the headline model has 48 M) the same DUMP_SAMPLE positions of both
+    buffers, drawn without replacement from a fixed seed and sorted: the same for every run with the same arguments."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    p, g = model.flat_parameters()
+    if p.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(p.numel(), DUMP_SAMPLE, replace=False))
+        idx = torch.from_numpy(idx).to(p.device)
+        p, g = p[idx], g[idx]
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("loss", last["loss"]), ("norm", last["norm"]), ("optimizer_scalars", last["optimizer_scalars"]),
+                    ("parameters", p), ("gradients", g)):
+        np.save(os.path.join(path, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+    log("outputs of the last timed step written to %s" % path)
+
+
 STREAM_CLASSES = ("stft_kernel", "istft_kernel", "pit_fwd", "pit_bwd")
 
 
@@ -553,7 +602,7 @@ def secondary_workloads(args, env, only=None):
         if only and name not in only:
             continue
         a = argparse.Namespace(**vars(args))
-        a.steps, a.warmup, a.no_kernel_events, a.aux = SECONDARY_STEPS, SECONDARY_WARMUP, False, False
+        a.steps, a.warmup, a.no_kernel_events, a.aux, a.dump_outputs = SECONDARY_STEPS, SECONDARY_WARMUP, False, False, None
         for k, v in over.items():
             if k != "env":
                 setattr(a, k, v)
@@ -629,15 +678,16 @@ def main():
     env = argparse.Namespace(torch=torch, dist=dist, skdist=skdist, world=world, rank=rank, local=local)
     res, aux_in = measure(args, env)
     res["library"] = library
-    default_run = world == 1 and is_headline(args)
-    if rank == 0 and world == 1 and not args.no_aux and (args.aux or default_run):
+    # what a plain run does ends here; the rest is --full
+    default_run = args.full and world == 1 and is_headline(args)
+    if args.full and rank == 0 and world == 1 and not args.no_aux and (args.aux or default_run):
         from sepkern import ops
         res["aux"] = aux_kernels(torch, ops, aux_in[0], args.batch, args.num_spk)
     if rank == 0 and default_run and not args.no_power_probe and "roofline" in res:
         res["roofline"]["power_note"] = power_probe(torch)
-    if world == 1 and not args.no_secondary and is_headline(args):
+    if default_run and not args.no_secondary:
         res["secondary"] = secondary_workloads(args, env, only=[s for s in args.secondary_only.split(",") if s])
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("timing the CPU baseline (bounded sample)")
         res["cpu_baseline"] = cpu_baseline(args.hidden, args.layers, args.num_spk, args.batch, args.frames)
         log("CPU baseline done: %s frames/s on %d threads" % (res["cpu_baseline"]["value"], res["cpu_baseline"]["cores"]))

@@ -9,7 +9,7 @@ mkdir -p $O; cd /tmp; export TMPDIR=/tmp
 for dt in f32 bf16; do
   for c in FETCH_SIZE WRITE_SIZE; do
     spk=2; [ $dt = bf16 ] && spk=3
-    rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/prof_${tag}_${dt}_$c -- python3 $R/bench.py --dtype $dt --num-spk $spk --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-secondary > /dev/null 2> $O/prof_${tag}_${dt}_$c.err || exit 3
+    rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/prof_${tag}_${dt}_$c -- python3 $R/bench.py --full --dtype $dt --num-spk $spk --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events --no-secondary > /dev/null 2> $O/prof_${tag}_${dt}_$c.err || exit 3
   done
 done
 python3 $R/profiles/pmc_traffic.py $tag > $O/pmc_traffic_$tag.txt || exit 6

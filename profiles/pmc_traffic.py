@@ -61,7 +61,7 @@ def main():
         res[k] = {"launches": len(e["FETCH_SIZE"]), "fetch_bytes_raw": round(f), "fetch_bytes_x2": round(2 * f),
                   "write_bytes": round(w), "hbm_bytes": round(2 * f + w)}
     doc = {"_comment": "rocprofv3 --kernel-trace --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, profiles/collect.sh) "
-                       "over `python3 bench.py [--dtype bf16] --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events` on one "
+                       "over `python3 bench.py --full [--dtype bf16] --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-events` on one "
                        "MI355X; per-launch averages; FETCH_SIZE doubled per MI355X_MICROARCH.md; memory-side requests of "
                        "the L2s (Infinity-Cache hits included).", "tag": tag, "kernels": res,
            "kernel_source_id": kernel_source_id(root), "git_sha": git_sha(root)}

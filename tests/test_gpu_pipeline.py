@@ -259,13 +259,14 @@ def test_bench_launches_its_own_ranks_when_no_launcher_did():
 
 
 def test_bench_line_carries_the_contract_fields():
-    """One small `python bench.py` run on the GPU: ONE JSON line with the driver's contract fields, the `roofline` object
+    """One small `python bench.py --full` run on the GPU: ONE JSON line with the driver's contract fields, the `roofline` object
     (dominant class + every MFMA-bound class under `by_kernel`, the recurrences with their MFMA floor and hand-off share)
     and -- on request -- the CPU baseline."""
     import json
     root = os.path.dirname(PKG)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--hidden", "320", "--layers", "2",
-                        "--batch", "32", "--frames", "60", "--no-cpu-baseline"], cwd=root, capture_output=True, text=True, timeout=400)
+                        "--batch", "32", "--frames", "60", "--no-cpu-baseline", "--full"], cwd=root, capture_output=True, text=True,
+                       timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -287,9 +288,45 @@ def test_bench_line_carries_the_contract_fields():
         assert by[k]["us_per_time_step"] > by[k]["mfma_floor_us"] > 0 and by[k]["handoff_us"] > 0
 
 
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """`python bench.py` without --full: the headline fields and nothing that needs runs or events of its own.  With
+    --dump-outputs it writes the last timed step's results as float32 .npy files; the inputs are seeded, so a second run
+    with the same arguments writes the same arrays bit for bit (the kernels are deterministic).  One timed step after none
+    of warm-up: its loss is the line's mean_loss."""
+    import json
+    root = os.path.dirname(PKG)
+    lines, dumps = [], []
+    for i in range(2):
+        out = str(tmp_path / ("run%d" % i))
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "0", "--hidden", "64",
+                            "--layers", "2", "--batch", "4", "--frames", "40", "--dump-outputs", out],
+                           cwd=root, capture_output=True, text=True, timeout=400)
+        assert r.returncode == 0, r.stderr[-3000:]
+        ls = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(ls) == 1
+        lines.append(json.loads(ls[0]))
+        dumps.append({n: np.load(os.path.join(out, n + ".npy"))
+                      for n in ("loss", "norm", "optimizer_scalars", "parameters", "gradients")})
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config", "library"):
+        assert k in d, k
+    assert d["steps"] == 1 and d["warmup"] == 0 and d["dtype"] == "f32" and d["ms_per_step"] > 0
+    for k in ("roofline", "kernels", "aux", "secondary", "cpu_baseline"):
+        assert k not in d, k
+    a = dumps[0]
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["parameters"].shape == a["gradients"].shape and a["parameters"].size > 0 and np.all(np.isfinite(a["parameters"]))
+    assert a["optimizer_scalars"].shape == (4,) and a["optimizer_scalars"][2] == 0
+    assert float(a["norm"]) == d["config"]["frames_per_step"] * 257 == 4 * 40 * 257
+    assert abs(float(a["loss"]) - d["config"]["mean_loss"]) <= 1e-6 + 1e-5 * d["config"]["mean_loss"]      # (mean_loss: 6 decimals)
+    for n in a:
+        np.testing.assert_array_equal(dumps[1][n], a[n], err_msg=n)
+
+
 def test_bench_default_run_carries_the_secondary_block():
-    """The DEFAULT `python bench.py` (the command the round driver runs; here with fewer headline steps and without the CPU
-    baseline) also times the other one-GPU BASELINE configurations in the same process and reports them under "secondary":
+    """`python bench.py --full` of the headline workload (here with fewer headline steps and without the CPU baseline) also
+    times the other one-GPU BASELINE configurations in the same process and reports them under "secondary":
     the variable-length set (fp32 and bf16), bf16 3-speaker, RSH 4-speaker -- VERDICT r04 item 1 --, the headline workload on
     the fp32-MFMA kernels throughout (the reference's literal arithmetic) and the reference's own default model and batch size
     (2 x 600, 100 utterances) -- VERDICT r05 item 2; `aux` carries the streaming kernels `north_star` names (STFT, mask-iSTFT, PIT
@@ -299,7 +336,7 @@ def test_bench_default_run_carries_the_secondary_block():
     workload."""
     import json
     root = os.path.dirname(PKG)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"],
                        cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
