@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 131
+#define SK_VERSION 132
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -413,6 +413,32 @@ int sk_grad_norm(const float* g, int64_t n, float max_norm, const float* guard, 
                  sk_stream_t stream);
 int sk_clip_adam(float* p, const float* g, float* m, float* v, int64_t n, const float* scal,
                  float lr, float beta1, float beta2, float eps, int step, sk_stream_t stream);
+
+/* ---------------------------------------------------------------- BSS Eval (scoring)
+ * Replaces the per-utterance host computation of sepkern/bsseval.py (mir_eval.separation.bss_eval_sources' SDR /
+ * SIR / SAR with a `taps`-long allowed-distortion filter; the reference's steps/evaluate_sources.py:57) for a batch of
+ * U utterances of S sources each.  ref / est: packed fp64 rows; utterance u has length lens_host[u] and its source
+ * (or estimate) i starts at element offs_host[u] + i*lens_host[u] of ref (est).  offs_host / lens_host are HOST arrays,
+ * copied into the workspace on `stream`.  1 <= S <= 4, 1 <= taps <= 512, lengths >= 1; all arithmetic is fp64.
+ * ws >= sk_bss_workspace_bytes(U, S, taps) (0 for arguments out of range).
+ *
+ * sk_bss_xcorr: the lag correlations alone, one record of X = P*(2*taps-1) + S*S*taps + S doubles per utterance at
+ *   xc + u*X, P = S*(S+1)/2:  [c_ij[d] for pairs i <= j in order (0,0),(0,1)..(0,S-1),(1,1).., d = -(taps-1)..taps-1]
+ *   [c_{r_i,e_k}[t], (i, k) row-major, t = 0..taps-1] [|e_k|^2, k = 0..S-1], with c_xy[d] = sum_m x[m] y[m+d].
+ *   Direct sums in a fixed order, no atomics: bitwise reproducible and independent of the batch; exact (every
+ *   product and partial sum representable) for 16-bit PCM scaled by 2^-15.
+ * sk_bss_eval: correlations, the block-Toeplitz Gram matrix of the delayed references and each source's own block,
+ *   their Cholesky factors (blocked, fp64 MFMA trailing update), forward substitution of the estimates' correlations
+ *   and the energies |P_all e_k|^2, |P_j e_k|^2, |e_k|^2.  out (U, S, S, 3) fp64: [u][k][j] = SDR, SIR, SAR in dB of
+ *   estimate k against true source j (a zero or negative denominator gives +inf).  status (U) int32: 0, or bit w set
+ *   when the factorisation of system w (0: all sources, j >= 1: source j alone) met a pivot that is not finite or
+ *   not above 2^-40 (~1e-12) times its diagonal entry (rank-deficient references): that utterance's numbers are not valid and
+ *   the caller re-scores it on the host (sepkern/bsseval_gpu.py). */
+size_t sk_bss_workspace_bytes(int U, int S, int taps);
+int sk_bss_xcorr(const double* ref, const double* est, const int64_t* offs_host, const int32_t* lens_host, int U, int S,
+                 int taps, void* ws, double* xc, sk_stream_t stream);
+int sk_bss_eval(const double* ref, const double* est, const int64_t* offs_host, const int32_t* lens_host, int U, int S,
+                int taps, void* ws, double* out, int32_t* status, sk_stream_t stream);
 
 #ifdef __cplusplus
 }

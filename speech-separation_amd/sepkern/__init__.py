@@ -6,5 +6,6 @@
     optim    fused clip_grad_norm_ + Adam over the flat buffers
     synth    WSJ0-2mix-shaped synthetic data (wav trees, id lists, HBM-resident batches)
     sisdr    SI-SDR scoring
+    bsseval_gpu  batched BSS Eval SDR / SIR / SAR on the device (bsseval: the host function)
 """
 from ._lib import SepkernError, load  # noqa: F401

@@ -730,3 +730,48 @@ def grad_norm(g, max_norm, scal, guard=None):
 def clip_adam(p, g, m, v, scal, lr, beta1, beta2, eps, step):
     _lib.call("sk_clip_adam", _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(scal), float(lr), float(beta1),
               float(beta2), float(eps), int(step), _stream())
+
+
+# ----------------------------------------------------------------------------- BSS Eval scoring (fp64)
+def bss_xc_len(S, taps):
+    """Doubles per utterance in sk_bss_xcorr's record (include/sepkern.h)."""
+    return S * (S + 1) // 2 * (2 * taps - 1) + S * S * taps + S
+
+
+def _bss_args(ref, est, offs, lens, S, taps):
+    _chk(ref, torch.float64)
+    _chk(est, torch.float64)
+    if ref.shape != est.shape or ref.dim() != 1 or not ref.is_contiguous() or not est.is_contiguous():
+        raise _lib.SepkernError("bss: ref and est must be contiguous 1-D fp64 tensors of one length (packed rows)")
+    offs = [int(o) for o in offs]
+    lens = [int(n) for n in lens]
+    if len(offs) != len(lens) or any(o + S * n > ref.numel() for o, n in zip(offs, lens)):
+        raise _lib.SepkernError("bss: offsets / lengths run past the packed rows")
+    U = len(lens)
+    h_offs = (C.c_int64 * U)(*offs)
+    h_lens = (C.c_int32 * U)(*lens)
+    nbytes = _lib.load().sk_bss_workspace_bytes(U, S, taps)
+    # per call, not the cached workspace(): a batch's matrices take gigabytes that should go back to the allocator
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=ref.device) if nbytes else None
+    return U, h_offs, h_lens, ws
+
+
+def bss_xcorr(ref, est, offs, lens, S, taps):
+    """Lag correlations of packed fp64 rows: utterance u's source / estimate i starts at offs[u] + i*lens[u] of ref /
+    est.  Returns (U, bss_xc_len(S, taps)) fp64 (record layout in include/sepkern.h)."""
+    U, h_offs, h_lens, ws = _bss_args(ref, est, offs, lens, S, taps)
+    xc = torch.empty(U, bss_xc_len(S, taps), dtype=torch.float64, device=ref.device)
+    _lib.call("sk_bss_xcorr", _ptr(ref), _ptr(est), h_offs, h_lens, U, S, taps, _ptr(ws), _ptr(xc), _stream())
+    return xc
+
+
+def bss_eval(ref, est, offs, lens, S, taps):
+    """SDR / SIR / SAR of every (estimate k, source j) pair: returns (out (U, S, S, 3) fp64 dB, status (U) int32);
+    status != 0 marks an utterance whose Gram matrix did not factor (include/sepkern.h)."""
+    U, h_offs, h_lens, ws = _bss_args(ref, est, offs, lens, S, taps)
+    out = torch.empty(U, S, S, 3, dtype=torch.float64, device=ref.device)
+    status = torch.empty(U, dtype=torch.int32, device=ref.device)
+    with _timed("bss_eval"):
+        _lib.call("sk_bss_eval", _ptr(ref), _ptr(est), h_offs, h_lens, U, S, taps, _ptr(ws), _ptr(out), _ptr(status),
+                  _stream())
+    return out, status

@@ -21,7 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, ".."))
 
 
-def get_args():
+def get_args(argv=None):
   parser = argparse.ArgumentParser(description="""Evaluates oracle (ideal) masks through the same STFT -> mask ->
   iSTFT path the separation models use""")
   parser.add_argument("data_dir", metavar="data-dir", type=str, help="Data directory with wav.scp")
@@ -29,11 +29,14 @@ def get_args():
   parser.add_argument("--fft-dim", type=int, help="Dimension of FFT", default=512)
   parser.add_argument("--step-size", type=int, help="STFT step size", default=128)
   parser.add_argument("--sample-rate", type=int, help="Audio sample rate", default=8000)
-  return parser.parse_args()
+  parser.add_argument("--gpu", action='store_true', default=False,
+                      help="Score BSS Eval in batches on the GPU (sepkern/bsseval_gpu.py); SI-SDR stays on the host")
+  parser.add_argument("--batch", type=int, default=256, help="Utterances per GPU batch (with --gpu)")
+  return parser.parse_args(argv)
 
 
-def main():
-  args = get_args()
+def main(argv=None):
+  args = get_args(argv)
   if args.fft_dim != 512 or args.step_size != 128:
     raise ValueError("the HIP STFT kernels are built for --fft-dim 512 --step-size 128")
   import torch
@@ -44,6 +47,27 @@ def main():
   dir_out = args.data_dir + ("/oracle_hard_mask_eval/" if args.hard_mask else "/oracle_soft_mask_eval/")
   os.makedirs(dir_out, exist_ok=True)
   out = {m: MetricFiles(dir_out, m) for m in ("SDR", "SIR", "SAR", "SISDR")}
+  pending = []                                    # --gpu: (id, device fp32 estimates, device int16 references)
+
+  def write(reco_id, ests, refs, sdr, sir, sar):
+    out["SDR"].add(reco_id, sdr)
+    out["SIR"].add(reco_id, sir)
+    out["SAR"].add(reco_id, sar)
+    out["SISDR"].add(reco_id, [si_sdr(ests[i], refs[i]) for i in range(len(refs))])
+
+  def flush():
+    if not pending:
+      return
+    from sepkern.bsseval_gpu import bss_eval_sources_batch
+    ests = [torch.stack(e) for _, e, _ in pending]                       # fp32, resident on the device
+    refs = [torch.stack([p[:e.shape[1]] for p in r]) for (_, _, r), e in zip(pending, ests)]   # int16 PCM
+    scores = bss_eval_sources_batch(refs, ests, compute_permutation=False)
+    if scores.n_fallback:
+      print("evaluate_oracle.py: %d utterance(s) re-scored on the host" % scores.n_fallback, file=sys.stderr)
+    for (reco_id, _, _), e, r, (sdr, sir, sar, _) in zip(pending, ests, refs, scores):
+      write(reco_id, e.cpu().numpy().astype(np.float64), r.cpu().numpy().astype(np.float64) / 32768.0, sdr, sir, sar)
+    pending.clear()
+
   with open(args.data_dir + "/wav.scp", 'r') as listF:
     for line in listF:
       reco_id, filename = line.rstrip().split(' ')
@@ -62,13 +86,16 @@ def main():
       else:
         masks = mags / mix_spec.abs().clamp_min(1e-20)
       wav, _ = ops.mask_istft([mix_spec], [[masks[i].contiguous() for i in range(num_src)]], want_pcm=False)
+      if args.gpu:
+        pending.append((reco_id, [wav[0][i] for i in range(num_src)], pcm[1:]))
+        if len(pending) >= args.batch:
+          flush()
+        continue
       ests = np.stack([wav[0][i].cpu().numpy().astype(np.float64) for i in range(num_src)])
       refs = np.stack([pcm[i + 1].cpu().numpy().astype(np.float64)[:ests.shape[1]] / 32768.0 for i in range(num_src)])
       sdr, sir, sar, _ = bss_eval_sources(refs, ests, compute_permutation=False)
-      out["SDR"].add(reco_id, sdr)
-      out["SIR"].add(reco_id, sir)
-      out["SAR"].add(reco_id, sar)
-      out["SISDR"].add(reco_id, [si_sdr(ests[i], refs[i]) for i in range(num_src)])
+      write(reco_id, ests, refs, sdr, sir, sar)
+  flush()
   for files in out.values():
     files.close()
 

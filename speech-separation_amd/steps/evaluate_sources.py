@@ -30,6 +30,9 @@ def get_args(argv=None):
     set of estimated sources and ground truth sources.""")
   parser.add_argument("data_dir", metavar="data-dir", type=str, help="Test set data directory")
   parser.add_argument("exp_dir", metavar="exp-dir", type=str, help="Experiment directory")
+  parser.add_argument("--gpu", action='store_true', default=False,
+                      help="Score BSS Eval in batches on the GPU (sepkern/bsseval_gpu.py); SI-SDR stays on the host")
+  parser.add_argument("--batch", type=int, default=256, help="Utterances per GPU batch (with --gpu)")
   return parser.parse_args(argv)
 
 
@@ -88,13 +91,15 @@ def main(argv=None):
   results = args.exp_dir + "/results"
   os.makedirs(results, exist_ok=True)
   out = {m: MetricFiles(results, m) for m in ("SDR", "SIR", "SAR", "SISDR", "SISDRi")}
-  for utt_id, mix_wav in read_pairs(args.data_dir + "/wav.scp"):
+  def load(utt_id, mix_wav):
     S = num_src[utt_id]
     ests = [load_wav(args.exp_dir + "/wav/s" + str(s + 1) + "/" + utt_id + ".wav") for s in range(S)]
     n = len(ests[0])                              # the first estimate sets the length (steps/evaluate_sources.py:51-55)
     ests = np.stack([e[:n] for e in ests])
     refs = np.stack([load_wav(mix_wav.replace("/mix/", "/s" + str(s + 1) + "/"))[:n] for s in range(S)])
-    sdr, sir, sar, _ = bss_eval_sources(refs, ests)
+    return refs, ests, n
+
+  def write(utt_id, mix_wav, refs, ests, n, sdr, sir, sar):
     out["SDR"].add(utt_id, sdr)
     out["SIR"].add(utt_id, sir)
     out["SAR"].add(utt_id, sar)
@@ -102,6 +107,28 @@ def main(argv=None):
     mix = load_wav(mix_wav)[:n]
     out["SISDR"].add(utt_id, si)
     out["SISDRi"].add(utt_id, [v - si_sdr(mix, refs[s]) for s, v in enumerate(si)])
+
+  pairs = read_pairs(args.data_dir + "/wav.scp")
+  if args.gpu:
+    from sepkern.bsseval_gpu import bss_eval_sources_batch
+    if args.batch < 1:
+      raise ValueError("--batch must be >= 1")
+    fallbacks = 0
+    for b0 in range(0, len(pairs), args.batch):
+      chunk = pairs[b0:b0 + args.batch]
+      loaded = [load(utt_id, mix_wav) for utt_id, mix_wav in chunk]
+      scores = bss_eval_sources_batch([l[0] for l in loaded], [l[1] for l in loaded])
+      fallbacks += scores.n_fallback
+      for (utt_id, mix_wav), (refs, ests, n), (sdr, sir, sar, _) in zip(chunk, loaded, scores):
+        write(utt_id, mix_wav, refs, ests, n, sdr, sir, sar)
+    if fallbacks:
+      print("evaluate_sources.py: %d utterance(s) re-scored on the host (Gram matrix not factored on the GPU)" % fallbacks,
+            file=sys.stderr)
+  else:
+    for utt_id, mix_wav in pairs:
+      refs, ests, n = load(utt_id, mix_wav)
+      sdr, sir, sar, _ = bss_eval_sources(refs, ests)
+      write(utt_id, mix_wav, refs, ests, n, sdr, sir, sar)
   for files in out.values():
     files.close()
 
