@@ -112,10 +112,12 @@ int sk_gemm_f32(const float* A, const float* B, float* C, const float* bias, int
  *      SIGN PHASES: the bf16 MFMA truncates the alignment of its addends towards minus infinity, so a plain split-product result
  *      carries a DC offset (about -2e-11 of the result per K element on all-positive operands: -1.5e-7 at K = 7168) that anything
  *      integrating the result amplifies (r05: the recurrence below a data gradient).  Both split kernels, in every form, therefore
- *      keep -sum instead of +sum in their accumulators over stretches of K (signs + - - + per period of about 128 K steps, the B
- *      operand negated before it is split): truncation then pulls down and up in turn and the offsets cancel
- *      (tests/test_gpu_signed_error.py: mean signed error at the fp32-MFMA kernels' level).
- *      SEPKERN_GEMM_PLANES=0: never 9.  Other operands (F = 257 columns, K = 514): the fp32-MFMA kernels as under 8.  Operands
+ *      keep -sum instead of +sum in their accumulators over stretches of K (signs + - - +, the B operand negated before it is
+ *      split): truncation then pulls down and up in turn and the offsets cancel (tests/test_gpu_signed_error.py: mean signed
+ *      error at the fp32-MFMA kernels' level).  The pattern runs over the whole K, in a whole number p = (n + 32) / 64 of periods
+ *      of about 64 K steps of 16 (n = K / 16 steps): a stretch is q = ceil(n / 4p) steps, 14 / 16 / 17 at K = 1792 / 7168 /
+ *      12800; products of fewer than 48 steps (K < 768) keep the plain form.
+ *      Other operands (F = 257 columns, K = 514): the fp32-MFMA kernels as under 8.  Operands
  *      beyond bf16's finite range (|x| > 3.39e38) round to inf.  SEPKERN_GEMM_SPLIT=0 makes 0 mean 8.
  *   1  the register-staged fp32-MFMA kernel (v_mfma_f32_32x32x2_f32), any alignment
  *   2  the 128 x 128-tile split kernel wherever the LDS-DMA conditions hold (else as 8)

@@ -19,6 +19,16 @@ extern "C" const char* sk_last_error(void) { return g_err; }
 
 extern "C" unsigned sk_build_flags(void) { return sk_gemm_build_flags() | sk_lstm_build_flags(); }
 
+int sk_num_cus() {
+  static int n = 0;
+  if (!n) {
+    int dev = 0;
+    hipDeviceProp_t p;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
+  }
+  return n;
+}
+
 extern "C" int sk_device_info(int* num_cu, int* lds_bytes) {
   int dev = 0;
   hipDeviceProp_t p;

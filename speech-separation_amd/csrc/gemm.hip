@@ -2282,17 +2282,8 @@ extern "C" int sk_gemm_workspace_init(void* ws, sk_stream_t stream) {
 }
 
 namespace {
-int gemm_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-  }
-  return n;
-}
-// workgroups of the stream-K kernel: one per CU, a multiple of 8 (the tile order counts on blockIdx & 7 = XCD)
-int streamk_wgs() { return gemm_cus() & ~7; }
+// workgroups of the stream-K kernels: one per CU, a multiple of 8 (the tile order counts on blockIdx & 7 = XCD)
+int streamk_wgs() { return sk_num_cus() & ~7; }
 }  // namespace
 
 extern "C" size_t sk_gemm_streamk_workspace_bytes(void) {
@@ -2313,15 +2304,147 @@ extern "C" int sk_gemm_f32(const float* A, const float* B, float* C, const float
 
 namespace {
 
+// Kernel ids (sk_gemm_last_kernel, include/sepkern.h)
+enum : int {
+  K_F32 = 1, K_SPLIT = 2, K_DMA = 3, K_WIDE = 4, K_STREAMK = 6, K_BF16 = 9, K_PLANES = 10,  // fp32 operands
+  K_BF2 = 11, K_BF2_WIDE = 12, K_BF2_STREAMK = 13,                                           // bf16 operands in memory
+  K_PL3 = 14                                                                                 // operands that arrive split
+};
+
+// Launch facts of each kernel: threads per block, block tile (M x N), and whether the grid is persistent (one workgroup per
+// CU, streamk_wgs(), instead of one per tile x K slice x batch entry)
+struct KernelShape {
+  int threads, tile_m, tile_n;
+  bool persistent;
+};
+KernelShape kernel_shape(int kernel) {
+  switch (kernel) {
+    case K_WIDE: case K_PLANES: return {512, 256, 128, false};
+    case K_STREAMK: return {512, 256, 256, true};
+    case K_BF2: return {bf2::NT, bf2::BM, 128, false};
+    case K_BF2_WIDE: return {bf2::NT, bf2::BM, 256, false};
+    case K_BF2_STREAMK: return {bf2::NT, bf2::BM, 256, true};
+    default: return {256, BM, BN, false};  // K_F32, K_SPLIT, K_DMA, K_BF16, K_PL3
+  }
+}
+
+// The __global__ function of a kernel in the form (transA, transB).  vec: the register-staged kernel with float4 loads (else
+// dword loads: an operand with unaligned rows, F = 257).  The LDS-DMA kernels have no T/T form; gemm_f32_kernel_planes is
+// templated on the k-major-ness of its operands, <AKM, BKM>: N/T = <false, false>, N/N = <false, true>, T/N = <true, true>.
+using GemmFn = void (*)(GemmArgs);
+GemmFn gemm_fn(int kernel, bool vec, int transA, int transB) {
+  static const GemmFn f32[2][2] = {{gemm_f32_kernel<false, false>, gemm_f32_kernel<false, true>},
+                                   {gemm_f32_kernel<true, false>, gemm_f32_kernel<true, true>}};
+  static const GemmFn f32_dword[2][2] = {{gemm_f32_kernel<false, false, false>, gemm_f32_kernel<false, true, false>},
+                                         {gemm_f32_kernel<true, false, false>, gemm_f32_kernel<true, true, false>}};
+  static const GemmFn split[2][2] = {{gemm_f32_kernel_split3<false, false>, gemm_f32_kernel_split3<false, true>},
+                                     {gemm_f32_kernel_split3<true, false>, nullptr}};
+  static const GemmFn dma[2][2] = {{gemm_f32_kernel_dma<false, false>, gemm_f32_kernel_dma<false, true>},
+                                   {gemm_f32_kernel_dma<true, false>, nullptr}};
+  static const GemmFn wide[2][2] = {{gemm_f32_kernel_dma256<false, false>, gemm_f32_kernel_dma256<false, true>},
+                                    {gemm_f32_kernel_dma256<true, false>, nullptr}};
+  static const GemmFn streamk[2][2] = {{gemm_f32_kernel_streamk<false, false>, gemm_f32_kernel_streamk<false, true>},
+                                       {gemm_f32_kernel_streamk<true, false>, nullptr}};
+  static const GemmFn bf16[2][2] = {{bf::gemm_bf16_kernel<false, false>, bf::gemm_bf16_kernel<false, true>},
+                                    {bf::gemm_bf16_kernel<true, false>, bf::gemm_bf16_kernel<true, true>}};
+  static const GemmFn planes[2][2] = {{gemm_f32_kernel_planes<false, true>, gemm_f32_kernel_planes<false, false>},
+                                      {gemm_f32_kernel_planes<true, true>, nullptr}};
+  const GemmFn(*t)[2];
+  switch (kernel) {
+    case K_SPLIT: t = split; break;
+    case K_DMA: t = dma; break;
+    case K_WIDE: t = wide; break;
+    case K_STREAMK: t = streamk; break;
+    case K_BF16: t = bf16; break;
+    case K_PLANES: t = planes; break;
+    default: t = vec ? f32 : f32_dword; break;
+  }
+  return t[transA != 0][transB != 0];
+}
+
+// The bf16-operand kernel (K_BF2 / _WIDE / _STREAMK) for operands stored (a_kmajor, b_kmajor)
+using Bf2Fn = void (*)(bf2::Args);
+Bf2Fn bf2_fn(int kernel, int a_kmajor, int b_kmajor) {
+  static const Bf2Fn nt128[2][2] = {{bf2::gemm_bf16_nt_kernel<128, false, false>, bf2::gemm_bf16_nt_kernel<128, false, true>},
+                                    {bf2::gemm_bf16_nt_kernel<128, true, false>, bf2::gemm_bf16_nt_kernel<128, true, true>}};
+  static const Bf2Fn nt256[2][2] = {{bf2::gemm_bf16_nt_kernel<256, false, false>, bf2::gemm_bf16_nt_kernel<256, false, true>},
+                                    {bf2::gemm_bf16_nt_kernel<256, true, false>, bf2::gemm_bf16_nt_kernel<256, true, true>}};
+  static const Bf2Fn streamk[2][2] = {{bf2::gemm_bf16_streamk_kernel<false, false>, bf2::gemm_bf16_streamk_kernel<false, true>},
+                                      {bf2::gemm_bf16_streamk_kernel<true, false>, bf2::gemm_bf16_streamk_kernel<true, true>}};
+  const Bf2Fn(*t)[2] = kernel == K_BF2_STREAMK ? streamk : kernel == K_BF2_WIDE ? nt256 : nt128;
+  return t[a_kmajor != 0][b_kmajor != 0];
+}
+
+// K cut into g.splitk slices of g.kchunk, a whole number of K steps bk each; only slices that hold work are counted
+template <class Args>
+void slice_k(Args& g, int splitk, int bk) {
+  g.kchunk = (int)(sk_cdiv(sk_cdiv(g.K, splitk), bk) * bk);
+  g.splitk = (int)sk_cdiv(g.K, g.kchunk);
+}
+
+// Workspace = [ticket counters | slabs]: the partial products of the K slices follow the counters
+float* ws_slabs(void* ws) { return ws ? (float*)((char*)ws + COUNTER_BYTES) : nullptr; }
+
+// The fp32 kernels reduce their K slices in-kernel (finish_splitk) when the counters cover every (batch, tile); otherwise
+// splitk_reduce_kernel does
+bool reduce_in_kernel(int splitk, int64_t tiles, int batch) {
+  return splitk > 1 && tiles * batch * sizeof(unsigned) <= COUNTER_BYTES;
+}
+
+// Sign phases of the split products (SignPhase): stretches of q K steps, signs + - - +, a whole number of periods of about 64
+// steps over the WHOLE K (the slices of a split-K product continue one pattern: K = 1792: q = 14, 7168: 16, 12800: 17 -- a sign
+// change per ~32 steps, the r05 N/N kernel's rate).  What is left of the offset is at most one stretch's worth inside the
+// result's last binade: measured on all-positive operands -5e-10 ... +3e-9 of the result where the plain form has -3.6e-8
+// (K = 1792) ... -2.7e-7 (K = 12800) and the fp32-MFMA kernels -4e-10 ... -1e-9 (profiles/r06_signed_error.txt).  Products
+// shorter than 48 steps (K < 768: the layer-0 projection's K = 272; offset -5e-9) keep the plain form -- three uneven
+// stretches would over-correct it.  Returns q (0: the plain form).
+int flip_quarter(int K) {
+  const int nks = K / BK;
+  if (!SK_SPLIT_FLIP || nks < 48) return 0;
+  const int periods = (nks + 32) / 64;
+  return (nks + 4 * periods - 1) / (4 * periods);
+}
+
+// The stream-K partition of nt output tiles of nk K steps over the persistent grid: sk_full whole rounds of tiles, then the
+// K steps of the remaining tiles laid end to end and cut into equal ranges.  false: whole tiles instead (a remainder too short
+// to give every workgroup a K step goes to the plain kernel's last round), or a grid or product outside the kernels' range.
+bool streamk_cut(int64_t nt, int64_t nk, int& sk_tiles, int& sk_full) {
+  const int P = streamk_wgs();
+  if (P < 8 || nt >= (1 << 24) || nk < 8) return false;
+  const int64_t full = nt / P, rem = nt - full * P;
+  if ((rem > 0 && rem * nk < P) || rem > 16384) return false;
+  sk_tiles = (int)nt;
+  sk_full = (int)full;
+  return true;
+}
+
+// g.tilesN, the number of output tiles and the grid of a launch of kernel shape s
+template <class Args>
+int64_t tile_grid(Args& g, const KernelShape& s, int batch, dim3& grid) {
+  g.tilesN = (int)sk_cdiv(g.N, s.tile_n);
+  const int64_t tiles = sk_cdiv(g.M, s.tile_m) * g.tilesN;
+  grid = s.persistent ? dim3((unsigned)streamk_wgs()) : dim3((unsigned)tiles, (unsigned)g.splitk, (unsigned)batch);
+  return tiles;
+}
+
+// C = act(sum of the K slices' slabs + bias (+ C)) for the kernels that leave the slabs to a second launch
+template <class Args>
+int reduce_slices(const Args& a, int batch, hipStream_t st) {
+  GemmArgs r{};  // (the fields splitk_reduce_kernel reads)
+  r.C = a.C; r.bias = a.bias; r.slabs = a.slabs;
+  r.M = a.M; r.N = a.N; r.ldc = a.ldc; r.splitk = a.splitk;
+  r.accumulate = a.accumulate; r.act = a.act; r.sC = a.sC; r.sbias = a.sbias;
+  const int64_t quads = sk_cdiv((int64_t)a.M * a.N, 4);
+  const unsigned nb = (unsigned)(sk_cdiv(quads, 256) > 2048 ? 2048 : sk_cdiv(quads, 256));
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb, 1, (unsigned)batch), dim3(256), 0, st, r);
+  SK_CHECK_LAUNCH("splitk_reduce_kernel");
+  return SK_OK;
+}
+
 // The LDS-DMA kernel takes a launch when every operand row is 16-byte aligned, every K slice is a multiple of its
 // K step, a k-major operand's tile dimension is a multiple of 4 (whole float4 pieces) and it is not the T/T form.
-// SEPKERN_GEMM_DMA=0 (diagnostics) keeps everything on the register-staged kernel.
 bool dma_ok(const GemmArgs& g, int transA, int transB, bool choose = false) {
-  static const bool enabled = [] {
-    const char* e = getenv("SEPKERN_GEMM_DMA");
-    return !(e && e[0] == '0');
-  }();
-  if (!enabled || !g.vecA || !g.vecB || (transA && transB)) return false;
+  if (!g.vecA || !g.vecB || (transA && transB)) return false;
   if (g.K % BK != 0 || g.kchunk % BK != 0) return false;
   if (transA && (g.M % 4 != 0 || g.M < 4)) return false;
   if (!transB && (g.N % 4 != 0 || g.N < 4)) return false;
@@ -2329,6 +2452,44 @@ bool dma_ok(const GemmArgs& g, int transA, int transB, bool choose = false) {
   // 12800 x 7168 x 1792), everything else faster by DMA (N/N +5 %, T/N +2..5 %, N = 514 N/T +25 %)
   if (choose && !transA && transB && g.M >= 1024 && g.N >= 1024) return false;
   return true;
+}
+
+// Which kernel an sk_gemm_f32_splitk / sk_gemm_bf16_splitk launch takes (g sliced, operand alignment known), and the
+// stream-K partition when that is the stream-K kernel.
+struct Choice {
+  int kernel, sk_tiles, sk_full;
+};
+Choice choose_kernel(const GemmArgs& g, bool bf16, int variant, int transA, int transB, int batch, bool ws) {
+  if (bf16) return {K_BF16, 0, 0};
+  // fp32 products run by default (variant 0) on the bf16 matrix pipe by the three-way split of both operands with six piece
+  // products (gemm_f32_kernel_planes / gemm_f32_kernel_split3) wherever the LDS-DMA conditions hold: 160-212 TFLOP/s
+  // fp32-equivalent on the training step's large products against 124-135 of the fp32-MFMA kernels (stand-alone, one MI355X).
+  // Variant 8 = the choice among the fp32-MFMA kernels (the reference's literal arithmetic; SEPKERN_GEMM_SPLIT=0 makes variant 0
+  // that); operands with unaligned rows or K % 16 != 0 take the fp32-MFMA kernels always.
+  static const bool split_on = [] { const char* e = getenv("SEPKERN_GEMM_SPLIT"); return !(e && e[0] == '0'); }();
+  if (variant == 0 && !split_on) variant = 8;
+  const bool dma = dma_ok(g, transA, transB);
+  const bool unsplit = g.splitk == 1, large = !transA && g.M >= 4096 && g.N >= 1024;
+  if ((variant == 0 || variant == 2 || variant == 9) && dma) {
+    // split ONCE per element while staging (gemm_f32_kernel_planes): unsplit, unbatched products.  With enough 256 x 128 tiles
+    // to fill the chip it is what variant 0 takes: 186-212 TFLOP/s on the projection / data-gradient / unsplit weight-gradient
+    // shapes against 160-168 of the 128 x 128 kernel; 158 vs 100-124 on the N = 514 Linear product.  It needs 72 KB of LDS and
+    // 200 VGPRs: callers that run a product BESIDE a persistent recurrence pass variant 2 (sepkern/engine.py).
+    const bool planes = unsplit && batch == 1 && g.M >= 256 && g.N >= 128 &&
+                        (variant == 9 || (variant == 0 && sk_cdiv(g.M, 256) * sk_cdiv(g.N, 128) >= 192));
+    return {planes ? K_PLANES : K_SPLIT, 0, 0};
+  }
+  const bool mfma_choose = variant == 8 || variant == 0;  // the r04 policy among the fp32-MFMA kernels
+  // 256 x 256 tiles, persistent, with a stream-K cut of the last partial round (fp32 MFMA): variant 6, or chosen under 8 for
+  // large unsplit products when the caller passes the workspace of sk_gemm_streamk_workspace_bytes().
+  Choice c = {K_STREAMK, 0, 0};
+  if (dma && ws && batch == 1 && g.M >= 256 && g.N >= 256 && unsplit && (variant == 6 || (mfma_choose && large)) &&
+      streamk_cut(sk_cdiv(g.M, 256) * sk_cdiv(g.N, 256), g.K / BK, c.sk_tiles, c.sk_full))
+    return c;
+  // 256 x 128 block tiles, 8 waves (fp32 MFMA): variant 4 (and 6 without the stream-K conditions), or chosen for the large
+  // unsplit N/T and N/N products -- measured +2 % / +5 % on them stand-alone.
+  if (dma && g.M >= 256 && (variant == 4 || variant == 6 || (mfma_choose && large && unsplit))) return {K_WIDE, 0, 0};
+  return {variant != 1 && dma_ok(g, transA, transB, mfma_choose) ? K_DMA : K_F32, 0, 0};
 }
 
 int gemm_launch(bool bf16, const float* A, const float* B, float* C, const float* bias, int M, int N, int K, int lda,
@@ -2340,153 +2501,29 @@ int gemm_launch(bool bf16, const float* A, const float* B, float* C, const float
   SK_CHECK_ARG(M > 0 && N > 0 && K > 0 && batch > 0 && batch <= 65535, "sk_gemm: bad sizes M=%d N=%d K=%d batch=%d", M, N, K, batch);
   SK_CHECK_ARG(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N, "sk_gemm: leading dimension too small");
   SK_CHECK_ARG(act == 0 || act == 1, "sk_gemm: unknown activation %d", act);
-  const int bk = bf16 ? bf::BK : BK;
   GemmArgs g;
   g.A = A; g.B = B; g.C = C; g.bias = bias;
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
   g.accumulate = accumulate; g.act = act;
   g.vecA = ((uintptr_t)A % 16 == 0) && (lda % 4 == 0) && (sA % 4 == 0);
   g.vecB = ((uintptr_t)B % 16 == 0) && (ldb % 4 == 0) && (sB % 4 == 0);
-  g.tilesN = (int)sk_cdiv(N, BN);
   g.sA = sA; g.sB = sB; g.sC = sC; g.sbias = sbias;
-  g.sk_tiles = 0; g.sk_full = 0; g.flip_q = 0;
-  g.kchunk = (int)(sk_cdiv(sk_cdiv(K, splitk), bk) * bk);
-  splitk = (int)sk_cdiv(K, g.kchunk);  // slices that actually hold work
-  g.splitk = splitk;
-  // ---- which kernel.  fp32 products run by default (variant 0) on the bf16 matrix pipe by the three-way split of both operands
-  // with six piece products (gemm_f32_kernel_planes / gemm_f32_kernel_split3) wherever the LDS-DMA conditions hold: 160-212 TFLOP/s
-  // fp32-equivalent on the training step's large products against 124-135 of the fp32-MFMA kernels (stand-alone, one MI355X).
-  // Variant 8 = the choice among the fp32-MFMA kernels (the reference's literal arithmetic; SEPKERN_GEMM_SPLIT=0 makes variant 0
-  // that); operands with unaligned rows or K % 16 != 0 take the fp32-MFMA kernels always.
-  static const bool split_on = [] { const char* e = getenv("SEPKERN_GEMM_SPLIT"); return !(e && e[0] == '0'); }();
-  if (variant == 0 && !split_on) variant = 8;
-  const bool split = !bf16 && (variant == 0 || variant == 2 || variant == 9) && dma_ok(g, transA, transB);
-  // split ONCE per element while staging (gemm_f32_kernel_planes): unsplit, unbatched products.  With enough 256 x 128 tiles to
-  // fill the chip it is what variant 0 takes (SEPKERN_GEMM_PLANES=0: never): 186-212 TFLOP/s on the projection / data-gradient /
-  // unsplit weight-gradient shapes against 160-168 of the 128 x 128 kernel; 158 vs 100-124 on the N = 514 Linear product.  It
-  // needs 72 KB of LDS and 200 VGPRs: callers that run a product BESIDE a persistent recurrence pass variant 2 (sepkern/engine.py).
-  static const bool planes_on = [] { const char* e = getenv("SEPKERN_GEMM_PLANES"); return !(e && e[0] == '0'); }();
-  const bool planes = split && splitk == 1 && batch == 1 && M >= 256 && N >= 128 &&
-                      (variant == 9 || (variant == 0 && planes_on && sk_cdiv(M, 256) * sk_cdiv(N, 128) >= 192));
-  // Sign phases of the split products (SignPhase): stretches of q K steps, signs + - - +, a whole number of periods of about 64
-  // steps over the WHOLE K (the slices of a split-K product continue one pattern: K = 1792: q = 14, 7168: 16, 12800: 17 -- a sign
-  // change per ~32 steps, the r05 N/N kernel's rate).  What is left of the offset is at most one stretch's worth inside the
-  // result's last binade: measured on all-positive operands -5e-10 ... +3e-9 of the result where the plain form has -3.6e-8
-  // (K = 1792) ... -2.7e-7 (K = 12800) and the fp32-MFMA kernels -4e-10 ... -1e-9 (profiles/r06_signed_error.txt).  Products
-  // shorter than 48 steps (K < 768: the layer-0 projection's K = 272; offset -5e-9) keep the plain form -- three uneven
-  // stretches would over-correct it.
-  if (split && SK_SPLIT_FLIP) {
-    const int nks = K / BK;
-    if (nks >= 48) {
-      const int periods = (nks + 32) / 64;
-      g.flip_q = (nks + 4 * periods - 1) / (4 * periods);
-    }
-  }
-  const bool mfma_choose = variant == 8 || (variant == 0 && !split);  // the r04 policy among the fp32-MFMA kernels
-  // 256 x 128 block tiles, 8 waves (fp32 MFMA): variant 4, or chosen for the large unsplit N/T and N/N products -- measured
-  // +2 % / +5 % on them stand-alone.  SEPKERN_GEMM_WIDE=0 (diagnostics): never chosen.
-  static const bool wide_ok = [] { const char* e = getenv("SEPKERN_GEMM_WIDE"); return !(e && e[0] == '0'); }();
-  const bool wide = !bf16 && !split && M >= 256 && dma_ok(g, transA, transB) &&
-                    (variant == 4 || variant == 6 || (mfma_choose && wide_ok && !transA && M >= 4096 && N >= 1024 && splitk == 1));
-  // 256 x 256 tiles, persistent, with a stream-K cut of the last partial round (fp32 MFMA): variant 6, or chosen under 8 for
-  // large unsplit products when the caller passes the workspace of sk_gemm_streamk_workspace_bytes().
-  // SEPKERN_GEMM_STREAMK=0 (diagnostics): never chosen.
-  static const bool streamk_ok = [] { const char* e = getenv("SEPKERN_GEMM_STREAMK"); return !(e && e[0] == '0'); }();
-  const bool sk_shape = ws && batch == 1 && M >= 256 && N >= 256 && splitk == 1 && dma_ok(g, transA, transB);
-  bool streamk = !bf16 && !split && sk_shape && (variant == 6 || (mfma_choose && streamk_ok && !transA && M >= 4096 && N >= 1024));
-  if (streamk) {
-    const int P = streamk_wgs();
-    const int64_t nt = sk_cdiv(M, 256) * sk_cdiv(N, 256), nk = K / BK;
-    g.sk_tiles = (int)nt;
-    g.sk_full = (int)(nt / P);
-    const int64_t R = (nt - (int64_t)g.sk_full * P) * nk;
-    // a remainder too short to give every workgroup a K step goes to whole tiles (the plain kernel's last round)
-    if (P < 8 || nt >= (1 << 24) || nk < 8 || (R > 0 && R < P) || nt - (int64_t)g.sk_full * P > 16384) streamk = false;
-  }
-  if (streamk) g.tilesN = (int)sk_cdiv(N, 256);
-  if (planes) g.tilesN = (int)sk_cdiv(N, 128);
-  const int64_t tiles = sk_cdiv(M, (wide || streamk || planes) ? 256 : BM) * g.tilesN;
+  slice_k(g, splitk, bf16 ? bf::BK : BK);
+  const Choice c = choose_kernel(g, bf16, variant, transA, transB, batch, ws != nullptr);
+  const KernelShape s = kernel_shape(c.kernel);
+  g.sk_tiles = c.sk_tiles; g.sk_full = c.sk_full;
+  g.flip_q = (c.kernel == K_SPLIT || c.kernel == K_PLANES) ? flip_quarter(K) : 0;
+  dim3 grid;
+  const int64_t tiles = tile_grid(g, s, batch, grid);
   SK_CHECK_ARG(tiles < (1ll << 31), "sk_gemm: too many tiles");
-  // workspace = [ticket counters | slabs]; the fp32 kernels reduce in-kernel when the counters cover every (batch, tile)
-  g.slabs = ws ? (float*)((char*)ws + COUNTER_BYTES) : nullptr;
-  const bool inkernel = !bf16 && splitk > 1 && tiles * batch * sizeof(unsigned) <= COUNTER_BYTES;
-  g.counters = inkernel ? (unsigned*)ws : nullptr;
-  dim3 grid((unsigned)tiles, (unsigned)splitk, (unsigned)batch);
+  g.slabs = ws_slabs(ws);
+  const bool inkernel = !bf16 && reduce_in_kernel(g.splitk, tiles, batch);
+  g.counters = (inkernel || c.kernel == K_STREAMK) ? (unsigned*)ws : nullptr;  // (the stream-K cut's tickets sit there too)
   hipStream_t st = (hipStream_t)stream;
-  t_last_kernel = bf16 ? 9 : planes ? 10 : streamk ? 6 : wide ? 4 : split ? 2 : (variant != 1 && dma_ok(g, transA, transB, mfma_choose)) ? 3 : 1;
-  if (bf16) {
-    if (!transA && !transB)
-      hipLaunchKernelGGL((bf::gemm_bf16_kernel<false, false>), grid, dim3(256), 0, st, g);
-    else if (!transA && transB)
-      hipLaunchKernelGGL((bf::gemm_bf16_kernel<false, true>), grid, dim3(256), 0, st, g);
-    else if (transA && !transB)
-      hipLaunchKernelGGL((bf::gemm_bf16_kernel<true, false>), grid, dim3(256), 0, st, g);
-    else
-      hipLaunchKernelGGL((bf::gemm_bf16_kernel<true, true>), grid, dim3(256), 0, st, g);
-  } else if (streamk) {
-    g.counters = (unsigned*)ws;
-    const dim3 pgrid((unsigned)streamk_wgs());
-    if (!transA && !transB)
-      hipLaunchKernelGGL((gemm_f32_kernel_streamk<false, false>), pgrid, dim3(512), 0, st, g);
-    else if (!transA && transB)
-      hipLaunchKernelGGL((gemm_f32_kernel_streamk<false, true>), pgrid, dim3(512), 0, st, g);
-    else
-      hipLaunchKernelGGL((gemm_f32_kernel_streamk<true, false>), pgrid, dim3(512), 0, st, g);
-  } else if (wide) {
-    if (!transA && !transB)
-      hipLaunchKernelGGL((gemm_f32_kernel_dma256<false, false>), grid, dim3(512), 0, st, g);
-    else if (!transA && transB)
-      hipLaunchKernelGGL((gemm_f32_kernel_dma256<false, true>), grid, dim3(512), 0, st, g);
-    else
-      hipLaunchKernelGGL((gemm_f32_kernel_dma256<true, false>), grid, dim3(512), 0, st, g);
-  } else if (planes) {
-    if (!transA && transB)
-      hipLaunchKernelGGL((gemm_f32_kernel_planes<false, false>), grid, dim3(512), 0, st, g);
-    else if (!transA && !transB)
-      hipLaunchKernelGGL((gemm_f32_kernel_planes<false, true>), grid, dim3(512), 0, st, g);  // (data gradients)
-    else
-      hipLaunchKernelGGL((gemm_f32_kernel_planes<true, true>), grid, dim3(512), 0, st, g);
-  } else if (split) {
-    if (!transA && !transB)
-      hipLaunchKernelGGL((gemm_f32_kernel_split3<false, false>), grid, dim3(256), 0, st, g);
-    else if (!transA && transB)
-      hipLaunchKernelGGL((gemm_f32_kernel_split3<false, true>), grid, dim3(256), 0, st, g);
-    else
-      hipLaunchKernelGGL((gemm_f32_kernel_split3<true, false>), grid, dim3(256), 0, st, g);
-  } else if (variant != 1 && dma_ok(g, transA, transB, mfma_choose)) {
-    if (!transA && !transB)
-      hipLaunchKernelGGL((gemm_f32_kernel_dma<false, false>), grid, dim3(256), 0, st, g);
-    else if (!transA && transB)
-      hipLaunchKernelGGL((gemm_f32_kernel_dma<false, true>), grid, dim3(256), 0, st, g);
-    else
-      hipLaunchKernelGGL((gemm_f32_kernel_dma<true, false>), grid, dim3(256), 0, st, g);
-  } else if (g.vecA && g.vecB) {
-    if (!transA && !transB)
-      hipLaunchKernelGGL((gemm_f32_kernel<false, false>), grid, dim3(256), 0, st, g);
-    else if (!transA && transB)
-      hipLaunchKernelGGL((gemm_f32_kernel<false, true>), grid, dim3(256), 0, st, g);
-    else if (transA && !transB)
-      hipLaunchKernelGGL((gemm_f32_kernel<true, false>), grid, dim3(256), 0, st, g);
-    else
-      hipLaunchKernelGGL((gemm_f32_kernel<true, true>), grid, dim3(256), 0, st, g);
-  } else {  // an operand with unaligned rows (F = 257): dword-load variant
-    if (!transA && !transB)
-      hipLaunchKernelGGL((gemm_f32_kernel<false, false, false>), grid, dim3(256), 0, st, g);
-    else if (!transA && transB)
-      hipLaunchKernelGGL((gemm_f32_kernel<false, true, false>), grid, dim3(256), 0, st, g);
-    else if (transA && !transB)
-      hipLaunchKernelGGL((gemm_f32_kernel<true, false, false>), grid, dim3(256), 0, st, g);
-    else
-      hipLaunchKernelGGL((gemm_f32_kernel<true, true, false>), grid, dim3(256), 0, st, g);
-  }
+  t_last_kernel = c.kernel;
+  hipLaunchKernelGGL(gemm_fn(c.kernel, g.vecA && g.vecB, transA, transB), grid, dim3(s.threads), 0, st, g);
   SK_CHECK_LAUNCH("sk_gemm");
-  if (splitk > 1 && !inkernel) {
-    const int64_t quads = sk_cdiv((int64_t)M * N, 4);
-    const unsigned nb = (unsigned)(sk_cdiv(quads, 256) > 2048 ? 2048 : sk_cdiv(quads, 256));
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb, 1, (unsigned)batch), dim3(256), 0, st, g);
-    SK_CHECK_LAUNCH("splitk_reduce_kernel");
-  }
-  return SK_OK;
+  return g.splitk > 1 && !inkernel ? reduce_slices(g, batch, st) : SK_OK;
 }
 
 }  // namespace
@@ -2531,67 +2568,26 @@ extern "C" int sk_gemm_bf16_mm(const void* A, const void* B, float* C, const flo
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
   g.accumulate = accumulate; g.act = act;
   g.sA = sA; g.sB = sB; g.sC = sC; g.sbias = sbias;
-  g.kchunk = (int)(sk_cdiv(sk_cdiv(K, splitk), bf2::BK) * bf2::BK);
-  splitk = (int)sk_cdiv(K, g.kchunk);
-  g.splitk = splitk;
-  g.slabs = ws ? (float*)((char*)ws + COUNTER_BYTES) : nullptr;  // (the head of a workspace belongs to the fp32 kernels' counters)
+  slice_k(g, splitk, bf2::BK);
+  g.slabs = ws_slabs(ws);  // (the head of a workspace belongs to the fp32 kernels' counters)
   g.counters = (unsigned*)ws; g.sk_tiles = 0; g.sk_full = 0;
   // splitk = 1 WITH a workspace (>= sk_gemm_streamk_workspace_bytes, zero-filled before its first use): the persistent
   // stream-K kernel where it applies (unbatched, 256-wide column tiles, at least 8 K steps) -- r03
-  bool streamk = splitk == 1 && ws && batch == 1 && M >= 256 && (N % 256 == 0 || N > 1024);
-  if (streamk) {
-    const int P = streamk_wgs();
-    const int64_t nt = sk_cdiv(M, bf2::BM) * sk_cdiv(N, 256), nk = K / bf2::BK;
-    g.sk_tiles = (int)nt;
-    g.sk_full = (int)(nt / P);
-    const int64_t rem = nt - (int64_t)g.sk_full * P, R = rem * nk;
-    if (P < 8 || nt >= (1 << 24) || nk < 8 || (R > 0 && R < P) || rem > 16384) streamk = false;
-  }
+  const bool cols256 = N % 256 == 0 || N > 1024;
+  const bool streamk = g.splitk == 1 && ws && batch == 1 && M >= 256 && cols256 &&
+                       streamk_cut(sk_cdiv(M, bf2::BM) * sk_cdiv(N, 256), K / bf2::BK, g.sk_tiles, g.sk_full);
   // 256-wide column tiles unless N is small enough that they would leave most of the chip idle
-  const int64_t tiles256 = sk_cdiv(M, bf2::BM) * sk_cdiv(N, 256) * splitk * batch;
-  const bool wide = streamk || ((N % 256 == 0 || N > 1024) && tiles256 >= 2 * 256);
-  const int bn = wide ? 256 : 128;
-  g.tilesN = (int)sk_cdiv(N, bn);
-  const int64_t tiles = sk_cdiv(M, bf2::BM) * g.tilesN;
+  const bool wide = streamk || (cols256 && sk_cdiv(M, bf2::BM) * sk_cdiv(N, 256) * g.splitk * batch >= 2 * 256);
+  const int kernel = streamk ? K_BF2_STREAMK : wide ? K_BF2_WIDE : K_BF2;
+  const KernelShape s = kernel_shape(kernel);
+  dim3 grid;
+  const int64_t tiles = tile_grid(g, s, batch, grid);
   SK_CHECK_ARG(tiles < (1ll << 31), "sk_gemm_bf16_mm: too many tiles");
-  dim3 grid((unsigned)tiles, (unsigned)splitk, (unsigned)batch);
   hipStream_t st = (hipStream_t)stream;
-  t_last_kernel = streamk ? 13 : wide ? 12 : 11;  // (sk_gemm_last_kernel: the bf16-operand kernels)
-#define SK_BF2_LAUNCH(BNV, AK, BKV) hipLaunchKernelGGL((bf2::gemm_bf16_nt_kernel<BNV, AK, BKV>), grid, dim3(bf2::NT), 0, st, g)
-#define SK_BF2_STREAMK(AK, BKV) \
-  hipLaunchKernelGGL((bf2::gemm_bf16_streamk_kernel<AK, BKV>), dim3((unsigned)streamk_wgs()), dim3(bf2::NT), 0, st, g)
-  if (streamk) {
-    if (!a_kmajor && !b_kmajor) SK_BF2_STREAMK(false, false);
-    else if (!a_kmajor) SK_BF2_STREAMK(false, true);
-    else if (!b_kmajor) SK_BF2_STREAMK(true, false);
-    else SK_BF2_STREAMK(true, true);
-  } else if (wide) {
-    if (!a_kmajor && !b_kmajor) SK_BF2_LAUNCH(256, false, false);
-    else if (!a_kmajor) SK_BF2_LAUNCH(256, false, true);
-    else if (!b_kmajor) SK_BF2_LAUNCH(256, true, false);
-    else SK_BF2_LAUNCH(256, true, true);
-  } else {
-    if (!a_kmajor && !b_kmajor) SK_BF2_LAUNCH(128, false, false);
-    else if (!a_kmajor) SK_BF2_LAUNCH(128, false, true);
-    else if (!b_kmajor) SK_BF2_LAUNCH(128, true, false);
-    else SK_BF2_LAUNCH(128, true, true);
-  }
-#undef SK_BF2_LAUNCH
-#undef SK_BF2_STREAMK
+  t_last_kernel = kernel;
+  hipLaunchKernelGGL(bf2_fn(kernel, a_kmajor, b_kmajor), grid, dim3(s.threads), 0, st, g);
   SK_CHECK_LAUNCH("sk_gemm_bf16_nt");
-  if (splitk > 1) {
-    GemmArgs r;
-    r.A = nullptr; r.B = nullptr; r.C = C; r.bias = bias;
-    r.M = M; r.N = N; r.K = K; r.lda = 0; r.ldb = 0; r.ldc = ldc;
-    r.accumulate = accumulate; r.act = act; r.vecA = r.vecB = 0; r.tilesN = g.tilesN;
-    r.splitk = splitk; r.kchunk = g.kchunk; r.slabs = g.slabs; r.counters = nullptr;
-    r.sA = 0; r.sB = 0; r.sC = sC; r.sbias = sbias;
-    const int64_t quads = sk_cdiv((int64_t)M * N, 4);
-    const unsigned nb = (unsigned)(sk_cdiv(quads, 256) > 2048 ? 2048 : sk_cdiv(quads, 256));
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb, 1, (unsigned)batch), dim3(256), 0, st, r);
-    SK_CHECK_LAUNCH("splitk_reduce_kernel");
-  }
-  return SK_OK;
+  return g.splitk > 1 ? reduce_slices(g, batch, st) : SK_OK;
 }
 
 // ---------------------------------------------------------------- operands that arrive split
@@ -2624,36 +2620,22 @@ extern "C" int sk_gemm_pl3_tn(const void* Apl, const void* Bpl, float* C, int M,
   g.Apl = (const __bf16*)Apl; g.Bpl = (const __bf16*)Bpl; g.planeA = planeA; g.planeB = planeB;
   g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
   g.accumulate = accumulate; g.act = 0; g.vecA = g.vecB = 1;
-  g.tilesN = (int)sk_cdiv(N, BN);
   g.sA = sA; g.sB = sB; g.sC = sC; g.sbias = 0;
-  g.sk_tiles = 0; g.sk_full = 0; g.flip_q = 0;
-  g.kchunk = (int)(sk_cdiv(sk_cdiv(K, splitk), BK) * BK);
-  splitk = (int)sk_cdiv(K, g.kchunk);
-  g.splitk = splitk;
-  if (SK_SPLIT_FLIP) {  // the sign-phase rule of gemm_launch: one pattern over the whole K
-    const int nks = K / BK;
-    if (nks >= 48) {
-      const int periods = (nks + 32) / 64;
-      g.flip_q = (nks + 4 * periods - 1) / (4 * periods);
-    }
-  }
-  const int64_t tiles = sk_cdiv(M, BM) * g.tilesN;
+  g.sk_tiles = 0; g.sk_full = 0;
+  slice_k(g, splitk, BK);
+  g.flip_q = flip_quarter(K);  // the split kernels' sign phases: one pattern over the whole K
+  const KernelShape s = kernel_shape(K_PL3);
+  dim3 grid;
+  const int64_t tiles = tile_grid(g, s, batch, grid);
   SK_CHECK_ARG(tiles < (1ll << 31), "sk_gemm_pl3_tn: too many tiles");
-  g.slabs = ws ? (float*)((char*)ws + COUNTER_BYTES) : nullptr;
-  const bool inkernel = splitk > 1 && tiles * batch * sizeof(unsigned) <= COUNTER_BYTES;
+  g.slabs = ws_slabs(ws);
+  const bool inkernel = reduce_in_kernel(g.splitk, tiles, batch);
   g.counters = inkernel ? (unsigned*)ws : nullptr;
-  dim3 grid((unsigned)tiles, (unsigned)splitk, (unsigned)batch);
   hipStream_t st = (hipStream_t)stream;
-  t_last_kernel = 14;
-  hipLaunchKernelGGL(gemm_f32_kernel_pl3, grid, dim3(256), 0, st, g);
+  t_last_kernel = K_PL3;
+  hipLaunchKernelGGL(gemm_f32_kernel_pl3, grid, dim3(s.threads), 0, st, g);
   SK_CHECK_LAUNCH("sk_gemm_pl3_tn");
-  if (splitk > 1 && !inkernel) {
-    const int64_t quads = sk_cdiv((int64_t)M * N, 4);
-    const unsigned nb = (unsigned)(sk_cdiv(quads, 256) > 2048 ? 2048 : sk_cdiv(quads, 256));
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb, 1, (unsigned)batch), dim3(256), 0, st, g);
-    SK_CHECK_LAUNCH("splitk_reduce_kernel");
-  }
-  return SK_OK;
+  return g.splitk > 1 && !inkernel ? reduce_slices(g, batch, st) : SK_OK;
 }
 
 extern "C" int sk_cast_bf16_rows(const float* src, int R, int C, int ld_src, void* dst, int ld_dst, int R_pad,

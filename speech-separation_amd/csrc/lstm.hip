@@ -1872,23 +1872,20 @@ int dispatch_bwd(int KS, bool bf, const BwdArgs& a, dim3 grid, hipStream_t st) {
   }
 }
 
-int num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) n = p.multiProcessorCount;
-  }
-  return n;
-}
-
 // Smallest number of batch groups per workgroup for which the whole grid (one workgroup per CU) is
 // co-resident; 0 if even GMAX groups per workgroup do not fit (then the caller launches per step).
 int groups_per_wg(int NUG, int NBG, int gmin, int wg_per_cu = 1) {
-  const int cus = num_cus();
+  const int cus = sk_num_cus();
   for (int g = (gmin < 1 ? 1 : gmin); g <= GMAX; ++g)
     if (NUG * ((NBG + g - 1) / g) * 2 <= cus * wg_per_cu) return g;
   return 0;
+}
+
+// XCD-local streams of 8 rows (mode bit 30, bf16) where the shape allows them: the 56-chunk instantiation (608 < H <= 896: 28
+// workgroups of 32 units per stream), at most 8 streams (B <= 32), a device of 8 XCDs x 32 CUs, a persistent launch; anything
+// else runs the ordinary form
+bool xl8_ok(bool xl8_bit, bool bf, int KS, int B, int gmin, int mode, bool fits) {
+  return xl8_bit && bf && KS == 56 && B <= 32 && gmin <= 1 && sk_num_cus() >= 256 && (mode == 1 || (mode == 0 && fits));
 }
 
 int check_common(const char* fn, int T, int B, int H, const float* whh, int mode) {
@@ -1977,14 +1974,11 @@ extern "C" int sk_lstm_fwd(const float* gx, const float* whh, const float* h0, c
   if (poll_delay == 0) poll_delay = nblocks >= 128 ? 8 : 4;
   if (poll_delay == 31) poll_delay = 0;
   a.map = map; a.nby = nby; a.opt = opt; a.poll_delay = poll_delay;
-  SK_CHECK_ARG(mode != 1 || fits, "sk_lstm_fwd: persistent mode cannot keep B=%d H=%d co-resident on %d CUs", B, H, num_cus());
+  SK_CHECK_ARG(mode != 1 || fits, "sk_lstm_fwd: persistent mode cannot keep B=%d H=%d co-resident on %d CUs", B, H, sk_num_cus());
   SK_CHECK_HIP(hipMemsetAsync(base + L.ctrl, 0, L.xbuf - L.ctrl, st));  // per-launch status word + flags (not the sticky word)
   if ((opt & 8) && mode != 2)  // tagged words: a new sequence must not find an old one's epochs in the buffers
     SK_CHECK_HIP(hipMemsetAsync(base + L.xbuf, 0, L.state - L.xbuf, st));
-  // XCD-local streams of 8 rows: where the shape allows it -- the 56-chunk instantiation (608 < H <= 896: 28 workgroups of 32 units
-  // per stream), at most 8 streams (B <= 32), a device of 8 XCDs x 32 CUs, a persistent launch; anything else runs the ordinary form
-  const bool xl8 = xl8_bit && bf && L.KS == 56 && B <= 32 && gmin <= 1 && num_cus() >= 256 && (mode == 1 || (mode == 0 && fits));
-  if (xl8) {
+  if (xl8_ok(xl8_bit, bf, L.KS, B, gmin, mode, fits)) {
     a.s_begin = 0; a.s_end = T;
     a.NBG = (B + 7) / 8;  // batch groups of EIGHT rows
     a.G = 1; a.nby = a.NBG;
@@ -2043,12 +2037,11 @@ extern "C" int sk_lstm_bwd(const float* dy, const float* dhn, const float* dcn, 
   if (poll_delay == 31) poll_delay = 0;
   a.map = map; a.nby = nby; a.poll_delay = poll_delay;
   dim3 grid((unsigned)L.KS, (unsigned)nby, 2);
-  SK_CHECK_ARG(mode != 1 || fits, "sk_lstm_bwd: persistent mode cannot keep B=%d H=%d co-resident on %d CUs", B, H, num_cus());
+  SK_CHECK_ARG(mode != 1 || fits, "sk_lstm_bwd: persistent mode cannot keep B=%d H=%d co-resident on %d CUs", B, H, sk_num_cus());
   SK_CHECK_HIP(hipMemsetAsync(base + L.ctrl, 0, L.xbuf - L.ctrl, st));
   if (dbias)  // (the kernels ADD their sums: a sequence advanced in step launches accumulates)
     SK_CHECK_HIP(hipMemsetAsync(dbias, 0, (size_t)L.NBG * 8 * H * sizeof(float), st));  // rows >= grid y stay 0
-  const bool xl8 = xl8_bit && bf && L.KS == 56 && B <= 32 && gmin <= 1 && num_cus() >= 256 && (mode == 1 || (mode == 0 && fits));
-  if (xl8) {  // (as sk_lstm_fwd's: 28 workgroups of 32 out units per (direction, 8-row group) stream, one XCD each)
+  if (xl8_ok(xl8_bit, bf, L.KS, B, gmin, mode, fits)) {  // (as sk_lstm_fwd's: 28 workgroups of 32 out units per (direction, 8-row group) stream, one XCD each)
     a.s_begin = 0; a.s_end = T; a.final_mm = want_d0;
     a.NBG = (B + 7) / 8;
     a.G = 1; a.nby = a.NBG;

@@ -15,6 +15,8 @@ int sk_fail(int code, const char* fmt, ...);
 // build-option bits of the translation units that carry diagnostic switches (sk_build_flags)
 unsigned sk_gemm_build_flags();
 unsigned sk_lstm_build_flags();
+// compute units of the current device, queried on first use and cached (0 while the query fails)
+int sk_num_cus();
 
 #define SK_CHECK_ARG(cond, ...)                          \
   do {                                                   \

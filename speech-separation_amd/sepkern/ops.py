@@ -82,9 +82,14 @@ def device_info():
 
 # ----------------------------------------------------------------------------- GEMM
 _NUM_CUS = None
-_STREAMK_BF16 = __import__('os').environ.get('SEPKERN_BF16_STREAMK', '1') != '0'
-_STREAMK = __import__('os').environ.get('SEPKERN_GEMM_STREAMK', '1') != '0'    # variant 0 may choose the stream-K kernel
-_SPLITK_MAX = int(__import__('os').environ.get('SEPKERN_SPLITK_MAX', '32'))   # diagnostic: cap the K slices
+
+
+def _num_cus():
+    """The device's CU count (queried once)."""
+    global _NUM_CUS
+    if _NUM_CUS is None:
+        _NUM_CUS = device_info()[0]
+    return _NUM_CUS
 
 
 def pick_splitk(M, N, K, batch=1):
@@ -92,16 +97,13 @@ def pick_splitk(M, N, K, batch=1):
     the matrix pipe of a CU is saturated by its resident 128x128 blocks, so time goes with the LARGEST number
     of blocks any CU gets, ceil(blocks / CUs); choose the slice count that minimises that quantisation loss
     plus the cost of writing and re-reading the partial slabs (measured: 1400 tiles on 256 CUs run at 91 %)."""
-    global _NUM_CUS
-    if _NUM_CUS is None:
-        _NUM_CUS = device_info()[0]
-    cus = _NUM_CUS
+    cus = _num_cus()
     tiles = ((M + 127) // 128) * ((N + 127) // 128) * batch
-    if tiles >= 16 * cus or K < 2048 or _SPLITK_MAX == 1:
+    if tiles >= 16 * cus or K < 2048:
         return 1
     work = 2.0 * M * N * K * batch / 140e12                      # seconds at the kernel's un-quantised rate
     best, best_t = 1, None
-    for s in range(1, min(33, _SPLITK_MAX + 1)):
+    for s in range(1, 33):
         if K // s < 512:
             break
         per_cu = tiles * s / cus
@@ -130,8 +132,8 @@ def gemm(A, B, Cout, M, N, K, lda, ldb, ldc, transA=False, transB=False, bias=No
     ws = None
     if splitk > 1:
         ws = workspace(_lib.load().sk_gemm_workspace_bytes(M, N, batch, splitk), ws_tag)
-    elif not bf16 and batch == 1 and (variant == 6 or (_STREAMK and M >= 4096 and N >= 1024 and
-                                                (variant == 0 or (variant == 8 and not transA)))):
+    elif not bf16 and batch == 1 and (variant == 6 or (M >= 4096 and N >= 1024 and
+                                                       (variant == 0 or (variant == 8 and not transA)))):
         ws = _streamk_ws()                                                              # pieces of the stream-K cut
     with _timed("gemm_bf16_kernel" if bf16 else "gemm_f32_kernel", 2.0 * M * N * K * batch) as rec:
         args = (_ptr(A), _ptr(B), _ptr(Cout), _ptr(bias), M, N, K, lda, ldb, ldc, int(transA), int(transB), int(accumulate),
@@ -217,21 +219,8 @@ def gemm_bf16_nt(A, B, Cout, M, N, K, lda, ldb, ldc, bias=None, accumulate=False
                  sbias=0, splitk=1, ws_tag="gemm", streamk=False):
     """Cout[M,N] = act(A[M,K] B[N,K]^T + bias (+ Cout)) with A, B bfloat16 tensors (K-contiguous, K % 64 == 0).
     streamk: as gemm_bf16_mm."""
-    _chk(A, torch.bfloat16)
-    _chk(B, torch.bfloat16)
-    _chk(Cout)
-    _chk(bias)
-    ws = None
-    if streamk and _STREAMK_BF16 and batch == 1 and splitk in (0, 1) and M >= 256 and (N % 256 == 0 or N > 1024) and K >= 512:
-        splitk = 1
-        ws = _streamk_ws()
-    if splitk == 0:
-        splitk = pick_splitk_bf16(M, N, K, batch)
-    if splitk > 1:
-        ws = workspace(_lib.load().sk_gemm_workspace_bytes(M, N, batch, splitk), ws_tag)
-    with _timed("gemm_bf16_nt_kernel", 2.0 * M * N * K * batch):
-        _lib.call("sk_gemm_bf16_nt", _ptr(A), _ptr(B), _ptr(Cout), _ptr(bias), M, N, K, lda, ldb, ldc, int(accumulate),
-                  int(act), batch, sA, sB, sC, sbias, int(splitk), _ptr(ws), _stream())
+    _gemm_bf16("sk_gemm_bf16_nt", (), A, B, Cout, M, N, K, lda, ldb, ldc, bias, accumulate, act, batch, sA, sB, sC, sbias,
+               splitk, ws_tag, streamk)
 
 
 def gemm_bf16_mm(A, B, Cout, M, N, K, lda, ldb, ldc, a_kmajor=False, b_kmajor=False, bias=None, accumulate=False, act=0, batch=1,
@@ -239,13 +228,20 @@ def gemm_bf16_mm(A, B, Cout, M, N, K, lda, ldb, ldc, a_kmajor=False, b_kmajor=Fa
     """Cout[M,N] = act(opA opB + bias (+ Cout)) on bfloat16 operands in memory, either of them optionally K-MAJOR
     (a_kmajor: A stored [K][M] with lda elements between k rows; b_kmajor: B stored [K][N]) -- sk_gemm_bf16_mm.  Row-major
     operands: K-contiguous as in gemm_bf16_nt.  K % 64 == 0.  streamk=True (unbatched products that have the chip to
-    themselves): the persistent stream-K kernel instead of K slices where it applies (SEPKERN_BF16_STREAMK=0: never)."""
+    themselves): the persistent stream-K kernel instead of K slices where it applies."""
+    _gemm_bf16("sk_gemm_bf16_mm", (int(a_kmajor), int(b_kmajor)), A, B, Cout, M, N, K, lda, ldb, ldc, bias, accumulate, act,
+               batch, sA, sB, sC, sbias, splitk, ws_tag, streamk)
+
+
+def _gemm_bf16(entry, kmajor, A, B, Cout, M, N, K, lda, ldb, ldc, bias, accumulate, act, batch, sA, sB, sC, sbias, splitk,
+               ws_tag, streamk):
+    """gemm_bf16_nt / gemm_bf16_mm through their own entry points (kmajor: the (a_kmajor, b_kmajor) arguments of _mm)."""
     _chk(A, torch.bfloat16)
     _chk(B, torch.bfloat16)
     _chk(Cout)
     _chk(bias)
     ws = None
-    if streamk and _STREAMK_BF16 and batch == 1 and splitk in (0, 1) and M >= 256 and (N % 256 == 0 or N > 1024) and K >= 512:
+    if streamk and batch == 1 and splitk in (0, 1) and M >= 256 and (N % 256 == 0 or N > 1024) and K >= 512:
         splitk = 1
         ws = _streamk_ws()
     if splitk == 0:
@@ -253,22 +249,20 @@ def gemm_bf16_mm(A, B, Cout, M, N, K, lda, ldb, ldc, a_kmajor=False, b_kmajor=Fa
     if splitk > 1:
         ws = workspace(_lib.load().sk_gemm_workspace_bytes(M, N, batch, splitk), ws_tag)
     with _timed("gemm_bf16_nt_kernel", 2.0 * M * N * K * batch):
-        _lib.call("sk_gemm_bf16_mm", _ptr(A), _ptr(B), _ptr(Cout), _ptr(bias), M, N, K, lda, ldb, ldc, int(a_kmajor), int(b_kmajor),
-                  int(accumulate), int(act), batch, sA, sB, sC, sbias, int(splitk), _ptr(ws), _stream())
+        _lib.call(entry, _ptr(A), _ptr(B), _ptr(Cout), _ptr(bias), M, N, K, lda, ldb, ldc, *kmajor, int(accumulate), int(act),
+                  batch, sA, sB, sC, sbias, int(splitk), _ptr(ws), _stream())
 
 
 def pick_splitk_bf16(M, N, K, batch=1):
     """K slices for the 256 x 256-tile bf16 kernel (one block per CU): enough blocks to fill the chip about twice,
     slices of at least 1024."""
-    global _NUM_CUS
-    if _NUM_CUS is None:
-        _NUM_CUS = device_info()[0]
+    cus = _num_cus()
     tiles = ((M + 255) // 256) * ((N + 255) // 256) * batch
     best, best_t = 1, None
     for s in range(1, 17):
         if K // s < 1024 and s > 1:
             break
-        rounds = -(-(tiles * s) // _NUM_CUS)
+        rounds = -(-(tiles * s) // cus)
         t = rounds / s + (0.0 if s == 1 else 0.02 * s)       # time ~ rounds x K/s, plus the slab round trip
         if best_t is None or t < best_t * 0.98:
             best, best_t = s, t
