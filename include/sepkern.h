@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 132
+#define SK_VERSION 133
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -39,12 +39,13 @@ typedef void* sk_stream_t; /* hipStream_t */
 int sk_version(void);
 const char* sk_last_error(void);
 /* Which numerics- or timing-changing build options this library was compiled with: 0 for the product build (plain `make`).
- * The kernel sources carry ablation / timing-only / tuning switches for the measurement scripts under profiles/ (`make variant`,
+ * The kernel sources carry arithmetic / tuning / stamp switches for the measurement scripts under profiles/ (`make variant`,
  * `make gemm_variant` build them into libsepkern_<name>.so next to the product library); a library built with any of them
  * reports it here, and the ctypes loader refuses it unless SEPKERN_ALLOW_DIAGNOSTIC_LIB=1 (sepkern/_lib.py), bench.py unless
  * --diagnostic -- a headline can then not come from a wrong-numerics build by accident. */
-#define SK_BUILD_TIMING_ONLY 0x1 /* results WRONG by construction (work skipped or faked to bound a kernel's time)        */
-#define SK_BUILD_ARITH 0x2       /* another arithmetic than documented (nine piece products, no sign phases, ...)          */
+#define SK_BUILD_TIMING_ONLY 0x1 /* results WRONG by construction (work skipped or faked to bound a kernel's time): reserved --
+                                    no switch of the product sources sets it; an investigation kept under profiles/ may   */
+#define SK_BUILD_ARITH 0x2       /* another arithmetic than documented (no sign phases, ...)                               */
 #define SK_BUILD_TUNING 0x4      /* same results, other tuning constants (LDS stages, ring depths, poll cadence, ...)      */
 #define SK_BUILD_STAMPS 0x8      /* per-phase clock stamps in the recurrence kernels                                       */
 unsigned sk_build_flags(void);
@@ -140,7 +141,8 @@ size_t sk_gemm_workspace_bytes(int M, int N, int batch, int splitk);
  * in); sk_gemm_bf16_nt / _mm: 11 / 12 the 256 x 128 / 256 x 256-tile bf16-operand kernel, 13 its stream-K form; sk_gemm_pl3_tn: 14;
  * 0 before the first launch.
  * A thread-local read-back: with the error string of sk_last_error() the library's only mutable state that is not a caller's
- * buffer (SURVEY 8b's rule has these two exceptions, both thread-local and neither read by any kernel or launch decision). */
+ * buffer (SURVEY 8b's rule has these exceptions -- sk_lstm_last_launch() is the third --, all thread-local and none read by any
+ * kernel or launch decision). */
 int sk_gemm_last_kernel(void);
 size_t sk_gemm_streamk_workspace_bytes(void);
 /* Zero the ticket counters at the head of a split-K workspace (once, before its first use; a buffer that was allocated
@@ -246,14 +248,27 @@ int sk_hprev_rows(const float* y, int ldy, const float* h0, const int32_t* offs,
  *   gates (T,B,2,4H)  post-activation i,f,g,o (gate-interleaved like gx) and cs (T,B,2,H) cell states, saved
  *                     for the backward pass (both NULL for inference)
  *   ws    workspace of sk_lstm_workspace_bytes(); zeroed by the call itself
- * mode (low byte): 0 auto, 1 persistent (one launch, flag-synchronised time loop), 2 one launch per step.
- * mode bits 8..15: minimum number of 16-row batch groups a workgroup carries (0/1 = as few as fit): a larger
- * value shrinks the persistent grid, leaving CUs free for kernels running concurrently on other streams.
- * Speed-only variants of the persistent kernels (never the arithmetic, except where noted): bit 16 bf16 matrix-core
- * inputs (this one IS arithmetic: BASELINE configs[3]); bit 17 retired in r05 (8-unit / 256-thread workgroups, two per CU: slower at every shape; setting it is SK_EINVAL); bits 18..19
- * block id -> stream map; bit 20 one polling wave per workgroup; bit 21 flags replicated per XCD; bit 22 one flag per
- * 128-byte line; bits 23..27 hold-back of a step's first poll in units of 0.1 us (0 = the library's choice, 31 = none);
- * bit 28 (fp32 forward, H <= 896): the product h W_hh^T by the EXACT three-way bf16 split of both fp32
+ * mode: a word of the SK_LSTM_* fields below, the same word for sk_lstm_fwd and sk_lstm_bwd except where noted.  Everything
+ * but the launch kind, SK_LSTM_BF16 and SK_LSTM_SPLIT3 / _TAGGED is speed only (never the arithmetic).
+ *   launch kind (low byte)  SK_LSTM_AUTO: persistent where the grid is co-resident, else per step; SK_LSTM_PERSISTENT: one launch
+ *                           with a flag-synchronised time loop (SK_EINVAL if the grid does not fit); SK_LSTM_PER_STEP
+ *   SK_LSTM_GMIN(g)         minimum number of 16-row batch groups a workgroup carries (0/1 = as few as fit, at most 8): a larger
+ *                           value shrinks the persistent grid, leaving CUs free for kernels running concurrently on other streams
+ *   SK_LSTM_BF16            bf16 matrix-core inputs (this one IS arithmetic: BASELINE configs[3])
+ *   SK_LSTM_BWD_EXCLUSIVE   BACKWARD (r06): the instantiation whose LDS footprint (127 KB) leaves no room for a workgroup of
+ *                           sk_gemm_pl3_tn beside it, so that products enqueued on other streams take the CUs the grid leaves free
+ *                           instead of sharing the recurrence's (without it and with one batch group per workgroup: 113 KB, such a
+ *                           workgroup fits).  FORWARD: the same bit was the 8-unit / 256-thread workgroup form, retired in r05
+ *                           (slower at every shape); setting it is SK_EINVAL
+ *   SK_LSTM_MAP(m)          block id -> stream map, 0..3
+ *   SK_LSTM_POLL1           forward: one polling wave per workgroup.  Backward: ignored (one wave polls always)
+ *   SK_LSTM_REPFLAGS        forward: flags replicated per XCD; cleared by SK_LSTM_FLAG_PER_LINE.  Backward: ignored
+ *   SK_LSTM_FLAG_PER_LINE   one flag per 128-byte line
+ *   SK_LSTM_DELAY(d)        hold-back of a step's first poll in units of 0.1 us, 1..30; SK_LSTM_DELAY_NONE (31): none.  0: FORWARD
+ *                           the library's choice (by grid size), BACKWARD none
+ *   SK_LSTM_SPLIT3, SK_LSTM_TAGGED   forward, fp32 (below); ignored with SK_LSTM_BF16 and by the backward
+ *   SK_LSTM_XL8             XCD-local streams (below)
+ * SK_LSTM_SPLIT3 (fp32 forward, H <= 896): the product h W_hh^T by the EXACT three-way bf16 split of both fp32
  * operands on the bf16 matrix pipe -- x = hi + mid + lo with three bf16 pieces (24 significand bits = 3 x 8); of the nine piece
  * products per element pair (each exact in fp32) the six of relative size >= 2^-16 are added into fp32 accumulators by
  * v_mfma_f32_16x16x32_bf16, the three of size <= 2^-24 -- together at most 2^-23 of |w||h|, see sk_gemm_f32_splitk variant 0 --
@@ -264,24 +279,41 @@ int sk_hprev_rows(const float* y, int ldy, const float* h0, const int32_t* offs,
  * other up -- the cell state integrates over the sequence what is left of it (tests/test_gpu_signed_error.py: 400 steps
  * against an fp64 recurrence).  The engine ships it for the fp32 forward recurrence (bench.py's config.numerics
  * names it);
- * bit 29 (fp32 forward; not together with bit 28): "the data is the flag" -- every exchanged h word carries the step's epoch
+ * SK_LSTM_TAGGED (fp32 forward; not together with SK_LSTM_SPLIT3): "the data is the flag" -- every exchanged h word carries the step's epoch
  * in its two low mantissa bits, producers publish without drain / barrier / flag, consumers hold back, pull, check every word
  * and pull again what was not complete; the next step's product runs on the tagged words (<= 3 ulp = 3.6e-7 relative),
  * everything stored (y, gates, cs, states) is exact.  The r03 default; still the engine's choice for H > 896;
- * bit 30 (bf16 forward with bit 16, persistent launches, 608 < H <= 896, B <= 32, a device of 8 XCDs x 32 CUs; ignored otherwise;
+ * SK_LSTM_XL8 (with SK_LSTM_BF16, both directions, persistent launches, 608 < H <= 896, B <= 32, a device of 8 XCDs x 32 CUs; ignored otherwise;
  * r06): XCD-LOCAL streams of 8 rows -- every (direction, 8-row batch group) stream is 28 workgroups of 32 hidden units on ONE
  * XCD, h_t published with plain stores and a plain flag (within an XCD the L2 is the coherence point; polls and pulls stay sc1),
  * 14 KB instead of 28 KB pulled per workgroup and step.  Same arithmetic bit for bit.  A workgroup joins the stream of the XCD it
  * runs on (HW_REG_XCC_ID + one counter per XCD): no dependence on the order in which blocks are dealt; an XCD that received fewer
- * than 28 workgroups ends in the bounded-spin status word (sk_lstm_status: SK_ETIMEOUT, the step is skipped). */
+ * than 28 workgroups ends in the bounded-spin status word (sk_lstm_status: SK_ETIMEOUT, the step is skipped).
+ */
+#define SK_LSTM_AUTO 0
+#define SK_LSTM_PERSISTENT 1
+#define SK_LSTM_PER_STEP 2
+#define SK_LSTM_KIND(mode) ((mode) & 0xff)
+#define SK_LSTM_GMIN_SHIFT 8 /* bits 8..15 */
+#define SK_LSTM_GMIN(g) (((g) & 0xff) << SK_LSTM_GMIN_SHIFT)
+#define SK_LSTM_BF16 (1 << 16)
+#define SK_LSTM_BWD_EXCLUSIVE (1 << 17)
+#define SK_LSTM_MAP_SHIFT 18 /* bits 18..19 */
+#define SK_LSTM_MAP(m) (((m) & 3) << SK_LSTM_MAP_SHIFT)
+#define SK_LSTM_POLL1 (1 << 20)
+#define SK_LSTM_REPFLAGS (1 << 21)
+#define SK_LSTM_FLAG_PER_LINE (1 << 22)
+#define SK_LSTM_DELAY_SHIFT 23 /* bits 23..27 */
+#define SK_LSTM_DELAY(d) (((d) & 31) << SK_LSTM_DELAY_SHIFT)
+#define SK_LSTM_DELAY_NONE 31
+#define SK_LSTM_SPLIT3 (1 << 28)
+#define SK_LSTM_TAGGED (1 << 29)
+#define SK_LSTM_XL8 (1 << 30)
 size_t sk_lstm_workspace_bytes(int T, int B, int H);
 int sk_lstm_fwd(const float* gx, const float* whh, const float* h0, const float* c0, const int32_t* lens,
                 const int32_t* offs, float* y, float* gates, float* cs, float* hn, float* cn, void* ws,
                 int T, int B, int H, int mode, sk_stream_t stream);
-/* Backward of the recurrence.  mode as sk_lstm_fwd (bits 0..7, 8..15, 16, 18..19, 22, 23..27, 30; bit 29: read by timing-only
- * diagnostic builds alone); bit 17 (speed only, r06): EXCLUSIVE -- the instantiation whose LDS footprint (127 KB) leaves no room
- * for a workgroup of sk_gemm_pl3_tn beside it, so that products enqueued on other streams take the CUs the grid leaves free instead
- * of sharing the recurrence's (without the bit and with one batch group per workgroup: 113 KB, such a workgroup fits).
+/* Backward of the recurrence.  mode: the SK_LSTM_* word above, read as its BACKWARD notes say.
  * dy (T,B,2H) is the gradient of the layer output, dhn / dcn (2,B,H; either may be NULL = 0)
  * the gradient wrt the final state (the RSH arch carries the hidden state from pass to pass, reference archs/RSH.py:172);
  * produces dgx (T,B,2,4H) = gradient of the gate pre-activations (gate-interleaved like gx; padded layout: zero at padded
@@ -309,6 +341,24 @@ int sk_lstm_bwd(const float* dy, const float* dhn, const float* dcn, const float
  * the GEMMs) is made in the same pass.  dbias of sk_lstm_bwd is already gate-major. */
 int sk_gate_rows(const float* src, float* dst, int nblk, int H, int C, int ld_src, int ld_dst, int back, int accumulate,
                  sk_stream_t stream);
+/* What the calling thread's LAST sk_lstm_fwd / sk_lstm_bwd call launched (tests/test_gpu_lstm_choice.py pins it case by case,
+ * tests/test_gpu_census.py generates DESIGN.md's kernel census from it).  Returns the number of kernel launches the call made
+ * (1 persistent; T per step, + 1 for the backward's dh0 / dc0 product; 0 before the first call or when the call returned an
+ * argument error) and fills out[SK_LSTM_Q_*]; a thread-local read-back like sk_gemm_last_kernel(). */
+#define SK_LSTM_Q_FAMILY 0    /* SK_LSTM_K_* below; with KS, BF16, PACKED (and GM) it names the template instantiation */
+#define SK_LSTM_Q_KS 1        /* 16-unit groups per direction: 20, 38 (fp32) / 40 (bf16, split3), 56, 64 */
+#define SK_LSTM_Q_BF16 2
+#define SK_LSTM_Q_PACKED 3    /* the call passed `offs` */
+#define SK_LSTM_Q_GM 4        /* lstm_bwd_kernel's batch groups a workgroup MAY carry, 1 or 8 (0 for every other family) */
+#define SK_LSTM_Q_EXCLUSIVE 5 /* the call asked for SK_LSTM_BWD_EXCLUSIVE */
+#define SK_LSTM_Q_BLOCKS 6    /* workgroups per launch */
+#define SK_LSTM_Q_G 7         /* batch groups a workgroup carries */
+#define SK_LSTM_K_FWD 1        /* lstm_fwd_kernel<KS, BF16, 8, false, PACKED> */
+#define SK_LSTM_K_FWD_SPLIT3 2 /* lstm_fwd_kernel<KS, false, 8, true, PACKED> */
+#define SK_LSTM_K_FWD_XL8 3    /* lstm_fwd_xl8_kernel<56, PACKED> */
+#define SK_LSTM_K_BWD 4        /* lstm_bwd_kernel<KS, BF16, GM> */
+#define SK_LSTM_K_BWD_XL8 5    /* lstm_bwd_xl8_kernel<56> */
+int sk_lstm_last_launch(int out[8]);
 /* Word 0 of the workspace is a STICKY status word: a launch whose bounded spin gave up sets it (no launch clears
  * it; allocate the workspace zeroed).  Its address can be handed to sk_grad_norm as `guard` (as a float: any
  * non-zero bit pattern counts) so that a failed launch never reaches the weights, without a host sync per step.

@@ -404,9 +404,7 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_kernel_dma(GemmArgs g) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       dma_1k(srcA[i], my_pieces + buf * 2 * TILE + i * 1024);
-#ifndef SK_ABL_HALFDMA  // (SK_ABL_*: ablation builds for tools/gemm_bench.py, `make gemm_variant`: results wrong by construction)
       dma_1k(srcB[i], my_pieces + buf * 2 * TILE + TILE + i * 1024);
-#endif
       srcA[i] += stepA;
       srcB[i] += stepB;
     }
@@ -427,16 +425,12 @@ __global__ __launch_bounds__(256, 3) void gemm_f32_kernel_dma(GemmArgs g) {
   if (NST == 3 && nk > 1) stage(1);
   int cur = 0;
   for (int kt = 0; kt < nk; ++kt) {
-#ifndef SK_ABL_NOBAR
     if (NST == 3 && kt + 1 < nk)
       asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // step kt has landed; the 4 instructions of step kt + 1 may still fly
     else
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of step kt have landed ...
     __syncthreads();                                   // ... and everybody's; all reads of the buffer refilled next are done
-#endif
-#ifndef SK_ABL_NODMA
     if (kt + NST - 1 < nk) stage(NST == 3 ? (cur + 2) % 3 : cur ^ 1);
-#endif
     const char* ai = lds[cur];
     const char* bi = lds[cur] + TILE;
 #pragma unroll
@@ -601,14 +595,6 @@ struct Split3 {
 // Operands beyond bf16's finite range (|x| > 3.39e38) round to inf.
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ Split3 split3(const float (&v)[8]) {
-#ifdef SK_SPLIT_FREE  // TIMING-ONLY diagnostic (wrong numerics): the pieces cost nothing -- an upper bound for a kernel that finds them ready in LDS
-  typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-  Split3 f;
-  f.hi = __builtin_bit_cast(bf16x8_t, (u32x4_){__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])});
-  f.mid = __builtin_bit_cast(bf16x8_t, (u32x4_){__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])});
-  f.lo = __builtin_bit_cast(bf16x8_t, (u32x4_){__float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[5]), __float_as_uint(v[6])});
-  return f;
-#endif
   unsigned h[4], m[4], l[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -630,12 +616,7 @@ __device__ __forceinline__ Split3 split3(const float (&v)[8]) {
 }
 
 __device__ __forceinline__ void mma6(f32x16& acc, const Split3& a, const Split3& b) {
-  // the SIX piece products, small terms first (it is one fp32 accumulator either way); SK_SPLIT_NINE: all nine (diagnostic build)
-#ifdef SK_SPLIT_NINE
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.lo, b.lo, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.lo, b.mid, acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.mid, b.lo, acc, 0, 0, 0);
-#endif
+  // the SIX piece products, small terms first (it is one fp32 accumulator either way)
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.lo, b.hi, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.hi, b.lo, acc, 0, 0, 0);
   acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a.mid, b.mid, acc, 0, 0, 0);
@@ -906,7 +887,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_kernel_streamk(GemmArgs g) {
 // operand element to split it (other waves' products run meanwhile).  Measured (one MI355X, stand-alone): 160-168 TFLOP/s
 // fp32-equivalent on the training step's large products against 124-135 of the fp32-MFMA kernels (whose pipe peaks at 157);
 // sustained it is POWER-bound: 181 TFLOP/s at 1.9 GHz and 1375 W of the 1400 W cap (the fp32-MFMA kernels: 126-130 at 2.39 GHz,
-// 1140-1260 W).  (-DSK_SPLIT_NINE builds all nine products: 130 TFLOP/s, the r03 form.)  Operand tiles are DMA'd into LDS as
+// 1140-1260 W).  (All nine products: 130 TFLOP/s, the r03 form.)  Operand tiles are DMA'd into LDS as
 // fp32 exactly as in gemm_f32_kernel_dma; the K order is the natural one (lane holds k = 8 (lane>>5) .. +7 of its row, the
 // bf16 MFMA's fragment shape).  Non-finite inputs: x = +-inf splits into (inf, nan, nan): such a product is NaN where an fp32
 // FMA gives +-inf; |x| > 3.39e38 rounds to inf.
@@ -1025,22 +1006,7 @@ __global__ __launch_bounds__(256, SK_SPLIT_OCC) void gemm_f32_kernel_split3(Gemm
       vb0[j] = p0[0]; vb0[j + 1] = p0[1];
       vb1[j] = p1[0]; vb1[j + 1] = p1[1];
     }
-#ifdef SK_SPLIT_FREE_TN  // TIMING-ONLY diagnostic (wrong, finite numerics): the T/N form (weight gradients) finds its pieces for free
-    auto sp = [&](const float (&v)[8]) {
-      if constexpr (TA && !TB) {
-        typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
-        Split3 f;
-        f.hi = __builtin_bit_cast(bf16x8_t, (u32x4_){__float_as_uint(v[0]) & 0x3f7f3f7fu, __float_as_uint(v[1]) & 0x3f7f3f7fu, __float_as_uint(v[2]) & 0x3f7f3f7fu, __float_as_uint(v[3]) & 0x3f7f3f7fu});
-        f.mid = __builtin_bit_cast(bf16x8_t, (u32x4_){__float_as_uint(v[4]) & 0x3f7f3f7fu, __float_as_uint(v[5]) & 0x3f7f3f7fu, __float_as_uint(v[6]) & 0x3f7f3f7fu, __float_as_uint(v[7]) & 0x3f7f3f7fu});
-        f.lo = f.hi;
-        return f;
-      } else {
-        return split3(v);
-      }
-    };
-#else
     auto sp = [&](const float (&v)[8]) { return split3(v); };
-#endif
     const Split3 a0 = sp(va0), b0 = sp(vb0);
     mma6(acc[0][0], a0, b0);
     const Split3 a1 = sp(va1);
@@ -2655,12 +2621,6 @@ extern "C" int sk_gemm_last_kernel(void) { return t_last_kernel; }
 // The numerics- or timing-changing macros this translation unit was built with (sk_build_flags, include/sepkern.h)
 unsigned sk_gemm_build_flags() {
   unsigned f = 0;
-#if defined(SK_SPLIT_FREE) || defined(SK_SPLIT_FREE_TN) || defined(SK_ABL_HALFDMA) || defined(SK_ABL_NOBAR) || defined(SK_ABL_NODMA)
-  f |= SK_BUILD_TIMING_ONLY;
-#endif
-#ifdef SK_SPLIT_NINE
-  f |= SK_BUILD_ARITH;
-#endif
   if (SK_SPLIT_FLIP != 1) f |= SK_BUILD_ARITH;
   if (SK_SPLIT_NST != 2 || SK_SPLIT_OCC != 2 || SK_PLANES_SCHED != 4) f |= SK_BUILD_TUNING;
   return f;

@@ -217,8 +217,6 @@ struct BwdArgs {
   int ld_bf;
   long long pl_bf;  // 0: one bf16 copy (rounded: the bf16 configuration's operand); > 0 (fp32 kernel): THREE planes this many elements
                     // apart -- the exact hi / mid / lo pieces of dgx, the operand sk_gemm_pl3_tn reads ("operands that arrive split")
-  int fast;  // mode bit 29: read by the timing-only build -DSK_BWD_BOUND38 alone
-  int exclusive;  // mode bit 17: the instantiation with the larger LDS footprint (no GEMM workgroup fits beside it), see launch_bwd
 };
 
 // Flag replication (opt bit 1): every producer raises its flag in NREP copies with ONE store instruction (NREP lanes,
@@ -655,9 +653,6 @@ __global__ __launch_bounds__(NW * 64, 2) void lstm_fwd_kernel(FwdArgs a) {
       f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
       {
         const float* hp = &hs[(kh * NQ) * 256 + lane * 4];
-#ifdef SK_TAIL_HALF
-        const bool tail = PK && B > 16 && s >= a.lens[16];  // see SK_TAIL_HALF at BwdCfg
-#endif
 #if SK_FWD_RING > 0
         if constexpr (S3) {
           // The 3 NQ fragment reads of the product (piece lo, mid, hi of chunk 0, 1, ...) through a ring of SK_FWD_RING + 1
@@ -680,9 +675,6 @@ __global__ __launch_bounds__(NW * 64, 2) void lstm_fwd_kernel(FwdArgs a) {
             if (i + D < NR) ring[(i + D) % (D + 1)] = rd(i + D);
             const bf16x8 hv = ring[i % (D + 1)];
             const int q = i / 3;
-#ifdef SK_UNITS12_BOUND  // TIMING-ONLY (wrong numerics): three quarters of the product -- what a 12-unit workgroup would multiply
-            if ((q & 3) == 3) continue;
-#endif
             if (i % 3 == 0) {
               acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1[q], hv, acc0, 0, 0, 0);  // hi  * lo
             } else if (i % 3 == 1) {
@@ -709,12 +701,6 @@ __global__ __launch_bounds__(NW * 64, 2) void lstm_fwd_kernel(FwdArgs a) {
 #endif
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
-#ifdef SK_TAIL_HALF
-          if (tail && (q & 1)) continue;
-#endif
-#ifdef SK_UNITS12_BOUND
-          if ((q & 3) == 3) continue;
-#endif
           if (S3) {
             // SIX of the nine piece products per 32 k (see split3 above), the small ones first.  The piece that is needed first is
             // fetched first and the products alternate between the two accumulators (no product waits for the one issued just
@@ -1088,37 +1074,11 @@ struct BwdW {
   bf16x8 b[BF ? BwdCfg<KS, BF>::NQ : 1];
 };
 
-// TIMING-ONLY diagnostic (-DSK_TAIL_HALF, `make variant NAME=tailhalf DEFS=-DSK_TAIL_HALF`; never shipped, WRONG numerics): an
-// upper bound for re-partitioning the tail of a ragged batch.  Once the short batch group's streams have left the grid (the long
-// group's steps s >= lens[16], B = 32), the long group's workgroups issue only every other MFMA chunk -- what a step's product
-// would cost if the 112 idle CUs took half of it for free (same launches, same hand-off, same pulls).
-#ifdef SK_TAIL_HALF
-#define SK_TAIL_SKIP(j) if (tail && ((j) & 1)) continue;
-#else
-#define SK_TAIL_SKIP(j)
-#endif
-
 template <int KS, bool BF, int SBI>
-__device__ __forceinline__ void bwd_consume(const BwdW<KS, BF>& W, const float* ring, int lane, f32x4& acc0, f32x4& acc1,
-                                            bool tail) {
+__device__ __forceinline__ void bwd_consume(const BwdW<KS, BF>& W, const float* ring, int lane, f32x4& acc0, f32x4& acc1) {
   using C = BwdCfg<KS, BF>;
   constexpr int n = C::cnt(SBI);
   const float* src = ring + (SBI % C::DEPTH) * C::SB * 256 + lane * 4;
-#ifdef SK_BWD_BOUND38
-  // TIMING-ONLY diagnostic (-DSK_BWD_BOUND38, never shipped, WRONG numerics): launches that pass mode bit 29 issue three of every
-  // eight MFMAs of the product -- the matrix-pipe time six bf16 piece products would take (96 instead of 256 cycles per 32 k'),
-  // with the pieces for free: an upper bound for a split-product form of this kernel (profiles/r06_bwd_split_top_layer.txt)
-  if (!BF && tail) {
-#pragma unroll
-    for (int j = 0; j < n; ++j) {
-      const float4 db = *reinterpret_cast<const float4*>(src + j * 256);
-      const int q = SBI * C::SB + j;
-      acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(W.f[4 * q + 0], db.x, acc0, 0, 0, 0);
-      if (!(j & 1)) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(W.f[4 * q + 1], db.y, acc1, 0, 0, 0);
-    }
-    return;
-  }
-#endif
 #if SK_BWD_RING > 0
   if constexpr (!BF && n > 0 && KS <= 56) {  // (KS = 64: 4 more registers would pass the 192 this kernel must stay under)
     // fp32: the fragment read of chunk j + 1 is issued before the four MFMAs of chunk j (the compiler's order: read, wait, four
@@ -1132,9 +1092,6 @@ __device__ __forceinline__ void bwd_consume(const BwdW<KS, BF>& W, const float* 
       if (j + 1 < n) rg[(j + 1) & 1] = *reinterpret_cast<const float4*>(src + (j + 1) * 256);
       const float4 db = rg[j & 1];
       const int q = SBI * C::SB + j;
-#ifdef SK_UNITS12_BOUND
-      if ((q & 3) == 3) continue;
-#endif
       acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(W.f[4 * q + 0], db.x, acc0, 0, 0, 0);
       acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(W.f[4 * q + 1], db.y, acc1, 0, 0, 0);
       acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(W.f[4 * q + 2], db.z, acc0, 0, 0, 0);
@@ -1151,7 +1108,6 @@ __device__ __forceinline__ void bwd_consume(const BwdW<KS, BF>& W, const float* 
 #endif
 #pragma unroll
   for (int j = 0; j < n; ++j) {
-    SK_TAIL_SKIP(j)
     const int q = SBI * C::SB + j;
     if (BF) {
       const bf16x8 db = *reinterpret_cast<const bf16x8*>(src + j * 256);  // dG[b = lane&15][k' = 32 cc + 8 (lane>>4) + 0..7]
@@ -1187,12 +1143,12 @@ __device__ __forceinline__ void bwd_prologue(const float* xbase, unsigned xoff, 
 // still be in flight), multiply, and refill its slot with sub-block I+DEPTH.
 template <int KS, bool BF, int I>
 __device__ __forceinline__ void bwd_ring(const BwdW<KS, BF>& wreg, const float* xbase, unsigned xoff, float* ring,
-                                         unsigned ring_lds, int w, int lane, f32x4& acc0, f32x4& acc1, bool tail) {
+                                         unsigned ring_lds, int w, int lane, f32x4& acc0, f32x4& acc1) {
   using C = BwdCfg<KS, BF>;
   if constexpr (I < C::NSB) {
     constexpr int younger = bwd_younger<KS, BF>(I);
     wait_vmcnt<younger>();
-    bwd_consume<KS, BF, I>(wreg, ring, lane, acc0, acc1, tail);
+    bwd_consume<KS, BF, I>(wreg, ring, lane, acc0, acc1);
     if constexpr (I + C::DEPTH < C::NSB) {
       if constexpr (C::cnt(I + C::DEPTH) > 0) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // all reads of this ring slot returned before it is refilled
@@ -1200,7 +1156,7 @@ __device__ __forceinline__ void bwd_ring(const BwdW<KS, BF>& wreg, const float* 
         bwd_issue<KS, BF, I + C::DEPTH>(xbase, xoff, ring_lds, w, lane);
       }
     }
-    bwd_ring<KS, BF, I + 1>(wreg, xbase, xoff, ring, ring_lds, w, lane, acc0, acc1, tail);
+    bwd_ring<KS, BF, I + 1>(wreg, xbase, xoff, ring, ring_lds, w, lane, acc0, acc1);
   }
 }
 
@@ -1213,7 +1169,7 @@ __device__ __forceinline__ int red_slot(int m, int n) { return (m >> 1) * 32 + 1
 // Returns, for the cell-owning lanes, sum over all k' of dG * W for their (unit, batch).
 template <int KS, bool BF>
 __device__ __forceinline__ float bwd_matmul(const BwdW<KS, BF>& wreg, const float* xbase, unsigned xoff, float* ring,
-                                            float (*red)[256], int w, int lane, bool tail = false) {
+                                            float (*red)[256], int w, int lane) {
   // xbase: the exchange buffer (kernel argument: scalar), xoff: byte offset of this stream's block of the step (uniform)
   const unsigned ring_lds = __builtin_amdgcn_readfirstlane((int)(unsigned)(uintptr_t)(__attribute__((address_space(3))) float*)ring);
   f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
@@ -1221,7 +1177,7 @@ __device__ __forceinline__ float bwd_matmul(const BwdW<KS, BF>& wreg, const floa
   // nothing may be scheduled into this region (the cell loads of the step were issued before it).
   __builtin_amdgcn_sched_barrier(0);
   bwd_prologue<KS, BF, 0>(xbase, xoff, ring_lds, w, lane);
-  bwd_ring<KS, BF, 0>(wreg, xbase, xoff, ring, ring_lds, w, lane, acc0, acc1, tail);
+  bwd_ring<KS, BF, 0>(wreg, xbase, xoff, ring, ring_lds, w, lane, acc0, acc1);
   __builtin_amdgcn_sched_barrier(0);
   // D row m = 4*(lane>>4) + reg (out unit), col n = lane&15 (batch)
 #pragma unroll
@@ -1380,13 +1336,7 @@ __global__ __launch_bounds__(NTHREADS, 2) __attribute__((amdgpu_num_vgpr(192))) 
           break;
         }
         SK_STAMP(0);
-#ifdef SK_TAIL_HALF
-        dh_rec = bwd_matmul<KS, BF>(wreg, a.xbuf, xo, ring, red, w, lane, a.offs && B > 16 && s >= a.lens[16]);
-#elif defined(SK_BWD_BOUND38)
-        dh_rec = bwd_matmul<KS, BF>(wreg, a.xbuf, xo, ring, red, w, lane, a.fast != 0);
-#else
         dh_rec = bwd_matmul<KS, BF>(wreg, a.xbuf, xo, ring, red, w, lane);
-#endif
         SK_STAMP(2);
       }
       // 3. cell backward (owner waves)
@@ -1796,104 +1746,126 @@ __global__ __launch_bounds__(256) void gate_rows_kernel(const float* __restrict_
   }
 }
 
-template <int KS, bool BF>
-int launch_fwd(const FwdArgs& a, int nblocks, hipStream_t st) {
-  if (a.offs)
-    hipLaunchKernelGGL((lstm_fwd_kernel<KS, BF, 8, false, true>), dim3((unsigned)nblocks), dim3(512), 0, st, a);
-  else
-    hipLaunchKernelGGL((lstm_fwd_kernel<KS, BF, 8>), dim3((unsigned)nblocks), dim3(512), 0, st, a);
-  return 0;
-}
-template <int KS>
-void launch_fwd_s3(const FwdArgs& a, int nblocks, hipStream_t st) {
-  if (a.offs)
-    hipLaunchKernelGGL((lstm_fwd_kernel<KS, false, 8, true, true>), dim3((unsigned)nblocks), dim3(512), 0, st, a);
-  else
-    hipLaunchKernelGGL((lstm_fwd_kernel<KS, false, 8, true, false>), dim3((unsigned)nblocks), dim3(512), 0, st, a);
-}
-template <int KS, bool BF>
-int launch_bwd(const BwdArgs& a, dim3 grid, hipStream_t st) {
-  // G = 1: the instantiation that keeps 113 KB of LDS -- a workgroup of gemm_f32_kernel_pl3 (48 KB) fits beside it and the weight
-  // gradients run CO-RESIDENT with the recurrence.  a.exclusive (mode bit 17) selects the 127 KB one instead: only a 32 KB split3
-  // workgroup would fit, the pl3 kernel does not -- the recurrence keeps its CUs to itself and the weight gradients take the CUs the
-  // grid leaves free.  The engine asks for that on RAGGED batches: once the short batch group's streams have left the grid, half
-  // the chip is idle for the rest of the launch and the weight gradients run there for free, while co-resident they only slow the
-  // long group's chain (measured, profiles/r06_wgrad_planes.txt: ragged 28.98 -> 28.48 ms exclusive, 29.40 co-resident; uniform
-  // 28.27 -> 27.95 co-resident, 28.11 exclusive).
-  if (a.G == 1 && !a.exclusive)
-    hipLaunchKernelGGL((lstm_bwd_kernel<KS, BF, 1>), dim3(grid.x * grid.y * grid.z), dim3(NTHREADS), 0, st, a);
-  else
-    hipLaunchKernelGGL((lstm_bwd_kernel<KS, BF, GMAX>), dim3(grid.x * grid.y * grid.z), dim3(NTHREADS), 0, st, a);
-  return 0;
-}
+// The recurrences' `mode` word (include/sepkern.h, SK_LSTM_*) as the host code reads it; the ONE place that decodes it.
+struct Mode {
+  int kind, gmin, map;
+  int poll_delay;  // units of 0.1 us; 0 = none, -1 = the library chooses (sk_lstm_fwd, by grid size)
+  bool bf, exclusive, poll1, repflags, flag_per_line, s3, tagged, xl8;
+};
 
-void launch_fwd_xl8(const FwdArgs& a, hipStream_t st) {  // bf16, 608 < H <= 896 (KS = 56): 8 XCDs x 32 blocks
-  if (a.offs)
-    hipLaunchKernelGGL((lstm_fwd_xl8_kernel<56, true>), dim3(256), dim3(512), 0, st, a);
-  else
-    hipLaunchKernelGGL((lstm_fwd_xl8_kernel<56, false>), dim3(256), dim3(512), 0, st, a);
-}
-
-int dispatch_fwd_s3(int KS, const FwdArgs& a, int nblocks, hipStream_t st) {
-  switch (KS) {
-    case 20: launch_fwd_s3<20>(a, nblocks, st); break;
-    case 40: launch_fwd_s3<40>(a, nblocks, st); break;
-    default: launch_fwd_s3<56>(a, nblocks, st); break;
-  }
-  return 0;
-}
-
-int dispatch_fwd(int KS, bool bf, const FwdArgs& a, int nblocks, hipStream_t st) {
-  if (bf) switch (KS) {
-      case 20: return launch_fwd<20, true>(a, nblocks, st);
-      case 40: return launch_fwd<40, true>(a, nblocks, st);
-      case 56: return launch_fwd<56, true>(a, nblocks, st);
-      default: return launch_fwd<64, true>(a, nblocks, st);
-    }
-  switch (KS) {
-    case 20: return launch_fwd<20, false>(a, nblocks, st);
-    case 38: return launch_fwd<38, false>(a, nblocks, st);
-    case 56: return launch_fwd<56, false>(a, nblocks, st);
-    default: return launch_fwd<64, false>(a, nblocks, st);
-  }
-}
-int dispatch_bwd(int KS, bool bf, const BwdArgs& a, dim3 grid, hipStream_t st) {
-  if (bf) switch (KS) {
-      case 20: return launch_bwd<20, true>(a, grid, st);
-      case 40: return launch_bwd<40, true>(a, grid, st);
-      case 56: return launch_bwd<56, true>(a, grid, st);
-      default: return launch_bwd<64, true>(a, grid, st);
-    }
-  switch (KS) {
-    case 20: return launch_bwd<20, false>(a, grid, st);
-    case 38: return launch_bwd<38, false>(a, grid, st);
-    case 56: return launch_bwd<56, false>(a, grid, st);
-    default: return launch_bwd<64, false>(a, grid, st);
-  }
+int decode_mode(const char* fn, bool backward, int mode, int H, Mode& m) {
+  m.kind = SK_LSTM_KIND(mode);
+  m.gmin = (mode >> SK_LSTM_GMIN_SHIFT) & 0xff;  // (frees CUs for concurrent kernels)
+  SK_CHECK_ARG(m.kind <= SK_LSTM_PER_STEP && m.gmin <= GMAX && (mode >> 31) == 0, "%s: unknown mode %d", fn, mode);
+  m.bf = mode & SK_LSTM_BF16;
+  m.exclusive = mode & SK_LSTM_BWD_EXCLUSIVE;
+  SK_CHECK_ARG(backward || !m.exclusive, "%s: mode bit 17 (8-unit / 256-thread workgroups) was retired in r05", fn);
+  m.map = (mode >> SK_LSTM_MAP_SHIFT) & 3;
+  m.flag_per_line = mode & SK_LSTM_FLAG_PER_LINE;
+  // forward only; flag replication was measured in the backward too (7.59 -> 7.50 us/step) and not kept
+  m.poll1 = !backward && (mode & SK_LSTM_POLL1);
+  m.repflags = !backward && (mode & SK_LSTM_REPFLAGS) && !m.flag_per_line;  // (the flag block is sized for either, not both)
+  m.s3 = !backward && (mode & SK_LSTM_SPLIT3) && !m.bf && pick_ks(H, true) != 64;  // (KS = 64: 168 + 88 registers do not fit)
+  m.tagged = !backward && (mode & SK_LSTM_TAGGED) && !m.bf && !m.s3;
+  m.xl8 = mode & SK_LSTM_XL8;
+  m.poll_delay = (mode >> SK_LSTM_DELAY_SHIFT) & 31;
+  if (m.poll_delay == SK_LSTM_DELAY_NONE) m.poll_delay = 0;
+  else if (m.poll_delay == 0 && !backward) m.poll_delay = -1;  // (backward: 0 = none until measured otherwise)
+  return SK_OK;
 }
 
 // Smallest number of batch groups per workgroup for which the whole grid (one workgroup per CU) is
 // co-resident; 0 if even GMAX groups per workgroup do not fit (then the caller launches per step).
-int groups_per_wg(int NUG, int NBG, int gmin, int wg_per_cu = 1) {
+int groups_per_wg(int NUG, int NBG, int gmin) {
   const int cus = sk_num_cus();
   for (int g = (gmin < 1 ? 1 : gmin); g <= GMAX; ++g)
-    if (NUG * ((NBG + g - 1) / g) * 2 <= cus * wg_per_cu) return g;
+    if (NUG * ((NBG + g - 1) / g) * 2 <= cus) return g;
   return 0;
 }
 
-// XCD-local streams of 8 rows (mode bit 30, bf16) where the shape allows them: the 56-chunk instantiation (608 < H <= 896: 28
-// workgroups of 32 units per stream), at most 8 streams (B <= 32), a device of 8 XCDs x 32 CUs, a persistent launch; anything
-// else runs the ordinary form
-bool xl8_ok(bool xl8_bit, bool bf, int KS, int B, int gmin, int mode, bool fits) {
-  return xl8_bit && bf && KS == 56 && B <= 32 && gmin <= 1 && sk_num_cus() >= 256 && (mode == 1 || (mode == 0 && fits));
+// The launch plan of one recurrence call, either direction.
+struct Plan {
+  WsLayout L;
+  int NBG, G, nby, blocks;  // batch groups, groups per workgroup, workgroups along the batch, workgroups per launch
+  bool fits;                // the ordinary grid is co-resident (one workgroup per CU)
+  bool persistent;          // one launch with a flag-synchronised time loop; else one launch per step
+  bool xl8;                 // the XCD-local form
+};
+
+Plan plan_launch(const Mode& m, int B, int H) {
+  Plan p;
+  p.L = ws_layout(B, H, m.bf || m.s3);  // (S3 exchanges bf16 images: the bf16 unit-group counts)
+  const int g = groups_per_wg(p.L.KS, p.L.NBG, m.gmin);
+  p.fits = g > 0;
+  p.persistent = m.kind == SK_LSTM_PERSISTENT || (m.kind == SK_LSTM_AUTO && p.fits);
+  // XCD-local streams of 8 rows (SK_LSTM_XL8, bf16) where the shape allows them: the 56-chunk instantiation (608 < H <= 896: 28
+  // workgroups of 32 units per stream), at most 8 streams (B <= 32), a device of 8 XCDs x 32 CUs, a persistent launch; anything
+  // else runs the ordinary form
+  p.xl8 = m.xl8 && m.bf && p.L.KS == 56 && B <= 32 && m.gmin <= 1 && sk_num_cus() >= 256 && p.persistent;
+  p.NBG = p.xl8 ? (B + 7) / 8 : p.L.NBG;  // (xl8: batch groups of EIGHT rows, one per workgroup)
+  p.G = p.fits && !p.xl8 ? g : 1;
+  p.nby = (p.NBG + p.G - 1) / p.G;
+  p.blocks = p.xl8 ? 256 : p.L.KS * p.nby * 2;  // (xl8: 8 XCDs x 32 blocks)
+  return p;
 }
 
-int check_common(const char* fn, int T, int B, int H, const float* whh, int mode) {
+typedef void (*FwdKernel)(FwdArgs);
+typedef void (*BwdKernel)(BwdArgs);
+
+int ks_index(int KS) { return KS == 20 ? 0 : KS < 56 ? 1 : KS == 56 ? 2 : 3; }  // 20, 38 / 40, 56, 64
+
+FwdKernel fwd_kernel(const Plan& p, const Mode& m, bool packed) {
+#define SK_PAIR(KS, BF, S3) {lstm_fwd_kernel<KS, BF, 8, S3, false>, lstm_fwd_kernel<KS, BF, 8, S3, true>}  // padded, packed
+  static const FwdKernel plain[2][4][2] = {
+      {SK_PAIR(20, false, false), SK_PAIR(38, false, false), SK_PAIR(56, false, false), SK_PAIR(64, false, false)},
+      {SK_PAIR(20, true, false), SK_PAIR(40, true, false), SK_PAIR(56, true, false), SK_PAIR(64, true, false)}};
+  static const FwdKernel split3[3][2] = {SK_PAIR(20, false, true), SK_PAIR(40, false, true), SK_PAIR(56, false, true)};
+#undef SK_PAIR
+  static const FwdKernel xl8[2] = {lstm_fwd_xl8_kernel<56, false>, lstm_fwd_xl8_kernel<56, true>};  // bf16, 608 < H <= 896
+  const int k = ks_index(p.L.KS);
+  return p.xl8 ? xl8[packed] : m.s3 ? split3[k][packed] : plain[m.bf][k][packed];
+}
+
+// GM = 1: the instantiation that keeps 113 KB of LDS -- a workgroup of gemm_f32_kernel_pl3 (48 KB) fits beside it and the weight
+// gradients run CO-RESIDENT with the recurrence.  SK_LSTM_BWD_EXCLUSIVE selects the 127 KB one instead: only a 32 KB split3
+// workgroup would fit, the pl3 kernel does not -- the recurrence keeps its CUs to itself and the weight gradients take the CUs the
+// grid leaves free.  The engine asks for that on RAGGED batches: once the short batch group's streams have left the grid, half
+// the chip is idle for the rest of the launch and the weight gradients run there for free, while co-resident they only slow the
+// long group's chain (measured, profiles/r06_wgrad_planes.txt: ragged 28.98 -> 28.48 ms exclusive, 29.40 co-resident; uniform
+// 28.27 -> 27.95 co-resident, 28.11 exclusive).
+int bwd_gm(const Plan& p, const Mode& m) { return p.xl8 ? 0 : p.G == 1 && !m.exclusive ? 1 : GMAX; }
+
+BwdKernel bwd_kernel(const Plan& p, const Mode& m) {
+#define SK_PAIR(KS, BF) {lstm_bwd_kernel<KS, BF, 1>, lstm_bwd_kernel<KS, BF, GMAX>}
+  static const BwdKernel plain[2][4][2] = {{SK_PAIR(20, false), SK_PAIR(38, false), SK_PAIR(56, false), SK_PAIR(64, false)},
+                                           {SK_PAIR(20, true), SK_PAIR(40, true), SK_PAIR(56, true), SK_PAIR(64, true)}};
+#undef SK_PAIR
+  return p.xl8 ? lstm_bwd_xl8_kernel<56> : plain[m.bf][ks_index(p.L.KS)][bwd_gm(p, m) == GMAX];
+}
+
+thread_local int t_last[8];  // what this thread's last sk_lstm_fwd / sk_lstm_bwd launched: sk_lstm_last_launch()
+thread_local int t_last_launches = 0;
+
+void clear_last() {
+  for (int& v : t_last) v = 0;
+  t_last_launches = 0;
+}
+void record_plan(int family, const Plan& p, const Mode& m, bool packed, int gm) {
+  t_last[SK_LSTM_Q_FAMILY] = family; t_last[SK_LSTM_Q_KS] = p.L.KS; t_last[SK_LSTM_Q_BF16] = m.bf;
+  t_last[SK_LSTM_Q_PACKED] = packed; t_last[SK_LSTM_Q_GM] = gm; t_last[SK_LSTM_Q_EXCLUSIVE] = m.exclusive;
+  t_last[SK_LSTM_Q_BLOCKS] = p.blocks; t_last[SK_LSTM_Q_G] = p.G;
+}
+
+// What both entry points check and decide before they touch the stream: sizes, the mode word, the plan.
+int check_and_plan(const char* fn, bool backward, int T, int B, int H, const float* whh, int mode, Mode& m, Plan& p) {
   SK_CHECK_ARG(T > 0 && B > 0 && H > 0, "%s: bad sizes T=%d B=%d H=%d", fn, T, B, H);
   SK_CHECK_ARG(H % 4 == 0 && H <= 1024, "%s: hidden size %d must be a multiple of 4 and <= 1024", fn, H);
   SK_CHECK_ARG(((uintptr_t)whh % 16) == 0, "%s: whh must be 16-byte aligned", fn);
-  SK_CHECK_ARG((mode & 0xff) >= 0 && (mode & 0xff) <= 2 && ((mode >> 8) & 0xff) <= GMAX && (mode >> 31) == 0,
-               "%s: unknown mode %d", fn, mode);
+  const int rc = decode_mode(fn, backward, mode, H, m);
+  if (rc) return rc;
+  p = plan_launch(m, B, H);
+  SK_CHECK_ARG(m.kind != SK_LSTM_PERSISTENT || p.fits, "%s: persistent mode cannot keep B=%d H=%d co-resident on %d CUs", fn, B, H,
+               sk_num_cus());
   return SK_OK;
 }
 
@@ -1902,15 +1874,6 @@ int check_common(const char* fn, int T, int B, int H, const float* whh, int mode
 // The numerics- or timing-changing macros this translation unit was built with (sk_build_flags, include/sepkern.h)
 unsigned sk_lstm_build_flags() {
   unsigned f = 0;
-#ifdef SK_TAIL_HALF
-  f |= SK_BUILD_TIMING_ONLY;
-#endif
-#ifdef SK_BWD_BOUND38
-  f |= SK_BUILD_TIMING_ONLY;
-#endif
-#ifdef SK_UNITS12_BOUND
-  f |= SK_BUILD_TIMING_ONLY;
-#endif
 #ifdef SK_LSTM_STAMPS
   f |= SK_BUILD_STAMPS;
 #endif
@@ -1931,30 +1894,25 @@ extern "C" size_t sk_lstm_workspace_bytes(int T, int B, int H) {
   return a > b ? a : b;
 }
 
+extern "C" int sk_lstm_last_launch(int out[8]) {
+  if (out)
+    for (int i = 0; i < 8; ++i) out[i] = t_last[i];
+  return t_last_launches;
+}
+
 extern "C" int sk_lstm_fwd(const float* gx, const float* whh, const float* h0, const float* c0, const int32_t* lens,
                            const int32_t* offs, float* y, float* gates, float* cs, float* hn, float* cn, void* ws, int T,
                            int B, int H, int mode, sk_stream_t stream) {
+  clear_last();
   SK_CHECK_ARG(gx && whh && h0 && c0 && lens && y && ws, "sk_lstm_fwd: null pointer");
   SK_CHECK_ARG((gates == nullptr) == (cs == nullptr), "sk_lstm_fwd: gates and cs must be given together");
   SK_CHECK_ARG(((uintptr_t)h0 % 16) == 0, "sk_lstm_fwd: h0 must be 16-byte aligned");
   SK_CHECK_ARG(((uintptr_t)gx % 16) == 0 && ((uintptr_t)gates % 16) == 0, "sk_lstm_fwd: gx / gates must be 16-byte aligned");
-  int rc = check_common("sk_lstm_fwd", T, B, H, whh, mode);
+  Mode m;
+  Plan p;
+  const int rc = check_and_plan("sk_lstm_fwd", false, T, B, H, whh, mode, m, p);
   if (rc) return rc;
-  const int gmin = (mode >> 8) & 0xff;  // bits 8..15: minimum batch groups per workgroup (frees CUs for concurrent kernels)
-  const bool bf = (mode >> 16) & 1;     // bit 16: bf16 matrix-core inputs
-  SK_CHECK_ARG(!((mode >> 17) & 1), "sk_lstm_fwd: mode bit 17 (8-unit / 256-thread workgroups) was retired in r05");
-  const int map = (mode >> 18) & 3;     // bits 18..19: block id -> stream assignment (speed only)
-  int opt = (mode >> 20) & 7;     // bit 20: one polling wave per workgroup; bit 21: flags replicated per XCD;
-                                        // bit 22: one flag per 128-byte line
-  if (opt & 4) opt &= ~2;              // one flag per line: no replicas on top (the flag block is sized for either)
-  // bit 28 (fp32): the product by the exact three-way bf16 split on the bf16 matrix pipe (S3)
-  const bool s3 = ((mode >> 28) & 1) && !bf && pick_ks(H, true) != 64;  // (KS = 64: 168 + 88 registers do not fit)
-  const bool tagged = ((mode >> 29) & 1) && !bf && !s3;  // bit 29 (fp32)
-  if (tagged) opt |= 8;                // the data is the flag (lstm_fwd_kernel)
-  int poll_delay = (mode >> 23) & 31;  // bits 23..27: FwdArgs::poll_delay, units of 0.1 us; 0 = choose, 31 = none
-  const bool xl8_bit = (mode >> 30) & 1;  // bit 30 (bf16): XCD-local streams of 8 rows (lstm_fwd_xl8_kernel)
-  mode &= 0xff;
-  const WsLayout L = ws_layout(B, H, bf || s3);  // (S3 exchanges bf16 images: the bf16 unit-group counts)
+  const WsLayout& L = p.L;
   hipStream_t st = (hipStream_t)stream;
   char* base = (char*)ws;
   FwdArgs a;
@@ -1962,36 +1920,22 @@ extern "C" int sk_lstm_fwd(const float* gx, const float* whh, const float* h0, c
   a.y = y; a.gates = gates; a.cs = cs; a.hn = hn; a.cn = cn;
   a.xbuf = (float*)(base + L.xbuf); a.state = (float*)(base + L.state);
   a.flags = (unsigned*)(base + L.flags); a.ctrl = (unsigned*)(base + L.ctrl);
-  a.T = T; a.B = B; a.H = H; a.NBG = L.NBG;
-  const int NUG = L.KS;
-  const int G = groups_per_wg(NUG, L.NBG, gmin, 1);
-  const bool fits = G > 0;
-  a.G = fits ? G : 1;
-  const int nby = (L.NBG + a.G - 1) / a.G;
-  const int nblocks = NUG * nby * 2;
+  a.T = T; a.B = B; a.H = H; a.NBG = p.NBG; a.G = p.G;
+  a.map = m.map; a.nby = p.nby;
+  a.opt = m.poll1 | m.repflags << 1 | m.flag_per_line << 2 | m.tagged << 3;  // (bit 3: the data is the flag, lstm_fwd_kernel)
   // hold-back of the first poll after one's own flag store (wait_flags): 0.8 us on a full grid, 0.4 us on a small one
   // (fewer flag stores to land); measured optimum for H 896/1024 (0.8) and H 256/300 (0.4), no effect at 2x600 / B = 100
-  if (poll_delay == 0) poll_delay = nblocks >= 128 ? 8 : 4;
-  if (poll_delay == 31) poll_delay = 0;
-  a.map = map; a.nby = nby; a.opt = opt; a.poll_delay = poll_delay;
-  SK_CHECK_ARG(mode != 1 || fits, "sk_lstm_fwd: persistent mode cannot keep B=%d H=%d co-resident on %d CUs", B, H, sk_num_cus());
+  a.poll_delay = m.poll_delay < 0 ? (p.blocks >= 128 ? 8 : 4) : m.poll_delay;
+  if (p.xl8 && a.poll_delay == 8) a.poll_delay = 4;  // (a stream's flag stores land sooner: the small-grid hold-back)
   SK_CHECK_HIP(hipMemsetAsync(base + L.ctrl, 0, L.xbuf - L.ctrl, st));  // per-launch status word + flags (not the sticky word)
-  if ((opt & 8) && mode != 2)  // tagged words: a new sequence must not find an old one's epochs in the buffers
+  if (m.tagged && m.kind != SK_LSTM_PER_STEP)  // tagged words: a new sequence must not find an old one's epochs in the buffers
     SK_CHECK_HIP(hipMemsetAsync(base + L.xbuf, 0, L.state - L.xbuf, st));
-  if (xl8_ok(xl8_bit, bf, L.KS, B, gmin, mode, fits)) {
-    a.s_begin = 0; a.s_end = T;
-    a.NBG = (B + 7) / 8;  // batch groups of EIGHT rows
-    a.G = 1; a.nby = a.NBG;
-    if (poll_delay == 8) a.poll_delay = 4;  // (a stream's flag stores land sooner: the small-grid hold-back)
-    launch_fwd_xl8(a, st);
-  } else if (mode == 1 || (mode == 0 && fits)) {
-    a.s_begin = 0; a.s_end = T;
-    s3 ? dispatch_fwd_s3(L.KS, a, nblocks, st) : dispatch_fwd(L.KS, bf, a, nblocks, st);
-  } else {  // one launch per step: the state travels through the workspace
-    for (int s = 0; s < T; ++s) {
-      a.s_begin = s; a.s_end = s + 1;
-      s3 ? dispatch_fwd_s3(L.KS, a, nblocks, st) : dispatch_fwd(L.KS, bf, a, nblocks, st);
-    }
+  const FwdKernel kern = fwd_kernel(p, m, offs != nullptr);
+  record_plan(p.xl8 ? SK_LSTM_K_FWD_XL8 : m.s3 ? SK_LSTM_K_FWD_SPLIT3 : SK_LSTM_K_FWD, p, m, offs != nullptr, 0);
+  // persistent: one launch; else one launch per step, the state travels through the workspace
+  for (int s = 0; s < (p.persistent ? 1 : T); ++s, ++t_last_launches) {
+    a.s_begin = s; a.s_end = p.persistent ? T : s + 1;
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.blocks), dim3(NTHREADS), 0, st, a);
   }
   SK_CHECK_LAUNCH("sk_lstm_fwd");
   return SK_OK;
@@ -2001,64 +1945,40 @@ extern "C" int sk_lstm_bwd(const float* dy, const float* dhn, const float* dcn, 
                            const float* cs, const float* c0, const int32_t* lens, const int32_t* offs, float* dgx,
                            float* dh0, float* dc0, float* dbias, void* dgx_bf16, int ld_bf16, int64_t plane_bf16, void* ws, int T,
                            int B, int H, int mode, sk_stream_t stream) {
+  clear_last();
   SK_CHECK_ARG(dy && whh && gates && cs && c0 && lens && dgx && ws, "sk_lstm_bwd: null pointer");
   SK_CHECK_ARG(!dgx_bf16 || (ld_bf16 >= 8 * H && ld_bf16 % 4 == 0 && ((uintptr_t)dgx_bf16 % 8) == 0 && plane_bf16 >= 0 && plane_bf16 % 4 == 0),
                "sk_lstm_bwd: bf16 twin needs ld >= 8H, ld %% 4 == 0, 8-byte alignment, plane stride %% 4");
   SK_CHECK_ARG(((uintptr_t)gates % 16) == 0 && ((uintptr_t)dgx % 16) == 0, "sk_lstm_bwd: gates / dgx must be 16-byte aligned");
-  int rc = check_common("sk_lstm_bwd", T, B, H, whh, mode);
+  Mode m;
+  Plan p;
+  const int rc = check_and_plan("sk_lstm_bwd", true, T, B, H, whh, mode, m, p);
   if (rc) return rc;
-  const int gmin = (mode >> 8) & 0xff;
-  const bool bf = (mode >> 16) & 1;
-  // block map as sk_lstm_fwd (+4: one flag per 128-byte line, mode bit 22); flag replication was measured here too
-  // (7.59 -> 7.50 us/step) and not kept
-  const int map = ((mode >> 18) & 3) | (((mode >> 22) & 1) << 2);
-  int poll_delay = (mode >> 23) & 31;  // as sk_lstm_fwd; 0 = none here until measured otherwise
-  const int fast = (mode >> 29) & 1;   // (diagnostic builds only, BwdArgs::fast)
-  const bool xl8_bit = (mode >> 30) & 1;  // bit 30 (bf16): XCD-local streams of 8 rows (lstm_bwd_xl8_kernel)
-  const int exclusive = (mode >> 17) & 1;  // bit 17: keep the CUs to the recurrence (launch_bwd)
-  mode &= 0xff;
-  const WsLayout L = ws_layout(B, H, bf);
+  SK_CHECK_ARG(!plane_bf16 || !m.bf, "sk_lstm_bwd: planes of dgx are the fp32 configuration's (mode bit 16 = bf16 inputs is set)");
+  const WsLayout& L = p.L;
   hipStream_t st = (hipStream_t)stream;
   char* base = (char*)ws;
   BwdArgs a;
   a.dy = dy; a.whh = whh; a.gates = gates; a.cs = cs; a.c0 = c0; a.lens = lens; a.offs = offs;
   a.dgx = dgx; a.dh0 = dh0; a.dc0 = dc0; a.dhn = dhn; a.dcn = dcn;
   a.dbias = dbias;
-  a.dgx_bf = (__bf16*)dgx_bf16; a.ld_bf = ld_bf16; a.pl_bf = plane_bf16; a.fast = fast; a.exclusive = exclusive;
-  SK_CHECK_ARG(!plane_bf16 || !bf, "sk_lstm_bwd: planes of dgx are the fp32 configuration's (mode bit 16 = bf16 inputs is set)");
+  a.dgx_bf = (__bf16*)dgx_bf16; a.ld_bf = ld_bf16; a.pl_bf = plane_bf16;
   a.xbuf = (float*)(base + L.xbuf); a.state = (float*)(base + L.state);
   a.flags = (unsigned*)(base + L.flags); a.ctrl = (unsigned*)(base + L.ctrl);
-  a.T = T; a.B = B; a.H = H; a.NBG = L.NBG;
-  const int want_d0 = (dh0 || dc0) ? 1 : 0;
-  const int G = groups_per_wg(L.KS, L.NBG, gmin);
-  const bool fits = G > 0;
-  a.G = fits ? G : 1;
-  const int nby = (L.NBG + a.G - 1) / a.G;
-  if (poll_delay == 31) poll_delay = 0;
-  a.map = map; a.nby = nby; a.poll_delay = poll_delay;
-  dim3 grid((unsigned)L.KS, (unsigned)nby, 2);
-  SK_CHECK_ARG(mode != 1 || fits, "sk_lstm_bwd: persistent mode cannot keep B=%d H=%d co-resident on %d CUs", B, H, sk_num_cus());
+  a.T = T; a.B = B; a.H = H; a.NBG = p.NBG; a.G = p.G;
+  a.map = m.map | m.flag_per_line << 2; a.nby = p.nby; a.poll_delay = m.poll_delay;
   SK_CHECK_HIP(hipMemsetAsync(base + L.ctrl, 0, L.xbuf - L.ctrl, st));
   if (dbias)  // (the kernels ADD their sums: a sequence advanced in step launches accumulates)
     SK_CHECK_HIP(hipMemsetAsync(dbias, 0, (size_t)L.NBG * 8 * H * sizeof(float), st));  // rows >= grid y stay 0
-  if (xl8_ok(xl8_bit, bf, L.KS, B, gmin, mode, fits)) {  // (as sk_lstm_fwd's: 28 workgroups of 32 out units per (direction, 8-row group) stream, one XCD each)
-    a.s_begin = 0; a.s_end = T; a.final_mm = want_d0;
-    a.NBG = (B + 7) / 8;
-    a.G = 1; a.nby = a.NBG;
-    hipLaunchKernelGGL((lstm_bwd_xl8_kernel<56>), dim3(256), dim3(NTHREADS), 0, st, a);
-  } else if (mode == 1 || (mode == 0 && fits)) {
-    a.s_begin = 0; a.s_end = T; a.final_mm = want_d0;
-    dispatch_bwd(L.KS, bf, a, grid, st);
-  } else {
-    a.final_mm = 0;  // a step launch never waits on other workgroups
-    for (int s = 0; s < T; ++s) {
-      a.s_begin = s; a.s_end = s + 1;
-      dispatch_bwd(L.KS, bf, a, grid, st);
-    }
-    if (want_d0) {
-      a.s_begin = T; a.s_end = T; a.final_mm = 1;
-      dispatch_bwd(L.KS, bf, a, grid, st);
-    }
+  const BwdKernel kern = bwd_kernel(p, m);
+  record_plan(p.xl8 ? SK_LSTM_K_BWD_XL8 : SK_LSTM_K_BWD, p, m, offs != nullptr, bwd_gm(p, m));
+  const bool want_d0 = dh0 || dc0;  // gradient wrt the initial state: one more product after the last step
+  // persistent: one launch, dh0 / dc0 included; else one per step (a step launch never waits on other workgroups) and one for them
+  const int nlaunch = p.persistent ? 1 : T + want_d0;
+  for (int s = 0; s < nlaunch; ++s, ++t_last_launches) {
+    a.s_begin = s; a.s_end = p.persistent ? T : s < T ? s + 1 : T;
+    a.final_mm = want_d0 && (p.persistent || s == T);
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.blocks), dim3(NTHREADS), 0, st, a);
   }
   SK_CHECK_LAUNCH("sk_lstm_bwd");
   return SK_OK;

@@ -623,9 +623,37 @@ def lstm_ws(T, B, H):
     return workspace(n, "lstm")
 
 
+# Fields of sk_lstm_fwd's / sk_lstm_bwd's `mode` word: include/sepkern.h's SK_LSTM_* names (what each means and which direction
+# reads it is written there).  The low byte is the launch kind.
+LSTM_AUTO, LSTM_PERSISTENT, LSTM_PER_STEP = 0, 1, 2
+LSTM_GMIN_SHIFT = 8                 # bits 8..15
+LSTM_BF16 = 1 << 16
+LSTM_BWD_EXCLUSIVE = 1 << 17        # backward; the forward's retired `half`
+LSTM_MAP_SHIFT = 18                 # bits 18..19
+LSTM_POLL1 = 1 << 20
+LSTM_REPFLAGS = 1 << 21
+LSTM_FLAG_PER_LINE = 1 << 22
+LSTM_DELAY_SHIFT = 23               # bits 23..27
+LSTM_DELAY_NONE = 31
+LSTM_SPLIT3 = 1 << 28
+LSTM_TAGGED = 1 << 29
+LSTM_XL8 = 1 << 30
+# sk_lstm_last_launch(): indices of its eight values, and the kernel families
+LSTM_Q_FAMILY, LSTM_Q_KS, LSTM_Q_BF16, LSTM_Q_PACKED, LSTM_Q_GM, LSTM_Q_EXCLUSIVE, LSTM_Q_BLOCKS, LSTM_Q_G = range(8)
+LSTM_K_FWD, LSTM_K_FWD_SPLIT3, LSTM_K_FWD_XL8, LSTM_K_BWD, LSTM_K_BWD_XL8 = 1, 2, 3, 4, 5
+
+
+def lstm_gmin(g):
+    return (int(g) & 0xff) << LSTM_GMIN_SHIFT
+
+
+def lstm_map(m):
+    return (int(m) & 3) << LSTM_MAP_SHIFT
+
+
 def lstm_variant_bits(half=False, blockmap=0, poll1=False, repflags=False, spread=False, poll_delay=0, tagged=False, split3=False,
                       xl8=False):
-    """Geometry / protocol variants of the persistent recurrence (speed only; include/sepkern.h, mode bits 17..29);
+    """Geometry / protocol variants of the persistent recurrence (speed only; include/sepkern.h, SK_LSTM_*);
     poll_delay: the forward kernel's polling wave holds its first poll of a step back (units of 0.1 us, 0 = the library's
     choice, 31 = none); tagged (forward, fp32): the exchanged h carries the step's epoch in its two low mantissa bits and
     nothing else is signalled (mode bit 29); split3 (forward, fp32): the product h W_hh^T by the exact three-way bf16 split
@@ -635,9 +663,26 @@ def lstm_variant_bits(half=False, blockmap=0, poll1=False, repflags=False, sprea
     if half:      # (the first field of SEPKERN_LSTM_FWD / _BWD keeps its place so that recorded switch strings stay readable)
         raise _lib.SepkernError("the 8-unit / 256-thread forward recurrence (field `half`, mode bit 17) was retired in r05: "
                                 "measured slower at every shape (DESIGN_HISTORY.md)")
-    return (((int(blockmap) & 3) << 18) | (0x100000 if poll1 else 0) |
-            (0x200000 if repflags else 0) | (0x400000 if spread else 0) | ((int(poll_delay) & 31) << 23) |
-            (0x20000000 if tagged else 0) | (0x10000000 if split3 else 0) | (0x40000000 if xl8 else 0))
+    return (lstm_map(blockmap) | (LSTM_POLL1 if poll1 else 0) | (LSTM_REPFLAGS if repflags else 0) |
+            (LSTM_FLAG_PER_LINE if spread else 0) | ((int(poll_delay) & 31) << LSTM_DELAY_SHIFT) |
+            (LSTM_TAGGED if tagged else 0) | (LSTM_SPLIT3 if split3 else 0) | (LSTM_XL8 if xl8 else 0))
+
+
+def lstm_variant_from_spec(spec):
+    """The mode bits of a SEPKERN_LSTM_FWD / _BWD string: up to nine comma-separated integers
+    "half,map,poll1,repflags,spread,delay,tagged,split3,xl8" (lstm_variant_bits' arguments; missing fields are 0)."""
+    v = [int(x) for x in spec.split(",")]
+    v += [0] * (9 - len(v))
+    return lstm_variant_bits(bool(v[0]), v[1], bool(v[2]), bool(v[3]), bool(v[4]), v[5], tagged=bool(v[6]), split3=bool(v[7]),
+                             xl8=bool(v[8]))
+
+
+def lstm_last_launch():
+    """(launches, [family, KS, bf16, packed, GM, exclusive, blocks, G]) of this thread's last lstm_fwd / lstm_bwd call
+    (sk_lstm_last_launch, include/sepkern.h; index the list with LSTM_Q_*)."""
+    out = (C.c_int * 8)()
+    n = _lib.load().sk_lstm_last_launch(out)
+    return n, list(out)
 
 
 def lstm_fwd(gx, whh, h0, c0, lens, y, gates, cs, hn, cn, T, B, H, mode=0, bf16=False, blockmap=0, offs=None, rows=None):
@@ -645,7 +690,7 @@ def lstm_fwd(gx, whh, h0, c0, lens, y, gates, cs, hn, cn, T, B, H, mode=0, bf16=
     blockmap 0..2: which workgroups share an XCD / a CU (mode bits 18..19; speed only).  offs (int32, T+1): the sequence tensors are PACKED
     rows (lens sorted descending; `rows` of them: the launch's algorithmic work for the profile); None: zero-padded (T, B, .)."""
     ws = lstm_ws(T, B, H)
-    mode = int(mode) | (0x10000 if bf16 else 0) | ((int(blockmap) & 3) << 18)
+    mode = int(mode) | (LSTM_BF16 if bf16 else 0) | lstm_map(blockmap)
     _chk(offs, torch.int32)
     with _timed("lstm_fwd_kernel", 2.0 * (T * B if rows is None else rows) * 2 * 4 * H * H):
         _lib.call("sk_lstm_fwd", _ptr(gx), _ptr(whh), _ptr(h0), _ptr(c0), _ptr(lens), _ptr(offs), _ptr(y), _ptr(gates), _ptr(cs),
@@ -664,7 +709,7 @@ def lstm_bwd(dy, whh, gates, cs, c0, lens, dgx, dh0, dc0, T, B, H, mode=0, dhn=N
             raise _lib.SepkernError("lstm_bwd: planes of dgx belong to the fp32 configuration")
         plane, dgx_bf16 = dgx_bf16.plane, dgx_bf16.t[0]
     ws = lstm_ws(T, B, H)
-    mode = int(mode) | (0x10000 if bf16 else 0)
+    mode = int(mode) | (LSTM_BF16 if bf16 else 0)
     _chk(dbias)
     _chk(offs, torch.int32)
     _chk(dgx_bf16, torch.bfloat16)

@@ -55,7 +55,7 @@ def main():
 
     def bits(var):
         return ops.lstm_variant_bits(bool(var[0]), var[1], bool(var[2]), bool(var[3]), bool(var[5]), var[6], tagged=bool(var[7]), split3=bool(var[8]),
-                                     xl8=bool(var[9])) | (var[4] << 8)
+                                     xl8=bool(var[9])) | ops.lstm_gmin(var[4])
 
     def run_fwd(var):
         g = gx.clone()

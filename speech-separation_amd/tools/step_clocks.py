@@ -95,7 +95,7 @@ def main():
         return ops.lstm_fwd(g, whh, h0, c0, pk.lens, y, g, cs, hn, cn, T, B, H, 1 | fbits, bf16=False)
 
     def bwd(excl=False):
-        return ops.lstm_bwd(dy, whh, g, cs, c0, pk.lens, dgx, dh0, dc0, T, B, H, 1 | bbits | (0x20000 if excl else 0), bf16=False)
+        return ops.lstm_bwd(dy, whh, g, cs, c0, pk.lens, dgx, dh0, dc0, T, B, H, 1 | bbits | (ops.LSTM_BWD_EXCLUSIVE if excl else 0), bf16=False)
     ws = fwd()
     torch.cuda.synchronize()
     ops.lstm_status(ws)

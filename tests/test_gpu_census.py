@@ -2,8 +2,9 @@
 
 One training step of every one-GPU BASELINE configuration (+ the reference's default model at its default batch size, + the
 headline in the reference's literal fp32-MFMA arithmetic) runs with a spy on the ctypes boundary: every C entry point called, and
-for the GEMMs the kernel the library chose (sk_gemm_last_kernel()).  The table generated from that is the one DESIGN.md section 4
-carries between its census markers: this test regenerates it and compares, so the document cannot go stale.
+for the GEMMs and the recurrences the kernel the library chose (sk_gemm_last_kernel(), sk_lstm_last_launch()).  The table
+generated from that is the one DESIGN.md section 4 carries between its census markers: this test regenerates it and compares,
+so the document cannot go stale.
 `python tests/test_gpu_census.py` prints the table (and writes gpurun_out/census.md).
 """
 import os
@@ -39,36 +40,22 @@ FIXED = {
 }
 
 
-def _pick_ks(H, bf):
-    need = (H + 15) // 16
-    for o in (20, 40 if bf else 38, 56, 64):
-        if o >= need:
-            return o
-    return 0
-
-
-def _lstm_kernel(name, args):
-    """The template instantiation and grid of a recurrence launch, restated from csrc/lstm.hip's dispatch."""
-    if name == "sk_lstm_fwd":
-        T, B, H, mode, offs = args[12], args[13], args[14], args[15], args[5]
-    else:
-        T, B, H, mode, offs = args[17], args[18], args[19], args[20], args[8]
-    bf = bool(mode & 0x10000)
-    s3 = name == "sk_lstm_fwd" and bool(mode & 0x10000000) and not bf and _pick_ks(H, True) != 64
-    ks = _pick_ks(H, bf or s3)
-    nbg = (B + 15) // 16
-    g = next(g_ for g_ in range(1, 9) if ks * ((nbg + g_ - 1) // g_) * 2 <= 256)
-    wgs = ks * ((nbg + g - 1) // g) * 2
-    if bool(mode & 0x40000000) and bf and ks == 56 and B <= 32:            # XCD-local streams of 8 rows (mode bit 30)
+def _lstm_row(name, T, B, H):
+    """Kernel instantiation and grid of the recurrence call that just returned, from sk_lstm_last_launch()."""
+    from sepkern import ops
+    _, q = ops.lstm_last_launch()
+    tf = lambda i: "true" if q[i] else "false"      # noqa: E731
+    if q[ops.LSTM_Q_FAMILY] in (ops.LSTM_K_FWD_XL8, ops.LSTM_K_BWD_XL8):           # XCD-local streams of 8 rows
         n8 = 2 * ((B + 7) // 8)
-        k = "lstm_fwd_xl8_kernel<56, %s>" % ("true" if offs else "false") if name == "sk_lstm_fwd" else "lstm_bwd_xl8_kernel<56>"
+        k = "lstm_fwd_xl8_kernel<56, %s>" % tf(ops.LSTM_Q_PACKED) if name == "sk_lstm_fwd" else "lstm_bwd_xl8_kernel<56>"
         return k, "T=%d B=%d H=%d: %d streams of 28 workgroups x 32 units x 8 rows, one XCD each (%d CUs held)" % (T, B, H, n8, 28 * n8)
     if name == "sk_lstm_fwd":
-        k = "lstm_fwd_kernel<%d, %s, 8, %s, %s>" % (ks, "true" if bf else "false", "true" if s3 else "false", "true" if offs else "false")
+        k = "lstm_fwd_kernel<%d, %s, 8, %s, %s>" % (q[ops.LSTM_Q_KS], tf(ops.LSTM_Q_BF16),
+                                                    "true" if q[ops.LSTM_Q_FAMILY] == ops.LSTM_K_FWD_SPLIT3 else "false", tf(ops.LSTM_Q_PACKED))
     else:
-        excl = bool(mode & 0x20000)
-        k = "lstm_bwd_kernel<%d, %s, %d>%s" % (ks, "true" if bf else "false", 1 if (g == 1 and not excl) else 8, " (exclusive)" if excl else "")
-    return k, "T=%d B=%d H=%d: %d persistent workgroups (one per CU), %d batch group(s) each" % (T, B, H, wgs, g)
+        k = "lstm_bwd_kernel<%d, %s, %d>%s" % (q[ops.LSTM_Q_KS], tf(ops.LSTM_Q_BF16), q[ops.LSTM_Q_GM],
+                                               " (exclusive)" if q[ops.LSTM_Q_EXCLUSIVE] else "")
+    return k, "T=%d B=%d H=%d: %d persistent workgroups (one per CU), %d batch group(s) each" % (T, B, H, q[ops.LSTM_Q_BLOCKS], q[ops.LSTM_Q_G])
 
 
 class Spy:
@@ -96,7 +83,7 @@ class Spy:
                 shape = "%s %d x %d x %d%s%s" % (form, M, N, K, " x%d" % batch if batch > 1 else "", " in %d K slices" % splitk if splitk > 1 else "")
                 key = (name, GEMM_KERNELS.get(kid, "kernel %d" % kid), shape, "side" if side else "main")
             elif name in ("sk_lstm_fwd", "sk_lstm_bwd"):
-                k, shape = _lstm_kernel(name, [val(a) for a in args])
+                k, shape = _lstm_row(name, *[val(a) for a in (args[12:15] if name == "sk_lstm_fwd" else args[17:20])])
                 key = (name, k, shape, "side" if side else "main")
             elif name in FIXED:
                 key = (name, FIXED[name], "", "side" if side else "main")

@@ -37,6 +37,14 @@ def test_library_exports_every_declared_symbol():
     assert _lib.load().sk_version() == _lib.SK_VERSION
 
 
+def test_ops_mirrors_the_lstm_mode_names_of_the_header():
+    """sepkern/ops.py's LSTM_* constants are include/sepkern.h's SK_LSTM_* values, every plain one of them."""
+    from sepkern import ops
+    defs = dict(re.findall(r"^#define SK_(LSTM_[A-Z0-9_]+) (\d+|\(1 << \d+\))(?: |$)", open(HEADER).read(), flags=re.M))
+    assert len(defs) >= 28 and {"LSTM_BF16", "LSTM_XL8", "LSTM_GMIN_SHIFT", "LSTM_Q_G", "LSTM_K_BWD_XL8"} <= set(defs)
+    assert {k: getattr(ops, k, None) for k in defs} == {k: eval(v) for k, v in defs.items()}
+
+
 def test_argument_errors_are_reported_not_thrown():
     from sepkern import _lib
     lib = _lib.load()
@@ -68,8 +76,8 @@ def test_product_build_reports_no_build_flags():
 
 
 def test_a_diagnostic_build_is_refused_by_the_loader_and_by_bench(tmp_path):
-    """`make gemm_variant DEFS=-DSK_SPLIT_FREE` builds a TIMING-ONLY library (wrong numerics) from the product
-    sources into the product's directory, with the product's SK_VERSION.  sk_build_flags() tells them apart: the ctypes loader refuses
+    """`make gemm_variant DEFS=-DSK_SPLIT_FLIP=0` builds a library with ANOTHER ARITHMETIC (no sign phases) from
+    the product sources into the product's directory, with the product's SK_VERSION.  sk_build_flags() tells them apart: the ctypes loader refuses
     such a library unless SEPKERN_ALLOW_DIAGNOSTIC_LIB=1, and bench.py exits non-zero on it without --diagnostic -- before it
     touches a GPU."""
     import subprocess
@@ -77,17 +85,17 @@ def test_a_diagnostic_build_is_refused_by_the_loader_and_by_bench(tmp_path):
     csrc = os.path.join(ROOT, "speech-separation_amd", "csrc")
     lib = os.path.join(ROOT, "speech-separation_amd", "sepkern", "libsepkern_t_refusal.so")
     try:
-        subprocess.check_call(["make", "-C", csrc, "gemm_variant", "NAME=t_refusal", "DEFS=-DSK_SPLIT_FREE"], stdout=subprocess.DEVNULL)
+        subprocess.check_call(["make", "-C", csrc, "gemm_variant", "NAME=t_refusal", "DEFS=-DSK_SPLIT_FLIP=0"], stdout=subprocess.DEVNULL)
         code = ("import sys; sys.path.insert(0, %r); from sepkern import _lib\n"
                 "try:\n    _lib.load(); print('LOADED', _lib.load().sk_build_flags())\n"
                 "except _lib.SepkernError as e:\n    print('REFUSED', e)\n" % os.path.join(ROOT, "speech-separation_amd"))
         env = dict(os.environ, SEPKERN_LIB=lib)
         env.pop("SEPKERN_ALLOW_DIAGNOSTIC_LIB", None)
         out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300).stdout
-        assert out.startswith("REFUSED") and "DIAGNOSTIC build" in out and "TIMING_ONLY" in out, out
+        assert out.startswith("REFUSED") and "DIAGNOSTIC build" in out and "ARITH" in out, out
         env["SEPKERN_ALLOW_DIAGNOSTIC_LIB"] = "1"
         out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300).stdout
-        assert out.split()[:2] == ["LOADED", "1"], out
+        assert out.split()[:2] == ["LOADED", "2"], out
         # bench.py: refuses before it needs a GPU, names the flag; --diagnostic gets past the check (and then fails here for want of a GPU)
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"], env=env, capture_output=True, text=True,
                            timeout=300)
