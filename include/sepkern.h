@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 133
+#define SK_VERSION 134
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -429,6 +429,50 @@ int sk_pit_mse_fwd(const float* mask, const float* mix, const float* const* src_
 int sk_pit_mse_bwd(const float* mask, const float* mix, const float* const* src_host,
                    const int32_t* best_perm, const float* out, const float* gscale, const int32_t* offs, int64_t nrows,
                    int T, int B, int F, int S, float* dmask, sk_stream_t stream);
+
+/* ---------------------------------------------------------------- SI-SDR uPIT loss (waveform domain)
+ * A second training loss beside PIT-MSE: utterance-level PIT on the negative SI-SDR of the time-domain estimates
+ * e_s = istft(mask_s * STFT(mix)) against the source waveforms.  No counterpart in the reference (its only loss is the
+ * magnitude MSE above); the metric is sepkern/sisdr.py's, which also restates the arithmetic below in numpy fp64.
+ * Three entry points, all on PACKED rows (offs as under "packed rows": row of (t, j) = offs[t] + j; utterance j has
+ * T_j = nframes[j] frames and L_j = hop * (T_j - 1) output samples; n_fft = 512, hop = 128 only; 1 <= S <= 4):
+ *
+ * sk_mask_istft_rows: sk_mask_istft's arithmetic (same frames, same overlap-add order, same window-sum-square division,
+ *   same trim) with the spectra read from rows: mix_rows_c64 (R, 257) complex64, mask (R, ld >= S*257) float32 with source s
+ *   in columns s*257 .. s*257+256.  Estimate s of utterance j: L_j float32 samples at wav_out + out_offs[j*S + s].
+ *   max_frames >= max_j T_j sizes the grid. */
+int sk_mask_istft_rows(const void* mix_rows_c64, const float* mask, int ld, const int32_t* offs, const int32_t* nframes,
+                       int B, int S, int n_fft, int hop, float* wav_out, const int64_t* out_offs, int max_frames,
+                       sk_stream_t stream);
+/* sk_sisdr_pit_fwd: est as sk_mask_istft_rows wrote it (est_offs[j*S + k]); reference i of utterance j = nsamp[j] samples at
+ *   ref + ref_offs[j*S + i] (elements; float32, or int16 PCM scaled by 1/32768 when pcm16 != 0 -- sk_stft's convention);
+ *   nsamp[j] = L_j samples of both are read.  From the plain sums sum e, sum r, sum e^2, sum r^2, sum e r (fp64, fixed order,
+ *   no atomics: bitwise reproducible, and an utterance's numbers do not depend on what else is in the batch) the zero-mean
+ *   a = <e~,r~>, b = <r~,r~>, c = <e~,e~> and
+ *     pair (B,S,S): pair[j][k][i] = SI-SDR(e_k, r_i) = 10 log10(((a/b) a + eps) / (c - (a/b) a + eps)) dB, eps = 1e-30
+ *                   (b <= 0, a silent reference: the projection is 0 and the value the finite 10 log10(eps / (c + eps)))
+ *     perm_score (S!,B) in itertools.permutations order: (1/S) sum_k pair[j][k][p(k)];  best_perm (B) = argMAX (first maximum)
+ *     out[0] = loss = -(1/count) sum_j best score, out[1] = count, out[2] = sum_j best score;  count = B, or count_dev[0]
+ *              (device scalar, may be NULL: the GLOBAL utterance count of a data-parallel step)
+ *     coef (B,S,3): A, B, C of d loss / d e_k[n] = A e_k[n] + B r_i[n] + C, i = the best permutation's reference for k
+ *              (r in its scaled units), i.e. -(1/(count S)) kappa (2 r~/a - 2 (e~ - (a/b) r~)/(c - a^2/b)), kappa = 10/ln 10;
+ *              0, 0, 0 for a pair with b <= 0, a == 0 or c - a^2/b <= 0 (silent source, exact copy): never NaN or Inf.
+ *   max_samples >= max_j nsamp[j] sizes the grid; ws >= sk_sisdr_workspace_bytes(B, S, max_samples) (0 for bad arguments). */
+size_t sk_sisdr_workspace_bytes(int B, int S, int max_samples);
+int sk_sisdr_pit_fwd(const float* est, const int64_t* est_offs, const void* ref, int pcm16, const int64_t* ref_offs,
+                     const int32_t* nsamp, int B, int S, int max_samples, const float* count_dev, float* pair,
+                     float* perm_score, int32_t* best_perm, float* out, float* coef, void* ws, sk_stream_t stream);
+/* sk_sisdr_mask_grad: dmask = gscale[0] * d loss / d mask, the gradient above taken back through the overlap-add, the
+ *   inverse FFT and the mask product in ONE kernel.  The adjoint of mask-apply + iSTFT is a forward STFT of another signal:
+ *   g_k[p] = (A e_k[n] + B r_i[n] + C) * gscale / wss[p] at p = n + n_fft/2, n in [0, L_j), zero elsewhere (formed by the sample
+ *   loader; wss = the forward's window-sum-square), framed WITHOUT reflection, U_k[t][f] = sum_n w[n] g_k[t hop + n] e^(-2 pi i f n / n_fft),
+ *     dmask[offs[t] + j][k*257 + f] = (c_f / n_fft) (Re X[t][f] Re U_k[t][f] + Im X[t][f] Im U_k[t][f]),  c_f = 1 for f in {0, 256}, else 2,
+ *   X = mix_rows_c64, contracted in the epilogue and stored from registers: neither g nor U exists in memory.
+ *   dmask (>= R, ld >= S*257): only rows offs[t] + j, t < T_j, columns < S*257 are written. */
+int sk_sisdr_mask_grad(const float* est, const int64_t* est_offs, const void* ref, int pcm16, const int64_t* ref_offs,
+                       const int32_t* nframes, const int32_t* best_perm, const float* coef, const float* gscale,
+                       const void* mix_rows_c64, const int32_t* offs, int B, int S, int n_fft, int hop, int max_frames,
+                       float* dmask, int ld, sk_stream_t stream);
 
 /* ---------------------------------------------------------------- RSH arch (reference archs/RSH.py)
  * One pass of the greedy source-assignment loss (archs/RSH.py:225-244): mask (T,B,F); x (T,B,ldx) whose

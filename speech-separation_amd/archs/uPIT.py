@@ -21,6 +21,10 @@ Beyond the reference (all optional, defaults reproduce it):
     (archs/uPIT.py:121-127); tests inject (h0, c0) by assigning model.next_hidden.
   * under torch.distributed (one process per GPU) gradients are all-reduced over RCCL inside
     backward and the loss is normalised by the GLOBAL frame count.
+  * conf key loss: 'mse' (default, the reference's magnitude PIT-MSE) or 'sisdr': utterance-level PIT on the negative
+    SI-SDR of the time-domain estimates istft(mask_s * STFT(mix)) against the source waveforms (include/sepkern.h
+    "SI-SDR uPIT loss").  It needs waveforms: WavTrainSet batches (steps/train_qsub.py --wav-input).  compute_loss then
+    returns (mean negative SI-SDR per utterance in dB, number of utterances).
 """
 import itertools
 import os
@@ -43,7 +47,7 @@ except ImportError:  # the frozen copy exp/<...>/arch.py is imported from anothe
     import sepkern  # noqa: F401
 from sepkern import dist as skdist
 from sepkern import ops
-from sepkern.data import features_from_pcm as _features_from_pcm
+from sepkern.data import features_from_pcm as _features_from_pcm, wave_features_from_pcm as _wave_features_from_pcm
 from sepkern.collate import collate_sorted, eval_magnitudes, read_scp, stage_copies, train_sample
 from sepkern.model import SepDNNBase, UnpackFn, to_packed as _to_packed
 from sepkern.packing import Packing
@@ -181,11 +185,49 @@ class _PitFn(torch.autograd.Function):
     return (dmask, None, None, None) + (None,) * len(srcs)
 
 
+LOSSES = ('mse', 'sisdr')
+
+
+def parse_loss(value):
+  """The conf key `loss`: 'mse' (default) or 'sisdr'."""
+  value = str(value).strip().lower()
+  if value not in LOSSES:
+    raise ValueError("conf key loss: %r is not one of %s" % (value, " / ".join(repr(v) for v in LOSSES)))
+  return value
+
+
+NEEDS_WAVEFORMS = "`loss=sisdr` needs waveforms: train with `--wav-input`"
+
+
+class _SisdrFn(torch.autograd.Function):
+  """out = [-mean_j best SI-SDR score, count, sum_j best score] from the packed mask rows: mask-apply + iSTFT, the SI-SDR
+  sums and PIT forward; the SI-SDR gradient and the iSTFT's adjoint fused in one kernel backward."""
+
+  @staticmethod
+  def forward(ctx, mask, pk, wave, desc, count_dev, S):
+    est, est_offs, _ = ops.mask_istft_rows(wave['mixc'], mask, pk, S, est_offs=desc['est_offs'])
+    ref_offs = desc['ref_offs']
+    res = ops.sisdr_pit_fwd(est, est_offs, wave['flat'], ref_offs, desc['nsamp'], S, 128 * (pk.T - 1), count_dev)
+    ctx.save_for_backward(est, est_offs, ref_offs, res["best_perm"], res["coef"], wave['mixc'], wave['flat'])
+    ctx.pk, ctx.S, ctx.shape = pk, S, tuple(mask.shape)
+    ctx.mark_non_differentiable(res["best_perm"])
+    return res["out"], res["best_perm"]
+
+  @staticmethod
+  def backward(ctx, gout, _gperm):
+    est, est_offs, ref_offs, best, coef, mixc, flat = ctx.saved_tensors
+    dmask = torch.empty(ctx.shape, dtype=torch.float32, device=est.device)
+    dmask[ctx.pk.R:].zero_()               # tail rows of an (Rp, .) buffer stay zero
+    ops.sisdr_mask_grad(est, est_offs, flat, ref_offs, best, coef, gout[0:1].contiguous(), mixc, ctx.pk, ctx.S, out=dmask)
+    return dmask, None, None, None, None, None
+
+
 class SepDNN(SepDNNBase):
   def __init__(self, gpuid, **kwargs):
     super(SepDNN, self).__init__()
     self.feat_dim = int(kwargs.get('feat_dim', 257))
     self.num_spk = int(kwargs.get('num_spk', 2))
+    self.loss_kind = parse_loss(kwargs.get('loss', 'mse'))
     for key in kwargs.keys():
       print('modelparam:', key, kwargs[key])
     # the reference hard-codes 2 x 600 (archs/uPIT.py:115-119); hidden_dim / num_layers widen it
@@ -269,6 +311,26 @@ def compute_loss_packed(model, mix, sources, pk, plotdir=""):
   return loss, norm
 
 
+def compute_loss_wave(model, mix, pk, wave):
+  """The loss=sisdr route: mix (R,F) packed magnitude rows (the network's input), wave as wave_features_from_pcm made it.
+  Returns (mean negative SI-SDR per utterance in dB, number of utterances)."""
+  S = model.num_spk
+  missing = [k for k in ('source' + str(i + 1) for i in range(S)) if k not in wave['sig_offs']]
+  if missing:
+    raise ValueError("loss=sisdr: the batch holds no waveform %s (num_spk = %d)" % (", ".join(missing), S))
+  model.zero_grad()
+  model.hidden = model.init_hidden(pk.B)
+  # data-parallel: divide by the GLOBAL utterance count (None = single process: the kernel uses B), while training only
+  training_step = model.training and torch.is_grad_enabled()
+  count = skdist.global_norm(pk.lens.new_full((1,), pk.B), 1) if training_step else None
+  desc = ops.sisdr_descriptors(pk, wave['sig_offs'], S)       # (uploaded before the network is enqueued, not behind it)
+  mask_out = model.forward_packed(mix, pk)
+  out, best = _SisdrFn.apply(mask_out, pk, wave, desc, count, S)
+  model.last_best_perm = best.detach()      # arg-max permutation per utterance (index into itertools.permutations)
+  model.step_frames = pk.R                  # (the norm counts utterances: the driver's frames/s line reads this)
+  return out[0], out[1].detach()
+
+
 def compute_loss_padded(model, mix, sources, lens, plotdir=""):
   """compute_loss on zero-padded time-major inputs resident on the GPU: mix (T,B,F), sources [(T,B,F)]*S float32,
   lens int32 (B) in any order.  They are packed (sk_pack_rows; a view when all lengths are equal) and go the packed way."""
@@ -288,6 +350,14 @@ def compute_loss_padded(model, mix, sources, lens, plotdir=""):
 
 def compute_loss(model, epoch, batch_sample, plotdir=""):
   dev = model.lin.weight.device
+  if getattr(model, 'loss_kind', 'mse') == 'sisdr':
+    if 'pcm' in batch_sample:
+      mix, _, pk, wave = _wave_features_from_pcm(batch_sample['pcm'], dev, source_mags=False)
+    elif 'packed' in batch_sample and 'wave' in batch_sample:     # staged by Prefetcher(keep_wave=True)
+      (mix, _, pk), wave = batch_sample['packed'], batch_sample['wave']
+    else:                                                         # npz feature batches hold magnitudes only
+      raise ValueError(NEEDS_WAVEFORMS)
+    return compute_loss_wave(model, mix, pk, wave)
   if 'pcm' in batch_sample:        # WavTrainSet batches: features are computed on the GPU
     mix, sources, pk = _features_from_pcm(batch_sample['pcm'], dev)
     return compute_loss_packed(model, mix, sources[:model.num_spk], pk, plotdir)

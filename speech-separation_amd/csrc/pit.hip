@@ -14,7 +14,7 @@
 
 namespace {
 
-constexpr int MAXS = 4;
+constexpr int MAXS = SK_MAXS;
 constexpr int TCH = 16;  // frames per block in the pairwise pass
 constexpr int RB = 4;    // (frame, utterance) rows per block in the backward pass
 
@@ -77,21 +77,6 @@ __global__ __launch_bounds__(256) void pit_pair_kernel(const float* __restrict__
     }
 }
 
-// Lexicographic permutation number `idx` of {0..S-1} (itertools.permutations order).
-__device__ __forceinline__ void nth_perm(int idx, int S, int* perm) {
-  int avail[MAXS];
-  for (int i = 0; i < S; ++i) avail[i] = i;
-  int fact = 1;
-  for (int i = 2; i < S; ++i) fact *= i;  // (S-1)!
-  for (int i = 0; i < S; ++i) {
-    const int q = idx / fact;
-    idx -= q * fact;
-    perm[i] = avail[q];
-    for (int j = q; j < S - 1 - i; ++j) avail[j] = avail[j + 1];
-    if (S - 1 - i > 0) fact /= (S - 1 - i);
-  }
-}
-
 __global__ __launch_bounds__(256) void pit_finalize_kernel(const float* __restrict__ partial, int nch,
                                                            const int32_t* __restrict__ lens, int B, int F, int S,
                                                            const float* __restrict__ norm_dev, float* __restrict__ pair_sse,
@@ -113,7 +98,7 @@ __global__ __launch_bounds__(256) void pit_finalize_kernel(const float* __restri
     int bi = 0;
     for (int p = 0; p < nperm; ++p) {
       int perm[MAXS];
-      nth_perm(p, S, perm);
+      sk_nth_perm(p, S, perm);
       float l = 0.f;
       for (int s = 0; s < S; ++s) l += pr[s * S + perm[s]];
       perm_loss[(int64_t)p * B + b] = l;
@@ -158,7 +143,7 @@ __global__ __launch_bounds__(256) void pit_bwd_kernel(const float* __restrict__ 
     } else {
       b = (int)(row % B);
     }
-    nth_perm(best_perm[b], S, perm[threadIdx.x]);
+    sk_nth_perm(best_perm[b], S, perm[threadIdx.x]);
   }
   __syncthreads();
   const float k = gscale[0] * 2.0f / ((float)S * out[1]);

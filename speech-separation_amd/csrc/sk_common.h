@@ -55,4 +55,25 @@ __device__ __forceinline__ float sk_block_sum256(float v, float* red /* >= 4 flo
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// Lexicographic permutation number `idx` of {0..S-1} (itertools.permutations order), S <= SK_MAXS: element i of the
+// permutation in bits 2i, 2i+1 of the result (no arrays: nothing a kernel would keep in scratch).
+#define SK_MAXS 4
+__device__ __forceinline__ unsigned sk_nth_perm_code(int idx, int S) {
+  unsigned avail = 0xE4u, code = 0u;  // the elements still free, in increasing order, two bits each
+  int fact = 1;
+  for (int i = 2; i < S; ++i) fact *= i;  // (S-1)!
+  for (int i = 0; i < S; ++i) {
+    const int q = idx / fact;
+    idx -= q * fact;
+    code |= ((avail >> (2 * q)) & 3u) << (2 * i);
+    avail = (avail & ((1u << (2 * q)) - 1u)) | ((avail >> (2 * q + 2)) << (2 * q));
+    if (S - 1 - i > 0) fact /= (S - 1 - i);
+  }
+  return code;
+}
+__device__ __forceinline__ void sk_nth_perm(int idx, int S, int* perm) {
+  const unsigned code = sk_nth_perm_code(idx, S);
+  for (int i = 0; i < S; ++i) perm[i] = (int)((code >> (2 * i)) & 3u);
+}
+
 __device__ __forceinline__ float sk_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }

@@ -10,6 +10,9 @@
 // Both kernels are streaming kernels (HBM roofline):
 //   STFT   reads 128 new samples and writes 257 bins per frame,
 //   iSTFT  reads 257 complex bins (+257 mask values) and writes 128 samples per frame per source.
+// The SI-SDR training loss (sisdr.hip) adds two kernels that share this FFT: istft_rows_kernel, the iSTFT reading the training
+// engine's packed rows, and sisdr_grad_kernel, its adjoint fused with the SI-SDR gradient -- the STFT kernel with another
+// sample loader and another epilogue (2 x 128 samples + 257 complex bins in, 257 gradients out per frame and source).
 //
 // Reference semantics restated: librosa.core.stft / istft as used at
 // steps/extract_feats.py:85-89,104-105 and steps/reconstruct_sources.py:39-42 (see oracle/stft.py).
@@ -375,6 +378,53 @@ __device__ __forceinline__ void istft_stash(const TileRegs& r, float2 (*rows)[RL
     if (q < 16 || k0 == 0) row[16 * q] = make_float2(r.x[q].x * r.m[q], r.x[q].y * r.m[q]);
 }
 
+// Output samples of the 16 hops of tile t0 from the windowed frames in the ring: thread (m0 = tid & 127, hsel = tid >> 7)
+// produces sample m0 of hops t0 + hsel + 2q, q = 0..7.  With all four taps inside [0, T) the window-sum-square is a
+// constant of the thread (inv_full = its reciprocal).
+__device__ __forceinline__ void istft_overlap_add(float2 (*rows)[RLD], const float* win, int t0, int T, int nout, int m0, int hsel,
+                                                  float inv_full, float* __restrict__ wav_out, int16_t* __restrict__ pcm_out,
+                                                  int64_t oo) {
+  // overlap-add in increasing frame order, window-sum-square normalisation, trim, convert
+  int slot = (t0 + hsel) % RING;  // ring slot of frame hp - 3 (frame t lives in slot (t + 3) % RING)
+#pragma unroll
+  for (int q = 0; q < FPB * HOP / 256; ++q) {
+    const int hp = t0 + hsel + 2 * q;
+    const int n = hp * HOP + m0 - NFFT / 2;
+    const int s3 = slot, s2 = slot + 1 >= RING ? slot + 1 - RING : slot + 1, s1 = slot + 2 >= RING ? slot + 2 - RING : slot + 2,
+              s0 = slot + 3 >= RING ? slot + 3 - RING : slot + 3;
+    slot = slot + 2 >= RING ? slot + 2 - RING : slot + 2;
+    if (n < 0 || n >= nout) continue;
+    float acc;
+    if (hp >= 3 && hp < T) {  // all four frames exist
+      acc = reinterpret_cast<const float*>(rows[s3])[3 * HOP + m0];
+      acc += reinterpret_cast<const float*>(rows[s2])[2 * HOP + m0];
+      acc += reinterpret_cast<const float*>(rows[s1])[HOP + m0];
+      acc += reinterpret_cast<const float*>(rows[s0])[m0];
+      acc *= inv_full;
+    } else {
+      acc = 0.f;
+      float wss = 0.f;
+      const int sl[4] = {s0, s1, s2, s3};
+#pragma unroll
+      for (int qq = 3; qq >= 0; --qq) {
+        const int t = hp - qq;
+        if (t >= 0 && t < T) {
+          const int m = qq * HOP + m0;
+          acc += reinterpret_cast<const float*>(rows[sl[qq]])[m];
+          const float w = win[m];
+          wss += w * w;
+        }
+      }
+      if (wss > 1.17549435e-38f) acc /= wss;
+    }
+    if (wav_out) wav_out[oo + n] = acc;
+    if (pcm_out) {
+      const float sv = acc * 32767.0f;
+      pcm_out[oo + n] = (int16_t)(long long)sv;  // truncation toward zero, wrap on overflow
+    }
+  }
+}
+
 // One workgroup reconstructs `tpb` consecutive 16-hop tiles of one (utterance, source): every frame is read
 // and transformed once; the 3 frames that overlap into the next tile stay in the LDS ring.
 __global__ __launch_bounds__(256, 3) void istft_kernel(
@@ -440,44 +490,249 @@ __global__ __launch_bounds__(256, 3) void istft_kernel(
     if (binmajor && tile + 1 < tile1) istft_fetch(pre, t0 + FPB, T, mix, mo, msf, mask, ko, ksf);  // travels under the FFTs
     istft_frame(rows[(t0 + fr + 3) % RING], tw, t256, win, j, (t0 + fr + 3) & 15);
     __syncthreads();
-    // overlap-add in increasing frame order, window-sum-square normalisation, trim, convert
-    int slot = (t0 + hsel) % RING;  // ring slot of frame hp - 3 (frame t lives in slot (t + 3) % RING)
+    istft_overlap_add(rows, win, t0, T, nout, m0, hsel, inv_full, wav_out, pcm_out, oo);
+  }
+}
+
+// ---- packed rows (the training engine's layout): row of (t, j) = offs[t] + j, mixture (R, 257) complex64, mask (R, ld)
+// with source s in columns s * 257 ...  A tile is read frame-major: thread tid owns bin tid of each of the 16 frames (one
+// coalesced row sweep per frame, the row's base a scalar), threads 0..15 also bin 256 of frame tid.  fetch() only issues
+// the loads, stash() applies the mask and fills the ring slots (RLD: the bin permutation keeps a frame's 256 stores conflict-free).
+struct RowRegs {
+  float2 x[17];
+  float m[17];
+};
+
+__device__ __forceinline__ void istft_rows_fetch(RowRegs& r, int t0, int T, const float2* __restrict__ mix,
+                                                 const float* __restrict__ mask, int ld, int col0,
+                                                 const int32_t* __restrict__ offs, int u) {
+  const int tid = threadIdx.x;
 #pragma unroll
-    for (int q = 0; q < FPB * HOP / 256; ++q) {
-      const int hp = t0 + hsel + 2 * q;
-      const int n = hp * HOP + m0 - NFFT / 2;
-      const int s3 = slot, s2 = slot + 1 >= RING ? slot + 1 - RING : slot + 1, s1 = slot + 2 >= RING ? slot + 2 - RING : slot + 2,
-                s0 = slot + 3 >= RING ? slot + 3 - RING : slot + 3;
-      slot = slot + 2 >= RING ? slot + 2 - RING : slot + 2;
-      if (n < 0 || n >= nout) continue;
-      float acc;
-      if (hp >= 3 && hp < T) {  // all four frames exist
-        acc = reinterpret_cast<const float*>(rows[s3])[3 * HOP + m0];
-        acc += reinterpret_cast<const float*>(rows[s2])[2 * HOP + m0];
-        acc += reinterpret_cast<const float*>(rows[s1])[HOP + m0];
-        acc += reinterpret_cast<const float*>(rows[s0])[m0];
-        acc *= inv_full;
-      } else {
-        acc = 0.f;
-        float wss = 0.f;
-        const int sl[4] = {s0, s1, s2, s3};
+  for (int q = 0; q < 17; ++q) {
+    const int t = q < FPB ? t0 + q : t0 + tid, k = q < FPB ? tid : 256;
+    const bool live = t < T && (q < FPB || tid < FPB);
+    const int64_t row = live ? (int64_t)offs[t] + u : 0;
+    r.x[q] = live ? mix[row * NBIN + k] : make_float2(0.f, 0.f);
+    r.m[q] = live ? mask[row * ld + col0 + k] : 0.f;
+  }
+}
+
+__device__ __forceinline__ void istft_rows_stash(const RowRegs& r, float2 (*rows)[RLD], int t0) {
+  const int tid = threadIdx.x;
 #pragma unroll
-        for (int qq = 3; qq >= 0; --qq) {
-          const int t = hp - qq;
-          if (t >= 0 && t < T) {
-            const int m = qq * HOP + m0;
-            acc += reinterpret_cast<const float*>(rows[sl[qq]])[m];
-            const float w = win[m];
-            wss += w * w;
-          }
+  for (int q = 0; q < 17; ++q) {
+    const int t = q < FPB ? t0 + q : t0 + tid, k = q < FPB ? tid : 256;
+    if (q < FPB || tid < FPB) rows[(t + 3) % RING][k ^ ((t + 3) & 15)] = make_float2(r.x[q].x * r.m[q], r.x[q].y * r.m[q]);
+  }
+}
+
+// istft_kernel on packed rows: blockIdx.y = j * S + s, float32 samples out.
+__global__ __launch_bounds__(256, 3) void istft_rows_kernel(const float2* __restrict__ mix, const float* __restrict__ mask, int ld,
+                                                            const int32_t* __restrict__ offs, const int32_t* __restrict__ nframes,
+                                                            int S, float* __restrict__ wav_out,
+                                                            const int64_t* __restrict__ out_offs, int tpb) {
+  __shared__ __attribute__((aligned(16))) float2 rows[RING][RLD];
+  __shared__ __attribute__((aligned(16))) float win[NFFT];
+  __shared__ float2 tw[NFFT];
+  __shared__ float2 t256[256];
+
+  const int us = blockIdx.y;
+  const int u = us / S, col0 = (us - u * S) * NBIN;
+  const int T = nframes[u];
+  const int nout = HOP * (T - 1);
+  const int ntiles = T / FPB + 1;  // hops 0 .. T carry output samples
+  const int tile0 = blockIdx.x * tpb;
+  if (tile0 >= ntiles) return;
+  const int tile1 = min(ntiles, tile0 + tpb);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = lane & 15, fr = 4 * __builtin_amdgcn_readfirstlane(wave) + (lane >> 4);
+  const int64_t oo = out_offs[us];
+
+  RowRegs pre;
+  istft_rows_fetch(pre, tile0 * FPB, T, mix, mask, ld, col0, offs, u);
+  for (int i = tid; i < NFFT; i += 256) {
+    tw[i] = g_tw512[i];
+    win[i] = g_hann512[i];
+  }
+  t256[tid] = g_tw512[(2 * (tid & 15) * (tid >> 4)) & 511];
+  if (tile0 > 0) {  // the 3 frames before this block's first tile (all of them exist: tile0 * FPB - 3 >= 13, < T)
+    const int tf = tile0 * FPB - 3;
+    for (int i = tid; i < 3 * NBIN; i += 256) {
+      const int f3 = i / NBIN, k = i - f3 * NBIN, t = tf + f3;
+      float2 x = make_float2(0.f, 0.f);
+      if (t < T) {
+        const int64_t row = (int64_t)offs[t] + u;
+        const float m = mask[row * ld + col0 + k];
+        x = mix[row * NBIN + k];
+        x.x *= m;
+        x.y *= m;
+      }
+      rows[(t + 3) % RING][k ^ ((t + 3) & 15)] = x;
+    }
+    __syncthreads();
+    if (fr < 3) istft_frame(rows[(tf + fr + 3) % RING], tw, t256, win, j, (tf + fr + 3) & 15);
+  }
+  const int m0 = tid & (HOP - 1), hsel = __builtin_amdgcn_readfirstlane(tid >> 7);
+  float wss_full = 0.f;
+  __syncthreads();  // win is complete
+#pragma unroll
+  for (int q = 3; q >= 0; --q) {
+    const float w = win[q * HOP + m0];
+    wss_full += w * w;
+  }
+  const float inv_full = 1.0f / wss_full;
+
+  for (int tile = tile0; tile < tile1; ++tile) {
+    const int t0 = tile * FPB;
+    __syncthreads();  // the previous tile's overlap-add is done with the slots about to be refilled
+    istft_rows_stash(pre, rows, t0);
+    __syncthreads();
+    if (tile + 1 < tile1) istft_rows_fetch(pre, t0 + FPB, T, mix, mask, ld, col0, offs, u);  // travels under the FFTs
+    istft_frame(rows[(t0 + fr + 3) % RING], tw, t256, win, j, (t0 + fr + 3) & 15);
+    __syncthreads();
+    istft_overlap_add(rows, win, t0, T, nout, m0, hsel, inv_full, wav_out, nullptr, oo);
+  }
+}
+
+// ---- adjoint of mask-apply + iSTFT, fused with the SI-SDR gradient (include/sepkern.h, sk_sisdr_mask_grad).
+// stft_kernel<frame-major> with another sample loader and another epilogue: the "signal" of (utterance j, estimate k) is
+//   g[p] = (A e_k[n] + B r_i[n] + C) * gscale / wss[p],  n = p - 256 in [0, L_j), 0 elsewhere, i = best permutation's source,
+// framed WITHOUT reflection (frame t = g[tH .. tH + 512)); each bin U[t][f] of its windowed transform is contracted with the
+// mixture's bin on the way out: dmask[offs[t] + j][k * 257 + f] = (c_f / 512) (Re X Re U + Im X Im U), c_f = 1 at f = 0, 256, else 2.
+__global__ __launch_bounds__(256, 4) void sisdr_grad_kernel(const float* __restrict__ est, const int64_t* __restrict__ est_offs,
+                                                            const void* __restrict__ ref, int pcm16,
+                                                            const int64_t* __restrict__ ref_offs,
+                                                            const int32_t* __restrict__ nframes,
+                                                            const int32_t* __restrict__ best_perm, const float* __restrict__ coef,
+                                                            const float* __restrict__ gscale, const float2* __restrict__ mix,
+                                                            const int32_t* __restrict__ offs, int S, float* __restrict__ dmask,
+                                                            int ld) {
+  __shared__ __attribute__((aligned(16))) float smp[NFFT + (FPB - 1) * HOP];
+  __shared__ __attribute__((aligned(16))) float win[NFFT];
+  __shared__ float2 tw[NFFT];
+  __shared__ float2 t256[256];
+  __shared__ float xch[16][16 * XLD];
+
+  const int us = blockIdx.y;
+  const int u = us / S, ks = us - u * S;
+  const int T = nframes[u];
+  const int L = HOP * (T - 1);
+  const int tile0 = blockIdx.x * TPB;
+  if (tile0 * FPB >= T) return;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int perm[SK_MAXS];
+  sk_nth_perm(best_perm[u], S, perm);
+  int src = perm[0];
+#pragma unroll
+  for (int q = 1; q < SK_MAXS; ++q) src = (q < S && ks == q) ? perm[q] : src;
+  const float gs = gscale[0];
+  const float cA = coef[3 * us] * gs, cB = coef[3 * us + 1] * gs * (pcm16 ? 1.0f / 32768.0f : 1.0f), cC = coef[3 * us + 2] * gs;
+  const float* const ep = est + est_offs[us];
+  const int64_t roff = ref_offs[u * S + src];
+  constexpr int SPAN = NFFT + (FPB - 1) * HOP, SPT = (SPAN + 255) / 256;
+
+  // every sample a thread loads has the same position m0 inside its hop (tiles start on hop boundaries, 256 = 2 hops)
+  const int m0 = tid & (HOP - 1);
+  float wsq[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const float w = g_hann512[q * HOP + m0];
+    wsq[q] = w * w;
+  }
+  const float inv_full = 1.0f / (((wsq[3] + wsq[2]) + wsq[1]) + wsq[0]);  // the order istft_overlap_add sums in
+
+  auto fetch = [&](int t0, float (&r)[SPT]) {
+#pragma unroll
+    for (int q = 0; q < SPT; ++q) {
+      const int i = tid + 256 * q;
+      const int p = t0 * HOP + i, n = p - NFFT / 2;
+      float v = 0.f;
+      if (i < SPAN && n >= 0 && n < L) {
+        const float rv = pcm16 ? (float)((const int16_t*)ref)[roff + n] : ((const float*)ref)[roff + n];
+        const int hp = p >> 7;  // frames hp - 3 .. hp cover p
+        float inv = inv_full;
+        if (hp < 3 || hp >= T) {
+          float wss = 0.f;
+#pragma unroll
+          for (int qq = 3; qq >= 0; --qq)
+            if (hp - qq >= 0 && hp - qq < T) wss += wsq[qq];
+          inv = wss > 1.17549435e-38f ? 1.0f / wss : 1.0f;
         }
-        if (wss > 1.17549435e-38f) acc /= wss;
+        v = (cA * ep[n] + cB * rv + cC) * inv;
       }
-      if (wav_out) wav_out[oo + n] = acc;
-      if (pcm_out) {
-        const float sv = acc * 32767.0f;
-        pcm_out[oo + n] = (int16_t)(long long)sv;  // truncation toward zero, wrap on overflow
+      r[q] = v;
+    }
+  };
+  auto stash = [&](const float (&r)[SPT]) {
+#pragma unroll
+    for (int q = 0; q < SPT; ++q) {
+      const int i = tid + 256 * q;
+      if (i < SPAN) smp[i] = r[q];
+    }
+  };
+
+  for (int i = tid; i < NFFT; i += 256) {
+    tw[i] = g_tw512[i];
+    win[i] = g_hann512[i];
+  }
+  t256[tid] = g_tw512[(2 * (tid & 15) * (tid >> 4)) & 511];
+  float pre[SPT];
+  fetch(tile0 * FPB, pre);
+  stash(pre);
+  __syncthreads();
+
+  const int j = lane & 15, g = lane >> 4;
+  const int fr = 4 * wave + g;
+  const int partner = (lane & 48) | ((16 - j) & 15);
+  for (int ti = 0; ti < TPB; ++ti) {
+    const int t0 = (tile0 + ti) * FPB;
+    if (t0 >= T) break;  // block-uniform
+    const int nfr = min(FPB, T - t0);
+    const bool more = ti + 1 < TPB && t0 + FPB < T;
+    if (more) fetch(t0 + FPB, pre);
+    const bool active = fr < nfr;
+    v2f z[16];
+#pragma unroll
+    for (int n1 = 0; n1 < 16; ++n1) {
+      const v2f sm = *reinterpret_cast<const v2f*>(&smp[fr * HOP + 32 * n1 + 2 * j]);
+      const v2f w = *reinterpret_cast<const v2f*>(&win[32 * n1 + 2 * j]);
+      z[n1] = sm * w;
+    }
+    fft256_g16(z, xch[4 * wave + g], t256, j);
+
+    // real-FFT split as in stft_kernel; every bin is contracted with the mixture's and stored straight from registers
+    const int64_t row = active ? (int64_t)offs[t0 + fr] + u : 0;
+    const float2* const xlo = mix + row * NBIN + j;
+    const float2* const xhi = mix + row * NBIN + (256 - j);
+    float* const dlo = dmask + row * ld + ks * NBIN + j;
+    float* const dhi = dmask + row * ld + ks * NBIN + (256 - j);
+    if (active) {
+#pragma unroll
+      for (int k2 = 0; k2 < 8; ++k2) {
+        v2f zc;
+        zc.x = __shfl(z[15 - k2].x, partner, 64);
+        zc.y = __shfl(z[15 - k2].y, partner, 64);
+        if (j == 0) zc = z[(16 - k2) & 15];
+        const v2f zk = z[k2], cz = conj(zc);
+        const int k = j + 16 * k2;
+        const v2f A = 0.5f * (zk + cz), Bt = cmul(ld2(&tw[k]), 0.5f * mul_mi(zk - cz));
+        const v2f ua = A + Bt, ub = conj(A - Bt);  // U[k], U[256 - k]
+        const v2f xa = ld2(xlo + 16 * k2), xb = ld2(xhi - 16 * k2);
+        const float sa = (k == 0) ? 1.0f / 512.0f : 2.0f / 512.0f;  // bin 256 - k is the Nyquist bin exactly when k == 0
+        dlo[16 * k2] = sa * (xa.x * ua.x + xa.y * ua.y);
+        dhi[-16 * k2] = sa * (xb.x * ub.x + xb.y * ub.y);
       }
+      if (j == 0) {  // bin 128 pairs with itself
+        const v2f zk = z[8], cz = conj(zk);
+        const v2f ua = 0.5f * (zk + cz) + cmul(ld2(&tw[128]), 0.5f * mul_mi(zk - cz));
+        const v2f xa = ld2(xlo + 128);
+        dlo[128] = (2.0f / 512.0f) * (xa.x * ua.x + xa.y * ua.y);
+      }
+    }
+    __syncthreads();  // every wave is done with smp
+    if (more) {
+      stash(pre);
+      __syncthreads();
     }
   }
 }
@@ -523,5 +778,41 @@ extern "C" int sk_mask_istft(const void* mix_c64, const int64_t* mix_offs, const
   hipLaunchKernelGGL(istft_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float2*)mix_c64, mix_offs, mix_st,
                      mix_sf, mask, mask_offs, mask_st, mask_sf, nframes, S, wav_out, pcm_out, out_offs, tpb);
   SK_CHECK_LAUNCH("sk_mask_istft");
+  return SK_OK;
+}
+
+extern "C" int sk_mask_istft_rows(const void* mix_rows_c64, const float* mask, int ld, const int32_t* offs,
+                                  const int32_t* nframes, int B, int S, int n_fft, int hop, float* wav_out,
+                                  const int64_t* out_offs, int max_frames, sk_stream_t stream) {
+  SK_CHECK_ARG(n_fft == NFFT && hop == HOP, "sk_mask_istft_rows: only n_fft=512, hop=128 are built (got %d, %d)", n_fft, hop);
+  SK_CHECK_ARG(S >= 1 && S <= SK_MAXS, "sk_mask_istft_rows: num_spk %d outside 1..%d", S, SK_MAXS);
+  SK_CHECK_ARG(mix_rows_c64 && mask && offs && nframes && wav_out && out_offs, "sk_mask_istft_rows: null pointer");
+  SK_CHECK_ARG(ld >= S * NBIN, "sk_mask_istft_rows: mask rows of %d floats hold fewer than S*F = %d", ld, S * NBIN);
+  SK_CHECK_ARG(B > 0 && (int64_t)B * S <= 65535 && max_frames > 1, "sk_mask_istft_rows: bad sizes");
+  const int ntiles = max_frames / FPB + 1;
+  const int64_t total = (int64_t)ntiles * B * S;
+  const int tpb = (int)std::min<int64_t>(std::max<int64_t>(total / 2048, 2), ntiles);
+  dim3 grid((unsigned)sk_cdiv(ntiles, tpb), (unsigned)(B * S));
+  hipLaunchKernelGGL(istft_rows_kernel, grid, dim3(256), 0, (hipStream_t)stream, (const float2*)mix_rows_c64, mask, ld, offs,
+                     nframes, S, wav_out, out_offs, tpb);
+  SK_CHECK_LAUNCH("sk_mask_istft_rows");
+  return SK_OK;
+}
+
+extern "C" int sk_sisdr_mask_grad(const float* est, const int64_t* est_offs, const void* ref, int pcm16,
+                                  const int64_t* ref_offs, const int32_t* nframes, const int32_t* best_perm,
+                                  const float* coef, const float* gscale, const void* mix_rows_c64, const int32_t* offs,
+                                  int B, int S, int n_fft, int hop, int max_frames, float* dmask, int ld,
+                                  sk_stream_t stream) {
+  SK_CHECK_ARG(n_fft == NFFT && hop == HOP, "sk_sisdr_mask_grad: only n_fft=512, hop=128 are built (got %d, %d)", n_fft, hop);
+  SK_CHECK_ARG(S >= 1 && S <= SK_MAXS, "sk_sisdr_mask_grad: num_spk %d outside 1..%d", S, SK_MAXS);
+  SK_CHECK_ARG(est && est_offs && ref && ref_offs && nframes && best_perm && coef && gscale && mix_rows_c64 && offs && dmask,
+               "sk_sisdr_mask_grad: null pointer");
+  SK_CHECK_ARG(ld >= S * NBIN, "sk_sisdr_mask_grad: dmask rows of %d floats hold fewer than S*F = %d", ld, S * NBIN);
+  SK_CHECK_ARG(B > 0 && (int64_t)B * S <= 65535 && max_frames > 1, "sk_sisdr_mask_grad: bad sizes");
+  dim3 grid((unsigned)sk_cdiv(max_frames, FPB * TPB), (unsigned)(B * S));
+  hipLaunchKernelGGL(sisdr_grad_kernel, grid, dim3(256), 0, (hipStream_t)stream, est, est_offs, ref, pcm16, ref_offs, nframes,
+                     best_perm, coef, gscale, (const float2*)mix_rows_c64, offs, S, dmask, ld);
+  SK_CHECK_LAUNCH("sk_sisdr_mask_grad");
   return SK_OK;
 }

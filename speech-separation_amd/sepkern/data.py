@@ -66,6 +66,41 @@ def features_from_pcm(pcm, dev):
   return feats[0], feats[1:], pk
 
 
+def wave_features_from_pcm(pcm, dev, source_mags=True):
+  """features_from_pcm for a loss that works on waveforms (archs/uPIT.py, loss=sisdr): the same batch ->
+  (mix (R,F), [source (R,F)...], Packing, wave), wave = {'mixc': the mixture's COMPLEX STFT as packed rows (Rp, F) complex64,
+  'flat': the batch's int16 PCM on the device (key-major, as the collator laid it out), 'nsamp': samples per utterance,
+  'sig_offs': {key: [offset of utterance j's signal in flat]}}.  The magnitudes are the same sk_stft launches as
+  features_from_pcm's (bit-identical network input); source_mags=False skips the sources' (a waveform loss does not read
+  them; the list is then empty)."""
+  import torch
+  from . import ops
+  from .packing import Packing
+  ns = [int(n) for n in pcm['lens']]
+  B, F = len(ns), 257
+  pk = Packing.from_lens([1 + n // 128 for n in ns], dev)
+  if pk.perm is not None:
+    raise ValueError("wave_features_from_pcm: the batch must be sorted by frame count, longest first (WavCollator does)")
+  flat = pcm['flat']
+  if flat.device != torch.device(dev):
+    flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
+  total = sum(ns)
+  starts = [sum(ns[:j]) for j in range(B)]
+  grid = dict(lengths=ns, out_offs=[b * F for b in range(B)], stride_t=[B * F] * B, stride_f=[1] * B)
+  feats = []
+  for q, _ in enumerate(pcm['keys'] if source_mags else pcm['keys'][:1]):
+    out = torch.zeros(pk.T, B, F, device=dev)
+    ops.stft_batch(flat[q * total:(q + 1) * total], out=out, **grid)
+    feats.append(pk.pack(out))
+  outc = torch.zeros(pk.T, B, F, dtype=torch.complex64, device=dev)
+  ops.stft_batch(flat[:total], want_complex=True, out=outc, **grid)
+  mixc = torch.view_as_complex(pk.pack(torch.view_as_real(outc).view(pk.T, B, 2 * F)).view(-1, F, 2))
+  flat.record_stream(torch.cuda.current_stream(dev))
+  wave = {'mixc': mixc, 'flat': flat, 'nsamp': ns,
+          'sig_offs': {k: [q * total + st for st in starts] for q, k in enumerate(pcm['keys'])}}
+  return feats[0], feats[1:], pk, wave
+
+
 # ----------------------------------------------------------------------------------------------- staging ahead of the step
 class Prefetcher:
   """Iterates a DataLoader of the arch's batches and hands them over ALREADY ON THE GPU, as packed rows.
@@ -78,14 +113,16 @@ class Prefetcher:
       asynchronous H2D per key, no padding anywhere; the batch arrives as {'packed': (mix, [sources], Packing)};
     * PCM batches (WavTrainSet, --wav-input): the int16 samples are copied and the STFT runs on the copy stream too.
   The consumer's stream waits for the batch's event; nothing on the host blocks.  Everything else in a batch (names,
-  ...) passes through untouched."""
+  ...) passes through untouched.
+  keep_wave (PCM batches only): the staged batch also carries 'wave' -- the mixture's complex rows and the device PCM
+  (wave_features_from_pcm) -- for a loss that works on waveforms; the sources' magnitudes are then not computed."""
 
   _END = object()
 
-  def __init__(self, loader, device, depth=2):
+  def __init__(self, loader, device, depth=2, keep_wave=False):
     import queue
     import threading
-    self.loader, self.device, self.depth = loader, device, max(1, int(depth))
+    self.loader, self.device, self.depth, self.keep_wave = loader, device, max(1, int(depth)), bool(keep_wave)
     self._queue_mod, self._threading = queue, threading
     self._stuck = None          # a staging thread that did not end when its consumer left early
 
@@ -131,7 +168,7 @@ class Prefetcher:
             except StopIteration:
               break
             t1 = time.perf_counter()
-            staged = self.stage(batch, dev)
+            staged = self.stage(batch, dev, self.keep_wave)
             ev = torch.cuda.Event()
             ev.record(stream)
             if timing:
@@ -179,11 +216,16 @@ class Prefetcher:
       for s in p[1]:
         yield s
       yield p[2].lens              # (lens / offs / perm are views of one staging tensor)
+    w = staged.get('wave') if isinstance(staged, dict) else None
+    if w is not None:
+      yield w['mixc']
+      yield w['flat']
 
   @staticmethod
-  def stage(batch, dev):
+  def stage(batch, dev, keep_wave=False):
     """One batch -> {'packed': (mix (R,F), [source (R,F)...], Packing), <other keys unchanged>} on `dev`, enqueued on the
-    CURRENT stream."""
+    CURRENT stream.  keep_wave: a PCM batch also gets 'wave' (wave_features_from_pcm; no source magnitudes); a batch that
+    holds no PCM cannot, which is an error here rather than at the loss."""
     import torch
     from torch.nn.utils.rnn import PackedSequence
     from .packing import Packing
@@ -192,11 +234,16 @@ class Prefetcher:
     if 'pcm' in batch:                   # WavCollator: {'pcm': {'flat': int16 tensor, 'keys', 'lens'}}: one pinned copy, STFT here
       pcm = batch['pcm']
       host = pcm['flat'] if pcm['flat'].is_pinned() else pcm['flat'].pin_memory()
-      mix, sources, pk = features_from_pcm(dict(pcm, flat=host), dev)
       out = {k: v for k, v in batch.items() if k != 'pcm'}
+      if keep_wave:
+        mix, sources, pk, out['wave'] = wave_features_from_pcm(dict(pcm, flat=host), dev, source_mags=False)
+      else:
+        mix, sources, pk = features_from_pcm(dict(pcm, flat=host), dev)
       out['packed'] = (mix, sources, pk)
       out['_keepalive'] = host
       return out
+    if keep_wave:
+      raise ValueError("Prefetcher(keep_wave=True) needs PCM batches (WavTrainSet / --wav-input): this batch holds no waveforms")
     seqs = {k: v for k, v in batch.items() if isinstance(v, PackedSequence)}
     if 'mix' not in seqs:
       return batch

@@ -449,6 +449,117 @@ def pit_mse_bwd(mask, mix, srcs, best_perm, out, gscale, packing=None, repeat=1)
     return dmask
 
 
+# ----------------------------------------------------------------------------- SI-SDR uPIT loss (waveform domain)
+def _est_offsets(pk, S):
+    """Offsets (host list, j * S + s) of the estimates of a packed batch in one flat buffer, and its length: utterance j has
+    128 (T_j - 1) samples per source."""
+    offs, acc = [], 0
+    for T in pk.lens_host:
+        for _ in range(S):
+            offs.append(acc)
+            acc += 128 * (int(T) - 1)
+    return offs, acc
+
+
+def mask_istft_rows(mixc, mask, pk, S, est_offs=None, repeat=1):
+    """Mask-apply + iSTFT on PACKED rows: mixc (>= R, 257) complex64, mask (>= R, ld >= S*257) float32 rows of the batch pk
+    -> (est: flat float32, est_offs: int64 device (B*S), offsets: the same as a host list).  Estimate s of utterance j is the
+    128 (T_j - 1) samples at offsets[j * S + s] -- what sk_mask_istft computes from the same spectra in its own layout.
+    est_offs: the device copy of the offsets when the caller made it ahead of time (the upload is a synchronous copy: made
+    behind a network's forward pass it would hold the host until that pass has run)."""
+    _chk(mixc, torch.complex64)
+    _chk(mask)
+    if pk.perm is not None:
+        raise _lib.SepkernError("mask_istft_rows needs a length-sorted batch (Packing without perm)")
+    if mixc.dim() != 2 or mixc.shape[1] != 257 or not mixc.is_contiguous() or mask.dim() != 2 or mask.stride(1) != 1:
+        raise _lib.SepkernError("mask_istft_rows: mixc must be (R, 257) contiguous, mask (R, ld) with unit column stride")
+    if mixc.shape[0] < pk.R or mask.shape[0] < pk.R or pk.lens_host[-1] < 2:
+        raise _lib.SepkernError("mask_istft_rows: fewer rows than the batch has frames, or an utterance of one frame")
+    offsets, total = _est_offsets(pk, S)
+    est = torch.empty(total, dtype=torch.float32, device=mixc.device)
+    d_offs = _i64(offsets, mixc.device) if est_offs is None else est_offs
+    _chk(d_offs, torch.int64)
+    # algorithmic bytes per frame and source: the complex spectrum, the mask, 128 samples out
+    with _timed("istft_rows_kernel", repeat * float(pk.R) * S * (257 * 8 + 257 * 4 + 128 * 4)):
+        for _ in range(repeat):
+            _lib.call("sk_mask_istft_rows", _ptr(mixc), _ptr(mask), int(mask.stride(0)), _ptr(pk.offs), _ptr(pk.lens), pk.B, S, 512, 128,
+                      _ptr(est), _ptr(d_offs), pk.T, _stream())
+    return est, d_offs, offsets
+
+
+def sisdr_descriptors(pk, sig_offs, S):
+    """The small device tables of one batch's SI-SDR loss, uploaded in one go BEFORE the network runs: est_offs (B*S) int64 as
+    mask_istft_rows lays the estimates out, ref_offs (B*S) int64 from sig_offs = {'source<i>': [offset of utterance j]}, nsamp
+    (B) int32 = 128 (T_j - 1)."""
+    offsets, _ = _est_offsets(pk, S)
+    refs = [int(sig_offs["source%d" % (i + 1)][j]) for j in range(pk.B) for i in range(S)]
+    both = _i64(offsets + refs, pk.device)
+    return dict(est_offs=both[:pk.B * S], ref_offs=both[pk.B * S:], nsamp=(pk.lens - 1) * 128)
+
+
+def sisdr_pit_fwd(est, est_offs, ref, ref_offs, nsamp, S, max_samples, count_dev=None, repeat=1):
+    """PIT on SI-SDR.  est: flat float32 estimates at est_offs (int64 device, B*S: j * S + k); ref: flat references, float32 or
+    int16 PCM (scaled by 1/32768), reference i of utterance j at ref_offs[j * S + i]; nsamp int32 device (B): samples per
+    utterance; count_dev: optional device scalar replacing B (the global utterance count under data parallelism) ->
+    dict(out (3,) = [-mean best score, count, sum of best scores], pair (B,S,S) dB, perm_score (S!,B), best_perm (B),
+    coef (B,S,3))."""
+    _chk(est)
+    pcm16 = ref.dtype == torch.int16
+    _chk(ref, torch.int16 if pcm16 else torch.float32)
+    _chk(est_offs, torch.int64)
+    _chk(ref_offs, torch.int64)
+    _chk(nsamp, torch.int32)
+    _chk(count_dev)
+    B = int(nsamp.numel())
+    if est_offs.numel() != B * S or ref_offs.numel() != B * S:
+        raise _lib.SepkernError("sisdr_pit_fwd: need B*S estimate and reference offsets")
+    nperm = 1
+    for i in range(2, S + 1):
+        nperm *= i
+    dev = est.device
+    pair = torch.empty(B, S, S, device=dev)
+    perm_score = torch.empty(nperm, B, device=dev)
+    best = torch.empty(B, dtype=torch.int32, device=dev)
+    out = torch.empty(3, device=dev)
+    coef = torch.empty(B, S, 3, device=dev)
+    ws = workspace(_lib.load().sk_sisdr_workspace_bytes(B, S, int(max_samples)), "sisdr")
+    # algorithmic bytes: every estimate and every reference sample once
+    with _timed("sisdr_fwd", repeat * float(est.numel()) * (4 + (2 if pcm16 else 4))):
+        for _ in range(repeat):
+            _lib.call("sk_sisdr_pit_fwd", _ptr(est), _ptr(est_offs), _ptr(ref), int(pcm16), _ptr(ref_offs), _ptr(nsamp), B, S,
+                      int(max_samples), _ptr(count_dev), _ptr(pair), _ptr(perm_score), _ptr(best), _ptr(out), _ptr(coef), _ptr(ws),
+                      _stream())
+    return dict(out=out, pair=pair, perm_score=perm_score, best_perm=best, coef=coef)
+
+
+def sisdr_mask_grad(est, est_offs, ref, ref_offs, best_perm, coef, gscale, mixc, pk, S, ld=None, out=None, repeat=1):
+    """dmask (Rp, ld) = gscale * d loss / d mask of the SI-SDR uPIT loss (sk_sisdr_mask_grad): the SI-SDR gradient and the
+    adjoint of mask-apply + iSTFT in one kernel.  Rows of the batch's frames are written, columns < S*257; the tail rows of a
+    fresh buffer are zeroed (as pit_mse_bwd leaves them); `out` (>= R rows) is written in place and otherwise left alone."""
+    pcm16 = ref.dtype == torch.int16
+    _chk(est)
+    _chk(ref, torch.int16 if pcm16 else torch.float32)
+    _chk(mixc, torch.complex64)
+    _chk(gscale)
+    _chk(coef)
+    _chk(best_perm, torch.int32)
+    if out is None:
+        ld = S * 257 if ld is None else int(ld)
+        out = torch.empty(pk.Rp, ld, dtype=torch.float32, device=est.device)
+        if pk.Rp > pk.R:
+            out[pk.R:].zero_()
+    _chk(out)
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < pk.R or mixc.shape[0] < pk.R or not mixc.is_contiguous():
+        raise _lib.SepkernError("sisdr_mask_grad: dmask / mixture rows do not cover the batch")
+    # algorithmic bytes per frame and source: 2 x 128 new samples, the mixture's complex row, 257 gradients out
+    with _timed("sisdr_bwd", repeat * float(pk.R) * S * (128 * (4 + (2 if pcm16 else 4)) + 257 * 8 + 257 * 4)):
+        for _ in range(repeat):
+            _lib.call("sk_sisdr_mask_grad", _ptr(est), _ptr(est_offs), _ptr(ref), int(pcm16), _ptr(ref_offs), _ptr(pk.lens),
+                      _ptr(best_perm), _ptr(coef), _ptr(gscale), _ptr(mixc), _ptr(pk.offs), pk.B, S, 512, 128, pk.T, _ptr(out),
+                      int(out.stride(0)), _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- RSH loss / attention
 def rsh_loss_fwd(mask, x, srcs, lens, used):
     """One greedy-assignment pass.  mask (T,B,F), x (T,B,2F) [mixture | attention], srcs list of S (T,B,F),

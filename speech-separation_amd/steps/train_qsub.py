@@ -133,6 +133,17 @@ def read_model_conf(path):
   return conf
 
 
+def waveform_loss(m, args):
+  """True when the conf file selects a loss that works on waveforms (archs/uPIT.py: loss=sisdr).  Such a loss cannot be
+  computed from npz magnitude features: without --wav-input the run ends here, not at its first batch."""
+  if not hasattr(m, "parse_loss"):
+    return False
+  kind = m.parse_loss(read_model_conf(args.model_config).get('loss', 'mse'))
+  if kind == 'sisdr' and not args.wav_input:
+    raise SystemExit(m.NEEDS_WAVEFORMS)
+  return kind == 'sisdr'
+
+
 # ----------------------------------------------------------------------------------------------- data
 def training_batches(m, args, rank, world):
   """DataLoader over this rank's share of the training set, and the sampler to re-seed per epoch (or None).
@@ -170,7 +181,8 @@ def staged(loader, args):
   if args.prefetch <= 0:
     return loader
   from sepkern.data import Prefetcher
-  return Prefetcher(loader, torch.device("cuda", torch.cuda.current_device()), depth=args.prefetch)
+  return Prefetcher(loader, torch.device("cuda", torch.cuda.current_device()), depth=args.prefetch,
+                    keep_wave=getattr(args, "keep_wave", False))
 
 
 def validation_batches(m, args, rank, world):
@@ -287,7 +299,9 @@ def train_epoch(m, model, optimizer, batches, epoch, world, torch_clip):
     win[0] += loss.detach().double() * norm.double()
     # under data parallelism `norm` is already the global frame count: every rank adds its 1/world share
     win[1] += norm.double() / world
-    win[2] += norm.double() / world
+    # (an arch whose norm is not frames x feat_dim -- uPIT with loss=sisdr counts utterances -- says how many frames the step had)
+    frames = getattr(model, "step_frames", None)
+    win[2] += norm.double() / world if frames is None else float(frames) * float(getattr(model, "feat_dim", 257))
     loss.backward()
     if torch_clip:
       # torch's optimizer knows nothing of the guard word: look at it here (one host sync per step on this
@@ -397,6 +411,7 @@ def main(argv=None):
     print("Using " + args.arch_file + " DNN architecture")
     print("Using GPU", gpu, "of", world)
   m = __import__(args.arch_file)
+  args.keep_wave = waveform_loss(m, args)        # (the prefetcher then carries the waveforms with the staged batch)
   torch.cuda.set_device(gpu)
   from sepkern.data import host_threads
   host_threads()                                 # (the arithmetic is on the GPU; see sepkern.data.host_threads)
