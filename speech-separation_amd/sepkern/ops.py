@@ -181,6 +181,9 @@ class Planes:
         self.rows, self.ld = t.shape[1], t.shape[2]
         self.plane = t.stride(0)
 
+    def record_stream(self, stream):
+        self.t.record_stream(stream)
+
     @staticmethod
     def empty(R, C, device, zero_tail=True):
         rows, ld = pad_to(R, 64), pad_to(C, 8)

@@ -6,6 +6,8 @@ for the GEMMs and the recurrences the kernel the library chose (sk_gemm_last_ker
 generated from that is the one DESIGN.md section 4 carries between its census markers: this test regenerates it and compares,
 so the document cannot go stale.
 `python tests/test_gpu_census.py` prints the table (and writes gpurun_out/census.md).
+It also writes census_order.txt beside census.md: per configuration the launches in the order they were enqueued -- what a
+host-side change of the engine must leave as it is, stream by stream.
 """
 import os
 import sys
@@ -61,7 +63,7 @@ def _lstm_row(name, T, B, H):
 class Spy:
     def __init__(self):
         from sepkern import _lib
-        self._lib, self.rows, self.orig = _lib, {}, _lib.call
+        self._lib, self.rows, self.seq, self.orig = _lib, {}, [], _lib.call
 
     def __enter__(self):
         lib = self._lib
@@ -90,6 +92,7 @@ class Spy:
             else:
                 return
             self.rows[key] = self.rows.get(key, 0) + 1
+            self.seq.append(key)
         lib.call = call
         return self
 
@@ -99,7 +102,7 @@ class Spy:
 
 
 def _step(arch, H, L, S, B, T, dtype, env=None, ragged=False):
-    """One training step of the given configuration on a uniform batch; returns the spy's rows."""
+    """One training step of the given configuration on a uniform batch; returns the spy (rows: counts, seq: enqueue order)."""
     import uPIT
     from sepkern.optim import ClipAdam
     from sepkern.packing import Packing
@@ -137,7 +140,7 @@ def _step(arch, H, L, S, B, T, dtype, env=None, ragged=False):
             step()
             torch.cuda.synchronize()
         model.check_status()
-        return spy.rows
+        return spy
     finally:
         for k, v in saved.items():
             if v is None:
@@ -160,10 +163,14 @@ CONFIGS = (
 )
 
 
-def census_markdown():
+def census_markdown(sequence=None):
+    """The census tables; sequence (a list): receives, per configuration, one line per launch in enqueue order."""
     out = []
     for title, cfg in CONFIGS:
-        rows = _step(**cfg)
+        spy = _step(**cfg)
+        rows = spy.rows
+        if sequence is not None:
+            sequence += ["== " + title] + [" | ".join(k) for k in spy.seq]
         out.append("**%s** -- one training step:" % title)
         out.append("")
         out.append("| launches | entry point | kernel | shape / grid | stream |")
@@ -200,8 +207,11 @@ def test_design_md_carries_the_generated_census():
 
 
 if __name__ == "__main__":
-    text = census_markdown()
+    seq = []
+    text = census_markdown(seq)
     os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
     with open(os.path.join(ROOT, "gpurun_out", "census.md"), "w") as fh:
         fh.write(text)
+        with open(os.path.join(os.path.dirname(fh.name), "census_order.txt"), "w") as fo:      # beside census.md
+            fo.write("\n".join(seq) + "\n")
     print(text)
