@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 134
+#define SK_VERSION 135
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -66,6 +66,25 @@ int sk_device_info(int* num_cu, int* lds_bytes);
 int sk_stft(const void* wav, int pcm16, const int64_t* wav_offs, const int32_t* nsamp, int nutt,
             int n_fft, int hop, int want_complex, void* out, const int64_t* out_offs,
             const int64_t* stride_t, const int64_t* stride_f, int frame_major, int max_frames, sk_stream_t stream);
+
+/* ---------------------------------------------------------------- resampling front end
+ * Replaces the `sr=` half of librosa.core.load (reference steps/extract_feats.py:74,85,97,104, steps/evaluate_oracle.py:96,122):
+ * band-limited sinc interpolation with resampy's kaiser_best filter (64 zero crossings, Kaiser window), every tap evaluated
+ * exactly; the arithmetic and the tap table are sepkern/resample.py's (unpinned: neither package is available to test against).
+ * Rate ratio L / M = sr_out / sr_in in lowest terms, L != M.  Signal u: n_in[u] samples at in + in_offs[u] (float32, or int16
+ * PCM scaled by 1/32768 when pcm16 != 0 -- sk_stft's convention); its n_out[u] float32 outputs go to out + out_offs[u]
+ * (elements), nothing beyond them is written:
+ *   y[n] = sum_{i < ntaps} taps[i * L + n % L] * x[first(n) + i],  first(n) = floor((n M - 64 max(L, M)) / L) + 1,
+ * x = 0 outside [0, n_in[u]), fp32 accumulation with i ascending (bitwise reproducible; no atomics).
+ * taps: ntaps x L float32, TAP-major, column c = the row of the outputs with n % L == c (phase (c M) % L), the factor
+ * min(1, L / M) included; ntaps must equal 128 max(L, M) / L + 1 (integer division): 257 for 2:1, 706 for 441:80, 129 upwards.
+ * The descriptor arrays live on the device; max_out >= max_u n_out[u] sizes the grid; 1 <= nsig <= 65535 (the grid's y).
+ * A workgroup stages (tile - 1) M / L + 2 + ntaps samples, plus the ntaps taps when L == 1, in LDS, tile = 1024, 512 or 256
+ * outputs, the largest that fits 60 KB.  A ratio whose 256-output tile does not fit is SK_EINVAL: M > 30 when L == 1
+ * (511 M + 4 floats), M / L beyond 40.09 otherwise (383 M / L + 3 floats). */
+int sk_resample(const void* in, int pcm16, const int64_t* in_offs, const int32_t* n_in, int nsig,
+                const float* taps, int L, int M, int ntaps,
+                float* out, const int64_t* out_offs, const int32_t* n_out, int max_out, sk_stream_t stream);
 
 /* ---------------------------------------------------------------- mask-apply + iSTFT back end
  * Replaces np.multiply(mix_spec, mask) + librosa.core.istft(hop_length=128) + (*32767).astype(int16)

@@ -113,42 +113,67 @@ class WavTrainSet(Dataset):
   of the recipe would have stored as npz is computed on the GPU inside compute_loss (sk_stft straight into the
   padded (T,B,F) batch).  12x less host I/O than float32 spectrograms and no zlib in the loader."""
 
-  def __init__(self, datadir, location=""):
+  def __init__(self, datadir, location="", sample_rate=None):
     import glob
     self.items = []
     for line in open(datadir + "/wav.scp"):
       reco_id, filename = line.rstrip('\n').split(' ')
       self.items.append(sorted(glob.glob(filename.replace("/mix/", "/*/"))))
-    self.collator = WavCollator()
+    # sample_rate (steps/train_qsub.py --sample-rate): the rate the network works at.  None: the files' own rate is never
+    # looked at (the recipe's data is wav8k).  With a rate, the loader still ships the int16 PCM as it is on disk -- at the
+    # file's rate, which it records -- and the batch is resampled on the GPU in front of the STFT (sk_resample), as the
+    # reference's librosa.load(path, sr=) does on the host.
+    self.sample_rate = None if sample_rate is None else int(sample_rate)
+    self.collator = WavCollator(self.sample_rate)
 
   def __len__(self):
     return len(self.items)
 
   def frame_counts(self):
     from sepkern.data import wav_frames
-    return [wav_frames(files[0]) for files in self.items]
+    return [wav_frames(files[0], sample_rate=self.sample_rate) for files in self.items]
 
   def __getitem__(self, idx):
     import scipy.io.wavfile
-    out = {}
+    out, rate = {}, None
     for i, f in enumerate(self.items[idx]):
       fs, x = scipy.io.wavfile.read(f)
       if x.dtype != np.int16 or x.ndim != 1:
         raise ValueError("%s: only mono 16-bit PCM wav is supported" % f)
+      if self.sample_rate is not None and rate is not None and fs != rate:
+        raise ValueError("%s is sampled at %d Hz, its mixture at %d: the sources of a mixture must share its rate" % (f, fs, rate))
+      rate = fs
       out['mix' if i == 0 else 'source' + str(i)] = x
     if len(out) == 1:
       out['source1'] = out['mix']
+    if self.sample_rate is not None:
+      out['rate'] = int(rate)
     return out
 
 
 class WavCollator():
   """Sorts by frame count (descending, as Collator does) and hands the batch over as ONE int16 tensor: the signals of all
-  utterances, key-major ('mix', 'source1', ...), longest utterance first -- {'pcm': {'flat', 'keys', 'lens'}}.  One tensor
+  utterances, key-major ('mix', 'source1', ...), longest utterance first -- {'pcm': {'flat', 'keys', 'lens'}}.  With
+  sample_rate (WavTrainSet(sample_rate=...)) the samples say at which 'rate' they were recorded, the frame counts are those at
+  sample_rate, and the batch also carries {'rate': [per utterance], 'target_rate': sample_rate}.  One tensor
   crosses from the loader's worker process to the trainer instead of 32 x (S + 1) (each of which costs a shared-memory
   hand-over: measured 15-18 ms per batch whatever the worker count, more than a 14 ms bf16 step)."""
 
+  def __init__(self, sample_rate=None):
+    self.sample_rate = None if sample_rate is None else int(sample_rate)
+
   def __call__(self, batch):
-    order = np.argsort(np.array([1 + len(d['mix']) // 128 for d in batch]))[::-1]
+    if self.sample_rate is None:
+      rates = None
+      frames = [1 + len(d['mix']) // 128 for d in batch]
+    else:        # every sample carries 'rate', the rate of its files: the order is that of the frame counts AFTER resampling
+      from sepkern.resample import out_len
+      if any('rate' not in d for d in batch):
+        raise ValueError("WavCollator(sample_rate=%d): a sample does not say at which rate it was recorded ('rate')" % self.sample_rate)
+      rates = [int(d['rate']) for d in batch]
+      batch = [{k: v for k, v in d.items() if k != 'rate'} for d in batch]
+      frames = [1 + out_len(len(d['mix']), r, self.sample_rate) // 128 for d, r in zip(batch, rates)]
+    order = np.argsort(np.array(frames))[::-1]
     others = [k for k in batch[0] if k != 'mix']
     bad = [k for k in others if not (k.startswith('source') and k[6:].isdigit())]
     if bad:
@@ -162,7 +187,11 @@ class WavCollator():
           raise ValueError("WavCollator: signal %r of an utterance has %s samples, its mixture %d -- the sources of a mixture "
                            "must have the mixture's length" % (k, len(d[k]) if k in d else "no", len(d['mix'])))
     flat = np.concatenate([batch[i][k] for k in keys for i in order])
-    return {'pcm': {'flat': torch.from_numpy(flat), 'keys': keys, 'lens': [int(len(batch[i]['mix'])) for i in order]}}
+    pcm = {'flat': torch.from_numpy(flat), 'keys': keys, 'lens': [int(len(batch[i]['mix'])) for i in order]}
+    if rates is not None:      # 'lens' stay the sample counts on disk; sepkern.data resamples when a rate differs from the target
+      pcm['rate'] = [rates[i] for i in order]
+      pcm['target_rate'] = self.sample_rate
+    return {'pcm': pcm}
 
 
 class _PitFn(torch.autograd.Function):

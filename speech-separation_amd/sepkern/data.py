@@ -35,26 +35,48 @@ def npz_frames(path, key="mix"):
     return int(shape[1]) if len(shape) > 1 else int(shape[0])
 
 
-def wav_frames(path, hop=128):
-    """STFT frame count 1 + N // hop of a wav file, from its header."""
+def wav_frames(path, hop=128, sample_rate=None):
+    """STFT frame count 1 + N // hop of a wav file, from its header; with sample_rate, N is the file's length once resampled
+    to that rate (sepkern/resample.py's length rule)."""
     with wave.open(path, "rb") as w:
-        return 1 + w.getnframes() // hop
+        n = w.getnframes()
+        if sample_rate is not None and w.getframerate() != int(sample_rate):
+            from .resample import out_len
+            n = out_len(n, w.getframerate(), sample_rate)
+        return 1 + n // hop
+
+
+def _at_target_rate(pcm, flat):
+  """A WavCollator batch that carries 'rate' (per utterance) and 'target_rate' (WavTrainSet(sample_rate=...)) with an utterance
+  recorded at another rate: every signal of the batch resampled on the device (ops.pcm_to_rate: one sk_resample launch per
+  rate) -> (float32 flat in the same key-major layout, samples per utterance at the target rate).  A batch without those keys,
+  or wholly at the target rate, is returned as it came: (flat, pcm['lens']) -- the int16 path, untouched."""
+  from . import ops
+  ns = [int(n) for n in pcm['lens']]
+  rates, target = pcm.get('rate'), pcm.get('target_rate')
+  if rates is None or target is None or all(int(r) == int(target) for r in rates):
+    return flat, ns
+  nk = len(pcm['keys'])
+  out, outs = ops.pcm_to_rate(flat, ns * nk, [int(r) for r in rates] * nk, target)
+  return out, outs[:len(ns)]
 
 
 def features_from_pcm(pcm, dev):
   """The on-GPU feature front end of a wav batch.  pcm = the arch's WavCollator batch: {'flat': int16 tensor
   holding every signal of the batch, key-major ('mix', 'source1', ...), longest utterance first; 'keys'; 'lens': samples per
-  utterance} -> (mix (R,F), [source (R,F)...] packed rows, their Packing): STFT magnitudes by sk_stft into the (T,B,F) grid,
+  utterance; optionally 'rate' (Hz per utterance) and 'target_rate': signals at another rate are resampled on the device
+  first, sk_resample} -> (mix (R,F), [source (R,F)...] packed rows, their Packing): STFT magnitudes by sk_stft into the (T,B,F) grid,
   then the valid rows.  One H2D copy for the whole batch; everything is enqueued on the CURRENT stream."""
   import torch
   from . import ops
   from .packing import Packing
-  ns = [int(n) for n in pcm['lens']]
-  B, F = len(ns), 257
-  pk = Packing.from_lens([1 + n // 128 for n in ns], dev)
   flat = pcm['flat']
   if flat.device != torch.device(dev):
     flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
+  src = flat
+  flat, ns = _at_target_rate(pcm, flat)                # (another tensor only when a signal had to be resampled)
+  B, F = len(ns), 257
+  pk = Packing.from_lens([1 + n // 128 for n in ns], dev)
   feats, at, total = [], 0, sum(ns)
   for _ in pcm['keys']:
     out = torch.zeros(pk.T, B, F, device=dev)
@@ -62,7 +84,7 @@ def features_from_pcm(pcm, dev):
                    stride_t=[B * F] * B, stride_f=[1] * B)
     at += total
     feats.append(pk.pack(out))
-  flat.record_stream(torch.cuda.current_stream(dev))
+  src.record_stream(torch.cuda.current_stream(dev))
   return feats[0], feats[1:], pk
 
 
@@ -70,20 +92,23 @@ def wave_features_from_pcm(pcm, dev, source_mags=True):
   """features_from_pcm for a loss that works on waveforms (archs/uPIT.py, loss=sisdr): the same batch ->
   (mix (R,F), [source (R,F)...], Packing, wave), wave = {'mixc': the mixture's COMPLEX STFT as packed rows (Rp, F) complex64,
   'flat': the batch's int16 PCM on the device (key-major, as the collator laid it out), 'nsamp': samples per utterance,
-  'sig_offs': {key: [offset of utterance j's signal in flat]}}.  The magnitudes are the same sk_stft launches as
+  'sig_offs': {key: [offset of utterance j's signal in flat]}}.  A batch that carries 'rate' / 'target_rate' with a signal at
+  another rate is resampled on the device first (sk_resample): 'flat' and 'nsamp' are then the float32 signals and their
+  counts at the target rate, which is what the loss scores against.  The magnitudes are the same sk_stft launches as
   features_from_pcm's (bit-identical network input); source_mags=False skips the sources' (a waveform loss does not read
   them; the list is then empty)."""
   import torch
   from . import ops
   from .packing import Packing
-  ns = [int(n) for n in pcm['lens']]
+  flat = pcm['flat']
+  if flat.device != torch.device(dev):
+    flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
+  src = flat
+  flat, ns = _at_target_rate(pcm, flat)                # resampled: float32 signals and their counts from here on
   B, F = len(ns), 257
   pk = Packing.from_lens([1 + n // 128 for n in ns], dev)
   if pk.perm is not None:
     raise ValueError("wave_features_from_pcm: the batch must be sorted by frame count, longest first (WavCollator does)")
-  flat = pcm['flat']
-  if flat.device != torch.device(dev):
-    flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
   total = sum(ns)
   starts = [sum(ns[:j]) for j in range(B)]
   grid = dict(lengths=ns, out_offs=[b * F for b in range(B)], stride_t=[B * F] * B, stride_f=[1] * B)
@@ -95,6 +120,7 @@ def wave_features_from_pcm(pcm, dev, source_mags=True):
   outc = torch.zeros(pk.T, B, F, dtype=torch.complex64, device=dev)
   ops.stft_batch(flat[:total], want_complex=True, out=outc, **grid)
   mixc = torch.view_as_complex(pk.pack(torch.view_as_real(outc).view(pk.T, B, 2 * F)).view(-1, F, 2))
+  src.record_stream(torch.cuda.current_stream(dev))
   flat.record_stream(torch.cuda.current_stream(dev))
   wave = {'mixc': mixc, 'flat': flat, 'nsamp': ns,
           'sig_offs': {k: [q * total + st for st in starts] for q, k in enumerate(pcm['keys'])}}

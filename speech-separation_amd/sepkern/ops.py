@@ -333,6 +333,99 @@ def stft_batch(wavs, want_complex=False, layout="TF", out=None, out_offs=None, s
     return ret if ret is not None else out
 
 
+def resample_into(src, in_offs, n_in, out, out_offs, n_out, sr_in, sr_out, repeat=1):
+    """sk_resample on signals described by offsets: signal u = n_in[u] samples at src[in_offs[u]] (1-D CUDA tensor, float32 or
+    int16 PCM scaled by 1/32768 in-kernel) at sr_in Hz -> its n_out[u] float32 samples at sr_out Hz at out[out_offs[u]]
+    (sepkern/resample.py defines the arithmetic and holds the tap table).  Nothing else of `out` is written.  Any number of
+    signals: the kernel takes 65535 per launch, more go in as many launches."""
+    from . import resample as rs
+    pcm16 = src.dtype == torch.int16
+    _chk(src, torch.int16 if pcm16 else torch.float32)
+    _chk(out)
+    in_offs, n_in, out_offs, n_out = ([int(v) for v in a] for a in (in_offs, n_in, out_offs, n_out))
+    nsig = len(n_in)
+    if src.dim() != 1 or out.dim() != 1 or not src.is_contiguous() or not out.is_contiguous():
+        raise _lib.SepkernError("resample: source and destination must be contiguous 1-D tensors")
+    if nsig == 0 or not (len(in_offs) == len(out_offs) == len(n_out) == nsig):
+        raise _lib.SepkernError("resample: one offset and one length per signal, in and out")
+    if any(o < 0 or n < 0 or o + n > src.numel() for o, n in zip(in_offs, n_in)) or \
+            any(o < 0 or n < 0 or o + n > out.numel() for o, n in zip(out_offs, n_out)):
+        raise _lib.SepkernError("resample: a signal runs past its buffer")
+    if max(n_out) == 0:
+        return out
+    pl = rs.plan(sr_in, sr_out)
+    taps = pl.device_taps(src.device)
+    dev = src.device
+    # descriptor arrays must outlive the (asynchronous) launch call: keep references until it returns
+    d_offs = _i64(in_offs + out_offs, dev)
+    d_ns = torch.tensor(n_in + n_out, dtype=torch.int32, device=dev)
+    # algorithmic bytes: every input sample once, every output sample once
+    with _timed("resample_kernel", repeat * float(sum(n_in) * (2 if pcm16 else 4) + sum(n_out) * 4)):
+        for _ in range(repeat):
+            for a in range(0, nsig, 65535):          # sk_resample takes at most 65535 signals (the grid's y): one launch per chunk
+                b = min(nsig, a + 65535)
+                _lib.call("sk_resample", _ptr(src), int(pcm16), _ptr(d_offs[a:b]), _ptr(d_ns[a:b]), b - a, _ptr(taps), pl.L, pl.M,
+                          pl.ntaps, _ptr(out), _ptr(d_offs[nsig + a:nsig + b]), _ptr(d_ns[nsig + a:nsig + b]), max(n_out[a:b]),
+                          _stream())
+    return out
+
+
+def resample_batch(flat, lengths, sr_in, sr_out, repeat=1):
+    """Resample a ragged batch: flat = ONE 1-D CUDA tensor holding the signals back to back (float32, or int16 PCM), lengths =
+    samples per signal, all at sr_in Hz -> (out_flat float32: the signals at sr_out Hz back to back, out_lengths);
+    out_lengths[u] = ceil(lengths[u] sr_out / sr_in).  Enqueued on the current stream."""
+    from . import resample as rs
+    ns = [int(n) for n in lengths]
+    if flat.dim() != 1 or sum(ns) != flat.numel():
+        raise _lib.SepkernError("resample_batch needs one 1-D tensor and lengths that add up to it")
+    outs = [rs.out_len(n, sr_in, sr_out) for n in ns]
+    in_offs, out_offs, ai, ao = [], [], 0, 0
+    for n, m in zip(ns, outs):
+        in_offs.append(ai)
+        out_offs.append(ao)
+        ai += n
+        ao += m
+    out = torch.empty(ao, dtype=torch.float32, device=flat.device)
+    resample_into(flat.contiguous(), in_offs, ns, out, out_offs, outs, sr_in, sr_out, repeat=repeat)
+    return out, outs
+
+
+def pcm_to_rate(flat, lengths, rates, target):
+    """A batch of int16 PCM signals recorded at DIFFERENT rates -> float32 at `target` Hz: flat = the signals back to back on
+    the device, lengths / rates per signal.  Signals are resampled grouped by rate (one sk_resample launch per rate); a signal
+    already at `target` is only scaled by 1/32768 (exact: what sk_stft's pcm16 path does to it).
+    Returns (out_flat float32, out_lengths)."""
+    from . import resample as rs
+    _chk(flat, torch.int16)
+    ns, rates, target = [int(n) for n in lengths], [int(r) for r in rates], int(target)
+    if flat.dim() != 1 or sum(ns) != flat.numel() or len(rates) != len(ns):
+        raise _lib.SepkernError("pcm_to_rate needs one 1-D tensor, lengths that add up to it and one rate per signal")
+    outs = [rs.out_len(n, r, target) if r != target else n for n, r in zip(ns, rates)]
+    in_offs, out_offs, ai, ao = [], [], 0, 0
+    for n, m in zip(ns, outs):
+        in_offs.append(ai)
+        out_offs.append(ao)
+        ai += n
+        ao += m
+    out = torch.empty(ao, dtype=torch.float32, device=flat.device)
+    for r in sorted(set(rates)):
+        idx = [u for u, ru in enumerate(rates) if ru == r]
+        if r != target:
+            resample_into(flat, [in_offs[u] for u in idx], [ns[u] for u in idx], out, [out_offs[u] for u in idx],
+                          [outs[u] for u in idx], r, target)
+            continue
+        k = 0
+        while k < len(idx):                  # runs of neighbouring signals are converted in one go
+            e = k
+            while e + 1 < len(idx) and idx[e + 1] == idx[e] + 1:
+                e += 1
+            n = sum(ns[u] for u in idx[k:e + 1])
+            a, b = in_offs[idx[k]], out_offs[idx[k]]
+            torch.mul(flat[a:a + n], 1.0 / 32768.0, out=out[b:b + n])
+            k = e + 1
+    return out, outs
+
+
 def mask_istft_flat(mixcat, maskcat, Ts, S, want_pcm=True, want_float=True, repeat=1):
     """Mask-apply + iSTFT on buffers that crossed PCIe as ONE copy each: mixcat = the utterances' (257, T_u) complex64
     spectra back to back (flattened), maskcat = None or, per utterance and source (utterance-major), the (257, T_u) float32

@@ -41,18 +41,19 @@ def utterance(utt, n_samples, num_spk=2):
     return uid, to16(mix), [to16(s) for s in srcs]
 
 
-def write_wav_tree(root, n_utts, num_spk=2, min_s=3.0, max_s=8.0, fixed_samples=None, seed=0, id_list=None):
-    """Writes <root>/{mix,s1..}/<id>.wav and returns the list of ids (also to `id_list` if given)."""
+def write_wav_tree(root, n_utts, num_spk=2, min_s=3.0, max_s=8.0, fixed_samples=None, seed=0, id_list=None, rate=SR):
+    """Writes <root>/{mix,s1..}/<id>.wav and returns the list of ids (also to `id_list` if given).  rate: the sample rate of
+    the files (a wav16k tree: rate=16000; durations min_s .. max_s are seconds at that rate)."""
     rng = np.random.default_rng(seed)
     for d in ["mix"] + ["s%d" % (s + 1) for s in range(num_spk)]:
         os.makedirs(os.path.join(root, d), exist_ok=True)
     ids = []
     for u in range(n_utts):
-        n = int(fixed_samples) if fixed_samples else int(rng.uniform(min_s, max_s) * SR)
+        n = int(fixed_samples) if fixed_samples else int(rng.uniform(min_s, max_s) * rate)
         uid, mix, srcs = utterance(u, n, num_spk)
-        scipy.io.wavfile.write(os.path.join(root, "mix", uid + ".wav"), SR, mix)
+        scipy.io.wavfile.write(os.path.join(root, "mix", uid + ".wav"), rate, mix)
         for s, w in enumerate(srcs):
-            scipy.io.wavfile.write(os.path.join(root, "s%d" % (s + 1), uid + ".wav"), SR, w)
+            scipy.io.wavfile.write(os.path.join(root, "s%d" % (s + 1), uid + ".wav"), rate, w)
         ids.append(uid)
     if id_list:
         os.makedirs(os.path.dirname(os.path.abspath(id_list)), exist_ok=True)

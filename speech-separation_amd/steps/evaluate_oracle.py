@@ -2,7 +2,8 @@
 """Oracle-mask upper bound: counterpart of the reference's steps/evaluate_oracle.py (non-segment branch,
 steps/evaluate_oracle.py:120-145; its segments branch does not run: `use_seg`/`rage`/`oracle_mask` NameErrors).
 
-For every utterance of <data-dir>/wav.scp: STFT of the mixture and of each source on the GPU (sk_stft), the
+For every utterance of <data-dir>/wav.scp (wav files at another rate than --sample-rate are first resampled to it on the GPU,
+sk_resample, as the reference's librosa.load(sr=) does): STFT of the mixture and of each source on the GPU (sk_stft), the
 ideal ratio mask |S_i| / |M| (or the binary mask with --hard-mask), mask-apply + iSTFT on the GPU
 (sk_mask_istft), then the score: BSS Eval SDR / SIR / SAR without permutation search (the reference calls
 mir_eval's bss_eval_sources with compute_permutation=False, steps/evaluate_oracle.py:118,143; here
@@ -47,7 +48,12 @@ def main(argv=None):
   dir_out = args.data_dir + ("/oracle_hard_mask_eval/" if args.hard_mask else "/oracle_soft_mask_eval/")
   os.makedirs(dir_out, exist_ok=True)
   out = {m: MetricFiles(dir_out, m) for m in ("SDR", "SIR", "SAR", "SISDR")}
-  pending = []                                    # --gpu: (id, device fp32 estimates, device int16 references)
+  pending = []                                    # --gpu: (id, device fp32 estimates, device references: int16 PCM, or float32 once resampled)
+
+  def host_ref(t):
+    """A device reference as fp64 on the host: int16 PCM scaled by 1/32768, resampled float32 as it is."""
+    x = t.cpu().numpy().astype(np.float64)
+    return x / 32768.0 if t.dtype == torch.int16 else x
 
   def write(reco_id, ests, refs, sdr, sir, sar):
     out["SDR"].add(reco_id, sdr)
@@ -60,24 +66,31 @@ def main(argv=None):
       return
     from sepkern.bsseval_gpu import bss_eval_sources_batch
     ests = [torch.stack(e) for _, e, _ in pending]                       # fp32, resident on the device
-    refs = [torch.stack([p[:e.shape[1]] for p in r]) for (_, _, r), e in zip(pending, ests)]   # int16 PCM
+    refs = [torch.stack([p[:e.shape[1]] for p in r]) for (_, _, r), e in zip(pending, ests)]   # int16 PCM (float32 once resampled)
     scores = bss_eval_sources_batch(refs, ests, compute_permutation=False)
     if scores.n_fallback:
       print("evaluate_oracle.py: %d utterance(s) re-scored on the host" % scores.n_fallback, file=sys.stderr)
     for (reco_id, _, _), e, r, (sdr, sir, sar, _) in zip(pending, ests, refs, scores):
-      write(reco_id, e.cpu().numpy().astype(np.float64), r.cpu().numpy().astype(np.float64) / 32768.0, sdr, sir, sar)
+      write(reco_id, e.cpu().numpy().astype(np.float64), host_ref(r), sdr, sir, sar)
     pending.clear()
 
   with open(args.data_dir + "/wav.scp", 'r') as listF:
     for line in listF:
       reco_id, filename = line.rstrip().split(' ')
       wav_files = sorted(glob.glob(filename.replace("/mix/", "/*/")))
-      pcm = []
+      pcm, rates = [], []
       for f in wav_files:
         fs, x = scipy.io.wavfile.read(f)
-        if fs != args.sample_rate or x.dtype != np.int16:
-          raise ValueError("%s: expected %d Hz 16-bit PCM" % (f, args.sample_rate))
+        if x.dtype != np.int16 or x.ndim != 1:
+          raise ValueError("%s: expected mono 16-bit PCM" % f)
         pcm.append(torch.from_numpy(np.ascontiguousarray(x)).cuda())
+        rates.append(int(fs))
+      if any(fs != args.sample_rate for fs in rates):
+        # librosa.load(f, sr=args.sample_rate) (reference steps/evaluate_oracle.py:96,122): mixture and sources resampled on the
+        # device (sk_resample); float32 signals from here on -- the resampled references are what the scores are taken against
+        ns = [int(p.numel()) for p in pcm]
+        flat, outs = ops.pcm_to_rate(torch.cat(pcm), ns, rates, args.sample_rate)
+        pcm = list(torch.split(flat, outs))
       num_src = len(pcm) - 1
       mix_spec = ops.stft_batch([pcm[0]], want_complex=True, layout="FT")[0]           # (257, T) complex64
       mags = torch.stack(ops.stft_batch(pcm[1:], want_complex=False, layout="FT"))      # (S, 257, T)
@@ -92,7 +105,7 @@ def main(argv=None):
           flush()
         continue
       ests = np.stack([wav[0][i].cpu().numpy().astype(np.float64) for i in range(num_src)])
-      refs = np.stack([pcm[i + 1].cpu().numpy().astype(np.float64)[:ests.shape[1]] / 32768.0 for i in range(num_src)])
+      refs = np.stack([host_ref(pcm[i + 1])[:ests.shape[1]] for i in range(num_src)])
       sdr, sir, sar, _ = bss_eval_sources(refs, ests, compute_permutation=False)
       write(reco_id, ests, refs, sdr, sir, sar)
   flush()

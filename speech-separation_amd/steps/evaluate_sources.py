@@ -10,7 +10,8 @@ steps/evaluate_sources.py (:36-110), so that run_eval.sh:88-93 finds results/SDR
       additionally: scale-invariant SDR (Le Roux et al. 2019) under its best permutation and its improvement over
       the unprocessed mixture -- the metric BASELINE.json's +-0.1 dB parity gate names.  Never mixed into the
       SDR files.
-Off the hot path: numpy on the host.
+Off the hot path: numpy on the host.  Reference and mixture wavs at another rate than the estimates' (--sample-rate) are
+resampled to it first, on the GPU (sk_resample) -- the estimates were made from resampled mixtures.
 """
 import argparse
 import itertools
@@ -33,6 +34,9 @@ def get_args(argv=None):
   parser.add_argument("--gpu", action='store_true', default=False,
                       help="Score BSS Eval in batches on the GPU (sepkern/bsseval_gpu.py); SI-SDR stays on the host")
   parser.add_argument("--batch", type=int, default=256, help="Utterances per GPU batch (with --gpu)")
+  parser.add_argument("--sample-rate", type=int, default=None,
+                      help="Rate the estimates were written at (default: read from the first estimate's header); reference "
+                           "and mixture wavs at another rate are resampled to it on the GPU before scoring (sk_resample)")
   return parser.parse_args(argv)
 
 
@@ -42,9 +46,24 @@ def read_pairs(path):
     return [tuple(line.rstrip('\n').split(' ')[:2]) for line in f if line.strip()]
 
 
-def load_wav(path):
+def load_wav(path, sample_rate=None):
+  """A 16-bit wav as fp64 in [-1, 1).  With sample_rate, a file at another rate is resampled to it (on the GPU, sk_resample:
+  the references the network was trained and run against, steps/extract_feats.py); the others are read as they always were."""
   fs, x = scipy.io.wavfile.read(path)
+  if sample_rate is not None and fs != sample_rate:
+    import torch
+    from sepkern import ops
+    if x.dtype != np.int16 or x.ndim != 1:
+      raise ValueError("%s: only mono 16-bit PCM wav can be resampled" % path)
+    y, _ = ops.resample_batch(torch.from_numpy(np.ascontiguousarray(x)).cuda(), [len(x)], fs, sample_rate)
+    return y.cpu().numpy().astype(np.float64)
   return x.astype(np.float64) / 32768.0
+
+
+def wav_rate(path):
+  import wave
+  with wave.open(path, "rb") as w:
+    return w.getframerate()
 
 
 class MetricFiles:
@@ -91,12 +110,17 @@ def main(argv=None):
   results = args.exp_dir + "/results"
   os.makedirs(results, exist_ok=True)
   out = {m: MetricFiles(results, m) for m in ("SDR", "SIR", "SAR", "SISDR", "SISDRi")}
+  rate = [args.sample_rate]                       # the estimates' rate: references and mixtures are brought to it
+
   def load(utt_id, mix_wav):
     S = num_src[utt_id]
-    ests = [load_wav(args.exp_dir + "/wav/s" + str(s + 1) + "/" + utt_id + ".wav") for s in range(S)]
+    est_files = [args.exp_dir + "/wav/s" + str(s + 1) + "/" + utt_id + ".wav" for s in range(S)]
+    if rate[0] is None:
+      rate[0] = wav_rate(est_files[0])
+    ests = [load_wav(f) for f in est_files]
     n = len(ests[0])                              # the first estimate sets the length (steps/evaluate_sources.py:51-55)
     ests = np.stack([e[:n] for e in ests])
-    refs = np.stack([load_wav(mix_wav.replace("/mix/", "/s" + str(s + 1) + "/"))[:n] for s in range(S)])
+    refs = np.stack([load_wav(mix_wav.replace("/mix/", "/s" + str(s + 1) + "/"), rate[0])[:n] for s in range(S)])
     return refs, ests, n
 
   def write(utt_id, mix_wav, refs, ests, n, sdr, sir, sar):
@@ -104,7 +128,7 @@ def main(argv=None):
     out["SIR"].add(utt_id, sir)
     out["SAR"].add(utt_id, sar)
     si = best_si_sdr(ests, refs)
-    mix = load_wav(mix_wav)[:n]
+    mix = load_wav(mix_wav, rate[0])[:n]
     out["SISDR"].add(utt_id, si)
     out["SISDRi"].add(utt_id, [v - si_sdr(mix, refs[s]) for s, v in enumerate(si)])
 

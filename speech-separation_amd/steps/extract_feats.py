@@ -10,8 +10,10 @@
 The reference calls librosa.load + librosa.stft per file on the CPU (steps/extract_feats.py:85-89,
 104-105); here wav files are read as int16 PCM, batched, and transformed by sk_stft (PCM scaling,
 reflect padding, periodic Hann, 512-point FFT and magnitude fused in one kernel) writing directly in
-the on-disk (257, T) layout.  Only 16-bit PCM at the requested sample rate is supported (the
-reference's data is wav8k); other inputs raise instead of being silently resampled.
+the on-disk (257, T) layout.  Only mono 16-bit PCM is supported.  A file at another rate than
+--sample-rate is resampled to it on the GPU in front of the STFT (sk_resample: the band-limited sinc
+interpolation librosa.load(sr=) delegates to resampy, sepkern/resample.py); files already at
+--sample-rate (the reference's data is wav8k) go to the STFT as int16, untouched.
 
 The stage is host-bound (the kernel transforms ~2 G frames/s; zlib compresses ~25 MB/s per core), so the host side is
 organised around that: a chunk's wav files are read by a thread pool while the previous chunk is on the GPU, every
@@ -47,18 +49,17 @@ def get_args():
   return parser.parse_args()
 
 
-def read_pcm(path, sr, offset=None, duration=None):
+def read_pcm(path, offset=None, duration=None):
+  """-> (int16 samples at the file's own rate, that rate)."""
   fs, x = scipy.io.wavfile.read(path)
-  if fs != sr:
-    raise ValueError("%s is sampled at %d Hz, expected %d (resampling is not built)" % (path, fs, sr))
   if x.dtype != np.int16:
     raise ValueError("%s: only 16-bit PCM wav is supported, got %s" % (path, x.dtype))
   if x.ndim > 1:
     raise ValueError("%s: only mono wav is supported" % path)
-  if offset is not None:       # librosa.load(offset=, duration=): whole frames from int(offset*sr)
-    start = int(offset * sr)
-    x = x[start:start + int(duration * sr)]
-  return np.ascontiguousarray(x)
+  if offset is not None:       # librosa.load(offset=, duration=): whole frames from int(offset*sr), cut at the file's rate
+    start = int(offset * fs)
+    x = x[start:start + int(duration * fs)]
+  return np.ascontiguousarray(x), int(fs)
 
 
 def main():
@@ -108,7 +109,7 @@ def main():
   F = 257
 
   def read_chunk(chunk):
-    return [[read_pcm(f, args.sample_rate, t0, dur) for _, f, t0, dur in items] for _, items, _ in chunk]
+    return [[read_pcm(f, t0, dur) for _, f, t0, dur in items] for _, items, _ in chunk]
 
   def write_npz(seg_id, file_dict):
     np.savez_compressed(os.path.join(args.feat_dir, seg_id), **file_dict)
@@ -129,10 +130,14 @@ def main():
           pcms.extend(arrs)
       order = {e[0]: n for n, e in enumerate(chunk)}
       entries.sort(key=lambda e: order[e[0]])          # the scp lines keep the order of wav.scp
+      rates = [fs for _, fs in pcms]
+      pcms = [x for x, _ in pcms]
       ns = [len(x) for x in pcms]
-      Ts = [1 + n // 128 for n in ns]
       host_in = torch.from_numpy(np.concatenate(pcms)).pin_memory()
       dev_in = host_in.to("cuda", non_blocking=True)                       # the chunk's samples: one copy
+      if any(fs != args.sample_rate for fs in rates):                      # resampled on the device, grouped by rate; float32 from here
+        dev_in, ns = ops.pcm_to_rate(dev_in, ns, rates, args.sample_rate)
+      Ts = [1 + n // 128 for n in ns]                                      # (frame counts of the signals the STFT sees)
       out_offs, acc = [], 0
       for T in Ts:
         out_offs.append(acc)

@@ -67,6 +67,9 @@ def get_args(argv=None):
   parser.add_argument("--wav-input", action="store_true",
                       help="read <data-dir>/wav.scp and compute the STFT features on the GPU inside the step "
                            "(arch must provide WavTrainSet) instead of loading feats_train.scp npz files")
+  parser.add_argument("--sample-rate", type=int, default=None,
+                      help="with --wav-input: the rate the network works at; wav files at another rate are resampled to it on "
+                           "the GPU (sk_resample), as the reference's librosa.load(sr=) does.  Default: the files are taken as they are")
   parser.add_argument("--seed", type=int, default=None, help="seed for weights, shuffling and h0/c0")
   return parser.parse_args(argv)
 
@@ -145,11 +148,18 @@ def waveform_loss(m, args):
 
 
 # ----------------------------------------------------------------------------------------------- data
+def wav_train_set(m, args, data_dir):
+  """The arch's WavTrainSet over data_dir; --sample-rate is handed on only when given (an arch without the argument keeps working)."""
+  if getattr(args, "sample_rate", None) is None:
+    return m.WavTrainSet(data_dir)
+  return m.WavTrainSet(data_dir, sample_rate=args.sample_rate)
+
+
 def training_batches(m, args, rank, world):
   """DataLoader over this rank's share of the training set, and the sampler to re-seed per epoch (or None).
   One process: the reference's shuffled loader (steps/train_qsub.py:80-81).  Several: EpochShards."""
   from sepkern import dist as skdist
-  dataset = m.WavTrainSet(args.data_dir) if args.wav_input else m.TrainSet(args.data_dir, args.train_copy_location)
+  dataset = wav_train_set(m, args, args.data_dir) if args.wav_input else m.TrainSet(args.data_dir, args.train_copy_location)
   seed = args.seed if args.seed is not None else 0
   workers = loader_workers(args, world)
   extra = dict(persistent_workers=True, prefetch_factor=2) if workers > 0 else {}      # workers live across epochs
@@ -189,7 +199,7 @@ def validation_batches(m, args, rank, world):
   from sepkern import dist as skdist
   if not args.cv_data_dir:
     return None
-  dataset = m.WavTrainSet(args.cv_data_dir) if args.wav_input else m.TrainSet(args.cv_data_dir)
+  dataset = wav_train_set(m, args, args.cv_data_dir) if args.wav_input else m.TrainSet(args.cv_data_dir)
   part = dataset if world == 1 else Subset(dataset, skdist.shard_indices_contiguous(len(dataset), rank, world))
   if len(part) == 0:
     return []                                    # more ranks than utterances: this rank only joins the final sum
