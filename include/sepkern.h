@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 135
+#define SK_VERSION 136
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -492,6 +492,27 @@ int sk_sisdr_mask_grad(const float* est, const int64_t* est_offs, const void* re
                        const int32_t* nframes, const int32_t* best_perm, const float* coef, const float* gscale,
                        const void* mix_rows_c64, const int32_t* offs, int B, int S, int n_fft, int hop, int max_frames,
                        float* dmask, int ld, sk_stream_t stream);
+
+/* ---------------------------------------------------------------- phase-sensitive uPIT targets (loss=psa / tpsa)
+ * The targets of the phase-sensitive approximation loss (sepkern/psa.py states the definition and restates it in numpy fp64),
+ * made from the batch's waveforms in ONE launch: with Y the mixture's STFT and S_s source s's, both as sk_stft defines them,
+ *   mix_rows[row][f]            = |Y[t][f]|                               (the bits sk_stft's magnitude output has)
+ *   targets[s*plane + row*ld+f] = (Re S_s Re Y + Im S_s Im Y) / |Y|  = |S_s| cos(theta_s - theta_Y),
+ * 0 where the fp32 |Y|^2 < 2^-100; clamp != 0 holds the target to [0, |Y|] (the truncated form).  The PIT-MSE kernels above
+ * take these rows in place of the source magnitudes.  The sources' spectra never exist in memory; the mixture's passes through
+ * ws (below) on its way from the lane that formed a bin to the same lane's S contractions.
+ * Signal q (0 = mixture, 1 + s = source s) of utterance u: nsamp[u] samples at wav + sig_offs[q*B + u] (elements; float32, or
+ * int16 PCM scaled by 1/32768 when pcm16 != 0), T_u = 1 + nsamp[u]/hop frames.  Row of frame t of utterance u:
+ *   offs != NULL:     offs[t] + u        (packed rows of a length-sorted batch, row_base NULL)
+ *   row_base != NULL: row_base[u] + t    (per-utterance blocks of (T_u, ld), offs NULL)
+ * Rows are ld >= 257 floats with unit bin stride; mix_rows and every target plane share ld.  Only the rows of existing frames
+ * and columns < 257 are written, each element by one lane in a fixed order: bitwise reproducible, and an utterance's numbers
+ * do not depend on the batch around it.  ws: work rows, 257 * 8 bytes for every row the launch addresses (rows 0 .. R-1 of the
+ * packed batch, or 0 .. sum_u T_u - 1), contents undefined afterwards.  min_samples <= min_u nsamp[u] must exceed n_fft/2 (reflect padding), max_frames >=
+ * max_u T_u sizes the grid; n_fft = 512, hop = 128 only; 1 <= S <= 4; B <= 65535. */
+int sk_stft_psa(const void* wav, int pcm16, const int64_t* sig_offs, const int32_t* nsamp, int B, int S, int n_fft, int hop,
+                int clamp, const int32_t* offs, const int64_t* row_base, float* mix_rows, float* targets, int ld, int64_t plane,
+                void* ws, int min_samples, int max_frames, sk_stream_t stream);
 
 /* ---------------------------------------------------------------- RSH arch (reference archs/RSH.py)
  * One pass of the greedy source-assignment loss (archs/RSH.py:225-244): mask (T,B,F); x (T,B,ldx) whose

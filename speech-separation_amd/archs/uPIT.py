@@ -25,6 +25,10 @@ Beyond the reference (all optional, defaults reproduce it):
     SI-SDR of the time-domain estimates istft(mask_s * STFT(mix)) against the source waveforms (include/sepkern.h
     "SI-SDR uPIT loss").  It needs waveforms: WavTrainSet batches (steps/train_qsub.py --wav-input).  compute_loss then
     returns (mean negative SI-SDR per utterance in dB, number of utterances).
+    'psa' / 'tpsa': the phase-sensitive approximation of the uPIT paper (sepkern/psa.py): the PIT-MSE above with the targets
+    |S_s| cos(theta_s - theta_mix) in place of |S_s| ('tpsa': held to [0, |mix|]), made from the waveforms by one kernel
+    (sk_stft_psa).  It needs waveforms too -- or npz features written by steps/extract_feats.py --psa-targets, which train
+    with the default loss=mse.  compute_loss returns what it returns for 'mse'.
 """
 import itertools
 import os
@@ -48,6 +52,7 @@ except ImportError:  # the frozen copy exp/<...>/arch.py is imported from anothe
 from sepkern import dist as skdist
 from sepkern import ops
 from sepkern.data import features_from_pcm as _features_from_pcm, wave_features_from_pcm as _wave_features_from_pcm
+from sepkern.data import psa_features_from_pcm as _psa_features_from_pcm
 from sepkern.collate import collate_sorted, eval_magnitudes, read_scp, stage_copies, train_sample
 from sepkern.model import SepDNNBase, UnpackFn, to_packed as _to_packed
 from sepkern.packing import Packing
@@ -214,11 +219,12 @@ class _PitFn(torch.autograd.Function):
     return (dmask, None, None, None) + (None,) * len(srcs)
 
 
-LOSSES = ('mse', 'sisdr')
+LOSSES = ('mse', 'sisdr', 'psa', 'tpsa')
+PSA_LOSSES = ('psa', 'tpsa')       # PIT-MSE on phase-sensitive targets (sepkern/psa.py); 'tpsa' holds them to [0, |mix|]
 
 
 def parse_loss(value):
-  """The conf key `loss`: 'mse' (default) or 'sisdr'."""
+  """The conf key `loss`: 'mse' (default), 'sisdr', 'psa' or 'tpsa'."""
   value = str(value).strip().lower()
   if value not in LOSSES:
     raise ValueError("conf key loss: %r is not one of %s" % (value, " / ".join(repr(v) for v in LOSSES)))
@@ -226,6 +232,11 @@ def parse_loss(value):
 
 
 NEEDS_WAVEFORMS = "`loss=sisdr` needs waveforms: train with `--wav-input`"
+
+
+def needs_waveforms(kind):
+  """NEEDS_WAVEFORMS for another loss that is made from the waveforms."""
+  return NEEDS_WAVEFORMS.replace("loss=sisdr", "loss=" + kind)
 
 
 class _SisdrFn(torch.autograd.Function):
@@ -379,7 +390,20 @@ def compute_loss_padded(model, mix, sources, lens, plotdir=""):
 
 def compute_loss(model, epoch, batch_sample, plotdir=""):
   dev = model.lin.weight.device
-  if getattr(model, 'loss_kind', 'mse') == 'sisdr':
+  kind = getattr(model, 'loss_kind', 'mse')
+  if kind in PSA_LOSSES:
+    if 'pcm' in batch_sample:
+      mix, targets, pk = _psa_features_from_pcm(batch_sample['pcm'], dev, clamp=kind == 'tpsa')
+    elif 'packed' in batch_sample and 'targets' in batch_sample:  # staged by Prefetcher(targets=kind): the targets are in place
+      if batch_sample['targets'] != kind:
+        raise ValueError("loss=%s: the batch was staged with %r targets" % (kind, batch_sample['targets']))
+      mix, targets, pk = batch_sample['packed']
+    else:                                                         # npz feature batches hold magnitudes only
+      raise ValueError(needs_waveforms(kind))
+    if len(targets) < model.num_spk:
+      raise ValueError("loss=%s: the batch holds %d source waveforms (num_spk = %d)" % (kind, len(targets), model.num_spk))
+    return compute_loss_packed(model, mix, targets[:model.num_spk], pk, plotdir)
+  if kind == 'sisdr':
     if 'pcm' in batch_sample:
       mix, _, pk, wave = _wave_features_from_pcm(batch_sample['pcm'], dev, source_mags=False)
     elif 'packed' in batch_sample and 'wave' in batch_sample:     # staged by Prefetcher(keep_wave=True)

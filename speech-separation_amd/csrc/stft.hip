@@ -737,7 +737,197 @@ __global__ __launch_bounds__(256, 4) void sisdr_grad_kernel(const float* __restr
   }
 }
 
+// ---- phase-sensitive targets (include/sepkern.h, sk_stft_psa; the definition is sepkern/psa.py's).
+// stft_kernel<frame-major> with a loop over the S + 1 signals of a tile and another epilogue: the mixture (q = 0) leaves
+// |Y| in its row and its 257 complex bins in the work rows; every source bin is contracted on its way out with the mixture's,
+//   target = (Re S Re Y + Im S Im Y) / |Y|   (0 where |Y|^2 < 2^-100; with clamp, held to [0, |Y|]),
+// and stored from registers at row offs[t] + u (packed) or row_base[u] + t.  A lane reads back exactly the bins it wrote itself
+// (lane j of a frame's group: Y[j + 16 k2] and the mirrors Y[256 - j - 16 k2], k2 < 8, lane 0 also Y[128]) a few microseconds
+// later: they come from L2.  Holding them in registers instead -- 17 complex values, 34 VGPRs on top of stft_kernel's 108 at
+// four workgroups per CU -- compiled to 128 VGPRs with 8 of them spilled to scratch.  The next signal's
+// samples of the same tile (or the next tile's mixture) travel while the current one is transformed.  Vector stores only.
+__device__ __forceinline__ void pin(v2f& x) {  // the bin is final here: what is done with it must not reach back into how it is rounded
+  asm volatile("" : "+v"(x.x), "+v"(x.y));
+}
+
+__global__ __launch_bounds__(256, 4) void stft_psa_kernel(const void* __restrict__ wav, int pcm16, const int64_t* __restrict__ sig_offs,
+                                                          const int32_t* __restrict__ nsamp, int B, int S, int clamp,
+                                                          const int32_t* __restrict__ offs, const int64_t* __restrict__ row_base,
+                                                          float* mix_rows, float* __restrict__ targets, int ld,
+                                                          int64_t plane, float2* ywork) {
+  __shared__ __attribute__((aligned(16))) float smp[NFFT + (FPB - 1) * HOP];
+  __shared__ __attribute__((aligned(16))) float win[NFFT];
+  __shared__ float2 tw[NFFT];
+  __shared__ float2 t256[256];
+  __shared__ float xch[16][16 * XLD];
+
+  const int u = blockIdx.y;
+  const int N = nsamp[u];
+  const int T = 1 + N / HOP;
+  const int tile0 = blockIdx.x * TPB;
+  if (tile0 * FPB >= T) return;
+  const int tend = min(T, (tile0 + TPB) * FPB);  // this block's frames: [tile0 * FPB, tend)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  constexpr int SPAN = NFFT + (FPB - 1) * HOP, SPT = (SPAN + 255) / 256;
+
+  // stft_kernel's sample loader, the signal q of the utterance chosen per call
+  auto fetch = [&](int t0, int q, float (&r)[SPT]) {
+    const int64_t woff = sig_offs[(int64_t)q * B + u];
+    const int nfr = min(FPB, T - t0);
+    const int span = NFFT + (nfr - 1) * HOP;
+    const int first = t0 * HOP - NFFT / 2;
+    if (first >= 0 && first + SPAN <= N) {
+      if (pcm16) {
+        const int16_t* w = (const int16_t*)wav + woff + first;
+#pragma unroll
+        for (int i2 = 0; i2 < SPT; ++i2) {
+          const int i = tid + 256 * i2;
+          r[i2] = (i < SPAN) ? (float)w[i] * (1.0f / 32768.0f) : 0.f;
+        }
+      } else {
+        const float* w = (const float*)wav + woff + first;
+#pragma unroll
+        for (int i2 = 0; i2 < SPT; ++i2) {
+          const int i = tid + 256 * i2;
+          r[i2] = (i < SPAN) ? w[i] : 0.f;
+        }
+      }
+      return;
+    }
+#pragma unroll
+    for (int i2 = 0; i2 < SPT; ++i2) {
+      const int i = tid + 256 * i2;
+      int src = first + i;
+      if (src < 0) src = -src;
+      if (src >= N) src = 2 * (N - 1) - src;
+      src = max(0, min(src, N - 1));
+      float v = pcm16 ? (float)((const int16_t*)wav)[woff + src] * (1.0f / 32768.0f) : ((const float*)wav)[woff + src];
+      r[i2] = (i < span) ? v : 0.f;
+    }
+  };
+  auto stash = [&](const float (&r)[SPT]) {
+#pragma unroll
+    for (int i2 = 0; i2 < SPT; ++i2) {
+      const int i = tid + 256 * i2;
+      if (i < SPAN) smp[i] = r[i2];
+    }
+  };
+
+  for (int i = tid; i < NFFT; i += 256) {
+    tw[i] = g_tw512[i];
+    win[i] = g_hann512[i];
+  }
+  t256[tid] = g_tw512[(2 * (tid & 15) * (tid >> 4)) & 511];
+  float pre[SPT];
+  fetch(tile0 * FPB, 0, pre);
+  stash(pre);
+  __syncthreads();
+
+  const int j = lane & 15, g = lane >> 4;
+  const int fr = 4 * wave + g;
+  const int partner = (lane & 48) | ((16 - j) & 15);
+  // a source's bin s against the mixture's y: one fused product-sum, the reciprocal square root, one multiply.  The upper end
+  // of the truncated form is the |Y| this lane STORED at q == 0, read back (mag): the stored bits, whichever way the compiler
+  // contracts a second y.x * y.x + y.y * y.y.
+  auto target = [&](v2f s, v2f y, const float* mag) {
+    const float y2 = y.x * y.x + y.y * y.y;
+    float v = (s.x * y.x + s.y * y.y) * __builtin_amdgcn_rsqf(y2);
+    if (!(y2 >= 0x1p-100f)) v = 0.f;
+    if (clamp) v = fminf(fmaxf(v, 0.f), *mag);
+    return v;
+  };
+
+  int t0 = tile0 * FPB, q = 0;
+  while (true) {  // (t0, q) in the order tiles outer, signals inner; every condition is block-uniform
+    int nq = q + 1, nt0 = t0;
+    if (nq > S) {
+      nq = 0;
+      nt0 = t0 + FPB;
+    }
+    const bool more = nt0 < tend;
+    if (more) fetch(nt0, nq, pre);  // the next signal's samples travel while this one is transformed
+    const bool active = fr < min(FPB, T - t0);
+    v2f z[16];
+#pragma unroll
+    for (int n1 = 0; n1 < 16; ++n1) {
+      const v2f sm = *reinterpret_cast<const v2f*>(&smp[fr * HOP + 32 * n1 + 2 * j]);
+      const v2f w = *reinterpret_cast<const v2f*>(&win[32 * n1 + 2 * j]);
+      z[n1] = sm * w;
+    }
+    fft256_g16(z, xch[4 * wave + g], t256, j);
+
+    if (active) {  // uniform over the 16-lane group, which is all the shuffles below reach
+      const int64_t row = offs ? (int64_t)offs[t0 + fr] + u : row_base[u] + (t0 + fr);
+      float* const base = (q == 0 ? mix_rows : targets + (int64_t)(q - 1) * plane) + row * ld;
+      float* const olo = base + j;
+      float* const ohi = base + (256 - j);
+      const float* const mlo = mix_rows + row * ld + j;  // |Y| of this frame, as stored
+      const float* const mhi = mix_rows + row * ld + (256 - j);
+      float2* const ylo = ywork + row * NBIN + j;  // the mixture's bins of this frame, written at q == 0 by this very lane
+      float2* const yhi = ywork + row * NBIN + (256 - j);
+#pragma unroll
+      for (int k2 = 0; k2 < 8; ++k2) {  // real-FFT split as in stft_kernel
+        v2f zc;
+        zc.x = __shfl(z[15 - k2].x, partner, 64);
+        zc.y = __shfl(z[15 - k2].y, partner, 64);
+        if (j == 0) zc = z[(16 - k2) & 15];
+        const v2f zk = z[k2], cz = conj(zc);
+        const int k = j + 16 * k2;
+        const v2f A = 0.5f * (zk + cz), Bt = cmul(ld2(&tw[k]), 0.5f * mul_mi(zk - cz));
+        v2f xa = A + Bt, xb = conj(A - Bt);  // X[k], X[256 - k]
+        pin(xa);
+        pin(xb);
+        if (q == 0) {
+          st2(ylo + 16 * k2, xa);
+          st2(yhi - 16 * k2, xb);
+          olo[16 * k2] = __builtin_amdgcn_sqrtf(xa.x * xa.x + xa.y * xa.y);
+          ohi[-16 * k2] = __builtin_amdgcn_sqrtf(xb.x * xb.x + xb.y * xb.y);
+        } else {
+          olo[16 * k2] = target(xa, ld2(ylo + 16 * k2), mlo + 16 * k2);
+          ohi[-16 * k2] = target(xb, ld2(yhi - 16 * k2), mhi - 16 * k2);
+        }
+      }
+      if (j == 0) {  // bin 128 pairs with itself
+        const v2f zk = z[8], cz = conj(zk);
+        v2f xa = 0.5f * (zk + cz) + cmul(ld2(&tw[128]), 0.5f * mul_mi(zk - cz));
+        pin(xa);
+        if (q == 0) {
+          st2(ylo + 128, xa);
+          olo[128] = __builtin_amdgcn_sqrtf(xa.x * xa.x + xa.y * xa.y);
+        } else {
+          olo[128] = target(xa, ld2(ylo + 128), mlo + 128);
+        }
+      }
+    }
+    if (!more) break;
+    __syncthreads();  // every wave is done with smp
+    stash(pre);
+    __syncthreads();
+    t0 = nt0;
+    q = nq;
+  }
+}
+
 }  // namespace
+
+extern "C" int sk_stft_psa(const void* wav, int pcm16, const int64_t* sig_offs, const int32_t* nsamp, int B, int S, int n_fft,
+                           int hop, int clamp, const int32_t* offs, const int64_t* row_base, float* mix_rows, float* targets,
+                           int ld, int64_t plane, void* ws, int min_samples, int max_frames, sk_stream_t stream) {
+  SK_CHECK_ARG(n_fft == NFFT && hop == HOP, "sk_stft_psa: only n_fft=512, hop=128 are built (got %d, %d)", n_fft, hop);
+  SK_CHECK_ARG(S >= 1 && S <= SK_MAXS, "sk_stft_psa: num_spk %d outside 1..%d", S, SK_MAXS);
+  SK_CHECK_ARG(min_samples > NFFT / 2, "sk_stft_psa: an utterance of %d samples: reflect padding needs more than n_fft/2 = %d",
+               min_samples, NFFT / 2);
+  SK_CHECK_ARG(wav && sig_offs && nsamp && mix_rows && targets && ws, "sk_stft_psa: null pointer");
+  SK_CHECK_ARG((offs != nullptr) != (row_base != nullptr), "sk_stft_psa: give the packed batch's offs or per-utterance row bases, one of them");
+  SK_CHECK_ARG(ld >= NBIN, "sk_stft_psa: rows of %d floats hold fewer than F = %d", ld, NBIN);
+  SK_CHECK_ARG(S == 1 || plane >= 0, "sk_stft_psa: negative plane stride");
+  SK_CHECK_ARG(B > 0 && B <= 65535 && max_frames > 0, "sk_stft_psa: bad B/max_frames");
+  dim3 grid((unsigned)sk_cdiv(max_frames, FPB * TPB), (unsigned)B);
+  hipLaunchKernelGGL(stft_psa_kernel, grid, dim3(256), 0, (hipStream_t)stream, wav, pcm16, sig_offs, nsamp, B, S, clamp, offs,
+                     row_base, mix_rows, targets, ld, plane, (float2*)ws);
+  SK_CHECK_LAUNCH("sk_stft_psa");
+  return SK_OK;
+}
 
 extern "C" int sk_stft(const void* wav, int pcm16, const int64_t* wav_offs, const int32_t* nsamp, int nutt, int n_fft,
                        int hop, int want_complex, void* out, const int64_t* out_offs, const int64_t* stride_t,

@@ -127,6 +127,37 @@ def wave_features_from_pcm(pcm, dev, source_mags=True):
   return feats[0], feats[1:], pk, wave
 
 
+PSA_TARGETS = ('psa', 'tpsa')        # Prefetcher(targets=...) / archs/uPIT.py's loss conf key: the target as it is / held to [0, |Y|]
+
+
+def psa_features_from_pcm(pcm, dev, clamp=False):
+  """features_from_pcm for the phase-sensitive losses (archs/uPIT.py, loss=psa / tpsa; sepkern/psa.py): the same batch ->
+  (mix (Rp,F), [target (Rp,F)...], Packing), the mixture's magnitude rows (bit for bit features_from_pcm's: the network's input
+  does not depend on the loss) and, where features_from_pcm returns the sources' magnitudes, their phase-sensitive targets
+  Re(S_s conj Y) / |Y| (clamp: held to [0, |Y|]).  ONE launch, sk_stft_psa, writes the packed rows: no (T,B,F) grid, no pack, no
+  source spectrum in memory.  A batch that carries 'rate' / 'target_rate' with a signal at another rate is resampled on the
+  device first (sk_resample).  Everything is enqueued on the CURRENT stream."""
+  import torch
+  from . import ops
+  from .packing import Packing
+  flat = pcm['flat']
+  if flat.device != torch.device(dev):
+    flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
+  src = flat
+  flat, ns = _at_target_rate(pcm, flat)                # (another tensor only when a signal had to be resampled)
+  nk, total = len(pcm['keys']), sum(ns)
+  if nk < 2:
+    raise ValueError("psa_features_from_pcm: the batch holds no source waveform")
+  pk = Packing.from_lens([1 + n // 128 for n in ns], dev)
+  if pk.perm is not None:
+    raise ValueError("psa_features_from_pcm: the batch must be sorted by frame count, longest first (WavCollator does)")
+  starts = [sum(ns[:j]) for j in range(len(ns))]
+  mix, targets = ops.stft_psa(flat, [[q * total + st for st in starts] for q in range(nk)], ns, nk - 1, pk=pk, clamp=clamp)
+  src.record_stream(torch.cuda.current_stream(dev))
+  flat.record_stream(torch.cuda.current_stream(dev))
+  return mix, targets, pk
+
+
 # ----------------------------------------------------------------------------------------------- staging ahead of the step
 class Prefetcher:
   """Iterates a DataLoader of the arch's batches and hands them over ALREADY ON THE GPU, as packed rows.
@@ -141,14 +172,19 @@ class Prefetcher:
   The consumer's stream waits for the batch's event; nothing on the host blocks.  Everything else in a batch (names,
   ...) passes through untouched.
   keep_wave (PCM batches only): the staged batch also carries 'wave' -- the mixture's complex rows and the device PCM
-  (wave_features_from_pcm) -- for a loss that works on waveforms; the sources' magnitudes are then not computed."""
+  (wave_features_from_pcm) -- for a loss that works on waveforms; the sources' magnitudes are then not computed.
+  targets ('psa' or 'tpsa'; PCM batches only): the staged 'packed' batch carries the sources' phase-sensitive targets
+  (psa_features_from_pcm; 'tpsa': held to [0, |Y|]) where it would carry their magnitudes."""
 
   _END = object()
 
-  def __init__(self, loader, device, depth=2, keep_wave=False):
+  def __init__(self, loader, device, depth=2, keep_wave=False, targets=None):
     import queue
     import threading
     self.loader, self.device, self.depth, self.keep_wave = loader, device, max(1, int(depth)), bool(keep_wave)
+    self.targets = self._targets_kind(targets)
+    if self.targets and self.keep_wave:
+      raise ValueError("Prefetcher: keep_wave and targets belong to different losses; give one of them")
     self._queue_mod, self._threading = queue, threading
     self._stuck = None          # a staging thread that did not end when its consumer left early
 
@@ -194,7 +230,7 @@ class Prefetcher:
             except StopIteration:
               break
             t1 = time.perf_counter()
-            staged = self.stage(batch, dev, self.keep_wave)
+            staged = self.stage(batch, dev, self.keep_wave, self.targets)
             ev = torch.cuda.Event()
             ev.record(stream)
             if timing:
@@ -248,13 +284,21 @@ class Prefetcher:
       yield w['flat']
 
   @staticmethod
-  def stage(batch, dev, keep_wave=False):
+  def _targets_kind(targets):
+    if targets is not None and targets not in PSA_TARGETS:
+      raise ValueError("Prefetcher(targets=%r): None, %s" % (targets, " or ".join(repr(t) for t in PSA_TARGETS)))
+    return targets
+
+  @staticmethod
+  def stage(batch, dev, keep_wave=False, targets=None):
     """One batch -> {'packed': (mix (R,F), [source (R,F)...], Packing), <other keys unchanged>} on `dev`, enqueued on the
     CURRENT stream.  keep_wave: a PCM batch also gets 'wave' (wave_features_from_pcm; no source magnitudes); a batch that
-    holds no PCM cannot, which is an error here rather than at the loss."""
+    holds no PCM cannot, which is an error here rather than at the loss.  targets ('psa' / 'tpsa'): a PCM batch's 'packed' holds
+    phase-sensitive targets in place of the source magnitudes (psa_features_from_pcm); a batch without PCM is again an error."""
     import torch
     from torch.nn.utils.rnn import PackedSequence
     from .packing import Packing
+    targets = Prefetcher._targets_kind(targets)
     if not isinstance(batch, dict):
       return batch
     if 'pcm' in batch:                   # WavCollator: {'pcm': {'flat': int16 tensor, 'keys', 'lens'}}: one pinned copy, STFT here
@@ -263,6 +307,9 @@ class Prefetcher:
       out = {k: v for k, v in batch.items() if k != 'pcm'}
       if keep_wave:
         mix, sources, pk, out['wave'] = wave_features_from_pcm(dict(pcm, flat=host), dev, source_mags=False)
+      elif targets:
+        mix, sources, pk = psa_features_from_pcm(dict(pcm, flat=host), dev, clamp=targets == 'tpsa')
+        out['targets'] = targets         # (says what 'packed' holds in place of the source magnitudes)
       else:
         mix, sources, pk = features_from_pcm(dict(pcm, flat=host), dev)
       out['packed'] = (mix, sources, pk)
@@ -270,6 +317,8 @@ class Prefetcher:
       return out
     if keep_wave:
       raise ValueError("Prefetcher(keep_wave=True) needs PCM batches (WavTrainSet / --wav-input): this batch holds no waveforms")
+    if targets:
+      raise ValueError("Prefetcher(targets=%r) needs PCM batches (WavTrainSet / --wav-input): this batch holds no waveforms" % targets)
     seqs = {k: v for k, v in batch.items() if isinstance(v, PackedSequence)}
     if 'mix' not in seqs:
       return batch

@@ -656,6 +656,67 @@ def sisdr_mask_grad(est, est_offs, ref, ref_offs, best_perm, coef, gscale, mixc,
     return out
 
 
+# ----------------------------------------------------------------------------- phase-sensitive targets (loss=psa / tpsa)
+def stft_psa(flat, sig_offs, nsamp, S, pk=None, clamp=False, out=None, repeat=1):
+    """The network's input and the phase-sensitive targets of a batch of waveforms in one launch (sk_stft_psa; sepkern/psa.py
+    defines the arithmetic).  flat: ONE 1-D CUDA tensor holding every signal, float32 or int16 PCM (scaled by 1/32768
+    in-kernel); sig_offs: S + 1 lists (the mixture's, then source 1 .. S) of B offsets into flat; nsamp: samples per utterance.
+    -> (mix_rows, targets): the mixture's magnitudes |Y| and a list of S views of one buffer, target_s = Re(S_s conj Y) / |Y|
+    (clamp: held to [0, |Y|]).
+    With pk (the batch's Packing, length-sorted: no perm) both are packed rows (Rp, 257), rows R.. zero; without it, utterance u
+    is the block of T_u = 1 + nsamp[u] // 128 rows that starts at row sum_{v<u} T_v (frame-major (T_u, 257)).
+    out = (mix (>= rows, ld), targets (S, >= rows, ld)) float32 with unit column stride is written in place."""
+    pcm16 = flat.dtype == torch.int16
+    _chk(flat, torch.int16 if pcm16 else torch.float32)
+    ns = [int(n) for n in nsamp]
+    B, F, dev = len(ns), 257, flat.device
+    sig_offs = [[int(o) for o in offs] for offs in sig_offs]
+    if flat.dim() != 1 or not flat.is_contiguous() or B == 0:
+        raise _lib.SepkernError("stft_psa needs one contiguous 1-D tensor of samples and at least one utterance")
+    if len(sig_offs) != S + 1 or any(len(o) != B for o in sig_offs):
+        raise _lib.SepkernError("stft_psa needs S + 1 = %d lists of %d signal offsets (mixture first)" % (S + 1, B))
+    if any(o < 0 or o + n > flat.numel() for offs in sig_offs for o, n in zip(offs, ns)):
+        raise _lib.SepkernError("stft_psa: a signal runs past the sample buffer")
+    Ts = [1 + n // 128 for n in ns]
+    if pk is not None:
+        if pk.perm is not None:
+            raise _lib.SepkernError("stft_psa needs a length-sorted batch (Packing without perm)")
+        if pk.B != B or [int(t) for t in pk.lens_host] != Ts:
+            raise _lib.SepkernError("stft_psa: the Packing's frame counts are not those of the signals")
+        rows, rows_p, bases = pk.R, pk.Rp, None
+    else:
+        bases, rows = [], 0
+        for T in Ts:
+            bases.append(rows)
+            rows += T
+        rows_p = rows
+    if out is None:
+        mix = torch.empty(rows_p, F, dtype=torch.float32, device=dev)
+        tgt = torch.empty(max(S, 1), rows_p, F, dtype=torch.float32, device=dev)
+        if rows_p > rows:
+            mix[rows:].zero_()
+            tgt[:, rows:].zero_()
+    else:
+        mix, tgt = out
+    _chk(mix)
+    _chk(tgt)
+    if mix.dim() != 2 or tgt.dim() != 3 or mix.stride(1) != 1 or tgt.stride(2) != 1 or tgt.stride(1) != mix.stride(0) or \
+            mix.shape[0] < rows or tgt.shape[1] < rows or tgt.shape[0] < S or mix.shape[1] != tgt.shape[2]:
+        raise _lib.SepkernError("stft_psa: out must be (mix (>= rows, ld), targets (S, >= rows, ld)) with one row stride")
+    ld = int(mix.stride(0)) if mix.shape[0] > 1 else int(mix.shape[1])
+    ws = torch.empty(rows * F, 2, dtype=torch.float32, device=dev)       # the mixture's complex bins on their way to the contractions
+    # descriptor arrays must outlive the (asynchronous) launch call: keep references until it returns
+    d64 = _i64([o for offs in sig_offs for o in offs] + (bases or []), dev)
+    d_ns = torch.tensor(ns, dtype=torch.int32, device=dev)
+    # algorithmic bytes per frame: 128 new samples of each of the S + 1 signals in, their 257 values out
+    with _timed("stft_psa_kernel", repeat * float(sum(Ts)) * (S + 1) * (128 * (2 if pcm16 else 4) + 257 * 4)):
+        for _ in range(repeat):
+            _lib.call("sk_stft_psa", _ptr(flat), int(pcm16), _ptr(d64), _ptr(d_ns), B, int(S), 512, 128, int(bool(clamp)),
+                      _ptr(pk.offs) if pk is not None else None, _ptr(d64[(S + 1) * B:]) if pk is None else None,
+                      _ptr(mix), _ptr(tgt), ld, int(tgt.stride(0)), _ptr(ws), min(ns), max(Ts), _stream())
+    return mix, [tgt[s] for s in range(S)]
+
+
 # ----------------------------------------------------------------------------- RSH loss / attention
 def rsh_loss_fwd(mask, x, srcs, lens, used):
     """One greedy-assignment pass.  mask (T,B,F), x (T,B,2F) [mixture | attention], srcs list of S (T,B,F),

@@ -4,11 +4,12 @@ steps/evaluate_oracle.py:120-145; its segments branch does not run: `use_seg`/`r
 
 For every utterance of <data-dir>/wav.scp (wav files at another rate than --sample-rate are first resampled to it on the GPU,
 sk_resample, as the reference's librosa.load(sr=) does): STFT of the mixture and of each source on the GPU (sk_stft), the
-ideal ratio mask |S_i| / |M| (or the binary mask with --hard-mask), mask-apply + iSTFT on the GPU
+ideal ratio mask |S_i| / |M| (or the binary mask with --hard-mask, or with --psm the ideal phase-sensitive mask
+clip(|S_i| cos(theta_i - theta_M) / |M|, 0, 1) of sepkern/psa.py, its numerator made by sk_stft_psa), mask-apply + iSTFT on the GPU
 (sk_mask_istft), then the score: BSS Eval SDR / SIR / SAR without permutation search (the reference calls
 mir_eval's bss_eval_sources with compute_permutation=False, steps/evaluate_oracle.py:118,143; here
 sepkern/bsseval.py) into {session,source}_{SDR,SIR,SAR}s.txt + *_stats.txt under
-<data-dir>/oracle_{soft,hard}_mask_eval/, and SI-SDR under its own SISDR names.
+<data-dir>/oracle_{soft,hard,psm}_mask_eval/, and SI-SDR under its own SISDR names.
 """
 import argparse
 import glob
@@ -27,6 +28,8 @@ def get_args(argv=None):
   iSTFT path the separation models use""")
   parser.add_argument("data_dir", metavar="data-dir", type=str, help="Data directory with wav.scp")
   parser.add_argument("--hard-mask", action='store_true', help="Use hard mask", default=False)
+  parser.add_argument("--psm", action='store_true', default=False,
+                      help="Use the ideal phase-sensitive mask (the oracle of the loss=psa / tpsa targets)")
   parser.add_argument("--fft-dim", type=int, help="Dimension of FFT", default=512)
   parser.add_argument("--step-size", type=int, help="STFT step size", default=128)
   parser.add_argument("--sample-rate", type=int, help="Audio sample rate", default=8000)
@@ -40,12 +43,14 @@ def main(argv=None):
   args = get_args(argv)
   if args.fft_dim != 512 or args.step_size != 128:
     raise ValueError("the HIP STFT kernels are built for --fft-dim 512 --step-size 128")
+  if args.hard_mask and args.psm:
+    raise ValueError("--hard-mask and --psm are two different oracles: give one of them")
   import torch
   from sepkern import ops
   from sepkern.bsseval import bss_eval_sources
   from sepkern.sisdr import si_sdr
   from evaluate_sources import MetricFiles
-  dir_out = args.data_dir + ("/oracle_hard_mask_eval/" if args.hard_mask else "/oracle_soft_mask_eval/")
+  dir_out = args.data_dir + ("/oracle_hard_mask_eval/" if args.hard_mask else "/oracle_psm_mask_eval/" if args.psm else "/oracle_soft_mask_eval/")
   os.makedirs(dir_out, exist_ok=True)
   out = {m: MetricFiles(dir_out, m) for m in ("SDR", "SIR", "SAR", "SISDR")}
   pending = []                                    # --gpu: (id, device fp32 estimates, device references: int16 PCM, or float32 once resampled)
@@ -93,8 +98,18 @@ def main(argv=None):
         pcm = list(torch.split(flat, outs))
       num_src = len(pcm) - 1
       mix_spec = ops.stft_batch([pcm[0]], want_complex=True, layout="FT")[0]           # (257, T) complex64
-      mags = torch.stack(ops.stft_batch(pcm[1:], want_complex=False, layout="FT"))      # (S, 257, T)
-      if args.hard_mask:
+      if args.psm:
+        n = int(pcm[0].numel())
+        if num_src < 1 or any(int(p.numel()) != n for p in pcm):
+          raise ValueError("%s: --psm needs sources of the mixture's length" % reco_id)
+        # truncated targets clip(Re(S_i conj M) / |M|, 0, |M|) and |M| as (T, 257) blocks, one launch; the mask is their quotient
+        mag, tg = ops.stft_psa(torch.cat(pcm), [[q * n] for q in range(num_src + 1)], [n], num_src, clamp=True)
+        masks = (torch.stack(tg) / mag.clamp_min(1e-20)).transpose(1, 2)                # (S, 257, T)
+      else:
+        mags = torch.stack(ops.stft_batch(pcm[1:], want_complex=False, layout="FT"))      # (S, 257, T)
+      if args.psm:
+        pass
+      elif args.hard_mask:
         masks = torch.nn.functional.one_hot(mags.argmax(0), num_src).permute(2, 0, 1).float()
       else:
         masks = mags / mix_spec.abs().clamp_min(1e-20)

@@ -15,6 +15,10 @@ the on-disk (257, T) layout.  Only mono 16-bit PCM is supported.  A file at anot
 interpolation librosa.load(sr=) delegates to resampy, sepkern/resample.py); files already at
 --sample-rate (the reference's data is wav8k) go to the STFT as int16, untouched.
 
+--psa-targets (train only): s1..sS hold the phase-sensitive targets |S_i| cos(theta_i - theta_mix) of sepkern/psa.py instead of
+the magnitudes |S_i| (--psa-clamp: held to [0, |mix|]), made together with the mixture's magnitudes by one sk_stft_psa launch
+per chunk; file names and keys stay, so the unchanged npz training path (loss=mse) then trains the phase-sensitive loss.
+
 The stage is host-bound (the kernel transforms ~2 G frames/s; zlib compresses ~25 MB/s per core), so the host side is
 organised around that: a chunk's wav files are read by a thread pool while the previous chunk is on the GPU, every
 chunk crosses PCIe as ONE pinned copy each way, and np.savez_compressed (zlib releases the GIL) runs on --writers
@@ -46,6 +50,10 @@ def get_args():
   parser.add_argument("--sample-rate", type=int, help="Audio sample rate", default=8000)
   parser.add_argument("--batch-files", type=int, help="utterances per kernel launch", default=256)
   parser.add_argument("--writers", type=int, default=8, help="threads that read wav files and compress / write the npz files")
+  parser.add_argument("--psa-targets", action='store_true', default=False,
+                      help="train only: store the sources' phase-sensitive targets (sepkern/psa.py) as s1..sS instead of their magnitudes")
+  parser.add_argument("--psa-clamp", action='store_true', default=False,
+                      help="with --psa-targets: the truncated form, targets held to [0, |mix|]")
   return parser.parse_args()
 
 
@@ -66,6 +74,10 @@ def main():
   args = get_args()
   if args.fft_dim != 512 or args.step_size != 128:
     raise ValueError("the HIP STFT kernel is built for --fft-dim 512 --step-size 128")
+  if args.psa_clamp and not args.psa_targets:
+    raise ValueError("--psa-clamp goes with --psa-targets")
+  if args.psa_targets and args.data_type != "train":
+    raise ValueError("--psa-targets: only the train features hold sources")
   import torch
   from sepkern import ops
   from sepkern.data import host_threads
@@ -114,6 +126,39 @@ def main():
   def write_npz(seg_id, file_dict):
     np.savez_compressed(os.path.join(args.feat_dir, seg_id), **file_dict)
 
+  def write_npz_rows(seg_id, rows_dict):       # --psa-targets: (T, 257) blocks as the kernel wrote them -> the on-disk (257, T)
+    write_npz(seg_id, {key: np.ascontiguousarray(a.T) for key, a in rows_dict.items()})
+
+  def psa_chunk(dev_in, ns, entries):
+    """The chunk's files as {seg_id: {'mix': (T,257), 's1': ...}} host arrays: one sk_stft_psa launch per source count."""
+    starts = np.concatenate([[0], np.cumsum(ns)])
+    out, copies = {}, []
+    for S in sorted(set(len(keyed) - 1 for _, _, keyed in entries)):
+      group = [e for e in entries if len(e[2]) - 1 == S]
+      lens = [ns[keyed[0][1]] for _, _, keyed in group]
+      for (seg_id, _, keyed), n in zip(group, lens):
+        if any(ns[k] != n for _, k in keyed):
+          raise ValueError("%s: a source's length differs from its mixture's" % seg_id)
+      Ts = [1 + n // 128 for n in lens]
+      if S == 0:                               # a mixture without sources: its magnitudes only
+        mags = torch.cat(ops.stft_batch([dev_in[starts[keyed[0][1]]:starts[keyed[0][1]] + n] for (_, _, keyed), n in zip(group, lens)]))
+        planes = [mags]
+      else:
+        sig_offs = [[int(starts[keyed[q][1]]) for _, _, keyed in group] for q in range(S + 1)]
+        mix, tg = ops.stft_psa(dev_in, sig_offs, lens, S, clamp=args.psa_clamp)
+        planes = [mix] + tg
+      host = [torch.empty(p.shape, dtype=p.dtype).pin_memory() for p in planes]
+      for h, p in zip(host, planes):
+        h.copy_(p, non_blocking=True)
+      copies.append((group, Ts, host))
+    torch.cuda.synchronize()
+    for group, Ts, host in copies:
+      at = 0
+      for (seg_id, _, keyed), T in zip(group, Ts):
+        out[seg_id] = {key: h.numpy()[at:at + T] for (key, _), h in zip(keyed, host)}
+        at += T
+    return out
+
   with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, args.writers)) as pool:
     def submit_read(chunk):      # a chunk's files, split over the pool's threads (file reads release the GIL)
       parts = [chunk[k::max(1, args.writers)] for k in range(max(1, args.writers))]
@@ -138,6 +183,15 @@ def main():
       if any(fs != args.sample_rate for fs in rates):                      # resampled on the device, grouped by rate; float32 from here
         dev_in, ns = ops.pcm_to_rate(dev_in, ns, rates, args.sample_rate)
       Ts = [1 + n // 128 for n in ns]                                      # (frame counts of the signals the STFT sees)
+      if args.psa_targets:
+        rows = psa_chunk(dev_in, ns, entries)
+        for seg_id, num_spk, keyed in entries:
+          writing.append(pool.submit(write_npz_rows, seg_id, rows[seg_id]))
+          featF.write(seg_id + ' ' + os.path.join(args.feat_dir, seg_id) + '.npz\n')
+          utt2num_spkF.write(seg_id + ' ' + str(num_spk) + '\n')
+          n_frames += Ts[keyed[0][1]]
+        writing = [w for w in writing if not (w.done() and w.result() is None)]
+        continue
       out_offs, acc = [], 0
       for T in Ts:
         out_offs.append(acc)

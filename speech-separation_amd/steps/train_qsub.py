@@ -147,6 +147,20 @@ def waveform_loss(m, args):
   return kind == 'sisdr'
 
 
+def prefetch_targets(m, args):
+  """'psa' / 'tpsa' when the conf file selects a loss whose targets are made from the waveforms (archs/uPIT.py: the
+  phase-sensitive losses) -- the prefetcher then stages those targets where it would stage the source magnitudes -- else None.
+  Like a waveform loss it cannot be computed from npz magnitude features: without --wav-input the run ends here."""
+  if not hasattr(m, "parse_loss"):
+    return None
+  kind = m.parse_loss(read_model_conf(args.model_config).get('loss', 'mse'))
+  if kind not in getattr(m, "PSA_LOSSES", ()):
+    return None
+  if not args.wav_input:
+    raise SystemExit(m.needs_waveforms(kind))
+  return kind
+
+
 # ----------------------------------------------------------------------------------------------- data
 def wav_train_set(m, args, data_dir):
   """The arch's WavTrainSet over data_dir; --sample-rate is handed on only when given (an arch without the argument keeps working)."""
@@ -192,7 +206,7 @@ def staged(loader, args):
     return loader
   from sepkern.data import Prefetcher
   return Prefetcher(loader, torch.device("cuda", torch.cuda.current_device()), depth=args.prefetch,
-                    keep_wave=getattr(args, "keep_wave", False))
+                    keep_wave=getattr(args, "keep_wave", False), targets=getattr(args, "prefetch_targets", None))
 
 
 def validation_batches(m, args, rank, world):
@@ -422,6 +436,7 @@ def main(argv=None):
     print("Using GPU", gpu, "of", world)
   m = __import__(args.arch_file)
   args.keep_wave = waveform_loss(m, args)        # (the prefetcher then carries the waveforms with the staged batch)
+  args.prefetch_targets = prefetch_targets(m, args)     # (... or stages phase-sensitive targets in place of the source magnitudes)
   torch.cuda.set_device(gpu)
   from sepkern.data import host_threads
   host_threads()                                 # (the arithmetic is on the GPU; see sepkern.data.host_threads)
