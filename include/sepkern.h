@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 136
+#define SK_VERSION 137
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -85,6 +85,23 @@ int sk_stft(const void* wav, int pcm16, const int64_t* wav_offs, const int32_t* 
 int sk_resample(const void* in, int pcm16, const int64_t* in_offs, const int32_t* n_in, int nsig,
                 const float* taps, int L, int M, int ntaps,
                 float* out, const int64_t* out_offs, const int32_t* n_out, int max_out, sk_stream_t stream);
+
+/* ---------------------------------------------------------------- dynamic mixing (training mixtures made on the device)
+ * Mixes B training mixtures from single-speaker signals in ONE launch, by the WSJ0-2mix rule (sepkern/mixing.py states the
+ * arithmetic and restates it in numpy fp64).  Source s of mixture u: nsamp[u] samples x_s at in + in_offs[s*B + u] (elements;
+ * float32, or int16 PCM scaled by 1/32768 when pcm16 != 0); a crop is an offset, and two mixtures may read the same samples.
+ *   P_s = mean x_s^2 (fp64);  g_s = fp32(amp[s*B + u] / sqrt(P_s)), 0 where P_s < 2^-40 (a silent source: no NaN, no huge gain)
+ *   m = max_n max(|sum_s g_s x_s[n]|, max_s |g_s x_s[n]|) (fp32);  c = fp32(peak[u] / m), 0 where m == 0;  G_s = g_s * c (fp32)
+ *   out + out_offs[(1+s)*B + u]: G_s x_s[n];   out + out_offs[u]: the mixture fmaf(G_s, x_s[n], acc), s ascending from acc = 0
+ * (the sum inside m is that same chain with g).  amp are LINEAR amplitudes (the host computes 10^(snr/20)).  The mixture and its
+ * sources share one scale, the largest magnitude among them is peak[u]; power is the plain mean square, not an active level.
+ * quantize != 0: every output v becomes clip(rint(32768 v), -32768, 32767) / 32768, what a 16-bit wav file would hand back.
+ * Only nsamp[u] floats at each of the (S + 1) B output offsets are written; gains (S*B floats, may be NULL) receives G.
+ * One workgroup per mixture, no workspace, no atomics: bitwise reproducible, and a mixture's numbers do not depend on the batch
+ * around it.  The descriptor arrays live on the device.  1 <= S <= 4, 1 <= B <= 65535, nsamp[u] >= 1. */
+int sk_dynamic_mix(const void* in, int pcm16, const int64_t* in_offs, const int32_t* nsamp, int B, int S,
+                   const float* amp, const float* peak, int quantize,
+                   float* out, const int64_t* out_offs, float* gains, sk_stream_t stream);
 
 /* ---------------------------------------------------------------- mask-apply + iSTFT back end
  * Replaces np.multiply(mix_spec, mask) + librosa.core.istft(hop_length=128) + (*32767).astype(int16)

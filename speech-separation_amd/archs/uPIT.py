@@ -29,6 +29,8 @@ Beyond the reference (all optional, defaults reproduce it):
     |S_s| cos(theta_s - theta_mix) in place of |S_s| ('tpsa': held to [0, |mix|]), made from the waveforms by one kernel
     (sk_stft_psa).  It needs waveforms too -- or npz features written by steps/extract_feats.py --psa-targets, which train
     with the default loss=mse.  compute_loss returns what it returns for 'mse'.
+  * DynMixTrainSet / DynMixCollator (steps/train_qsub.py --dynamic-mix): training mixtures drawn afresh every epoch from
+    single-speaker utterances and mixed on the GPU (sk_dynamic_mix); every loss above trains on them.
 """
 import itertools
 import os
@@ -194,6 +196,152 @@ class WavCollator():
     flat = np.concatenate([batch[i][k] for k in keys for i in order])
     pcm = {'flat': torch.from_numpy(flat), 'keys': keys, 'lens': [int(len(batch[i]['mix'])) for i in order]}
     if rates is not None:      # 'lens' stay the sample counts on disk; sepkern.data resamples when a rate differs from the target
+      pcm['rate'] = [rates[i] for i in order]
+      pcm['target_rate'] = self.sample_rate
+    return {'pcm': pcm}
+
+
+class DynMixTrainSet(Dataset):
+  """Dynamic mixing (steps/train_qsub.py --dynamic-mix): every training mixture is drawn afresh, every epoch, from
+  single-speaker utterances -- random partners, levels, crops and peak -- and MIXED ON THE GPU (sk_dynamic_mix; sepkern/mixing.py
+  states the rule).  datadir is Kaldi-style: wav.scp (`<utt-id> <path>` of mono 16-bit wav files, one speaker each) and utt2spk
+  (`<utt-id> <speaker>`).  The loader ships only the int16 slices of the S sources: S files are read per mixture, not S + 1, and
+  no float arithmetic runs on the host.
+
+  The dataset index encodes the epoch: idx = epoch * mixes_per_epoch + i (sepkern.dist.MixDraws hands those out), and item idx is
+  a function of (seed, idx) ALONE -- a numpy Generator seeded with that pair draws num_spk distinct speakers and one utterance of
+  each, the common length n = min(len_s) (at most max_samples when that is > 0), a uniform crop start in every longer source,
+  snr_s ~ U(-snr_db, +snr_db) dB independently per source (2.5: the level difference of two speakers lies in [-5, 5] dB, WSJ0-2mix's
+  range) and a peak uniform in [peak[0], peak[1]].  Persistent loader workers therefore never need to be told the epoch, and a
+  restarted run draws what the uninterrupted one would have.
+  -> {'source1': int16[n], ..., 'amp': [10^(snr_s / 20)], 'peak': p} (+ 'rate' with sample_rate: the files' rate; the batch is
+  resampled on the GPU in front of the mixing, and lengths, max_samples and the 257-sample limit count at sample_rate)."""
+
+  def __init__(self, datadir, num_spk, mixes_per_epoch=None, snr_db=2.5, peak=(0.9, 0.9), max_samples=0, seed=0, sample_rate=None,
+               quantize=False):
+    import wave
+    self.num_spk, self.seed = int(num_spk), int(seed)
+    self.snr_db, self.peak, self.max_samples = float(snr_db), (float(peak[0]), float(peak[1])), int(max_samples)
+    self.sample_rate = None if sample_rate is None else int(sample_rate)
+    if not 1 <= self.num_spk <= 4:
+      raise ValueError("DynMixTrainSet: num_spk = %d outside 1..4" % self.num_spk)
+    if self.snr_db < 0 or not 0 < self.peak[0] <= self.peak[1] <= 1.0 or self.max_samples < 0 or 0 < self.max_samples < 257:
+      raise ValueError("DynMixTrainSet: snr_db >= 0, 0 < peak[0] <= peak[1] <= 1 and max_samples 0 or >= 257 expected")
+    spk_of = dict(line.split()[:2] for line in open(datadir + "/utt2spk") if line.strip())
+    by_spk, short, self.rate = {}, 0, None
+    for line in open(datadir + "/wav.scp"):
+      if not line.strip():
+        continue
+      utt, path = line.rstrip('\n').split(' ', 1)
+      if utt not in spk_of:
+        raise ValueError("DynMixTrainSet: utt2spk names no speaker for %r" % utt)
+      with wave.open(path, "rb") as w:
+        if w.getnchannels() != 1 or w.getsampwidth() != 2:
+          raise ValueError("%s: only mono 16-bit PCM wav is supported" % path)
+        n, fs = w.getnframes(), w.getframerate()
+      if self.rate is not None and fs != self.rate:
+        raise ValueError("%s is sampled at %d Hz, the files before it at %d: the utterances of a corpus must share one rate" % (path, fs, self.rate))
+      self.rate = fs
+      if self._at_rate(n) < 257:          # fewer samples than the STFT's reflect padding needs: cannot be framed
+        short += 1
+        continue
+      by_spk.setdefault(spk_of[utt], []).append((path, n))
+    if short:
+      raise ValueError("DynMixTrainSet: %d utterance(s) of %s/wav.scp have fewer than 257 samples and cannot be framed; "
+                       "take them out of the list" % (short, datadir))
+    self.speakers = [by_spk[s] for s in sorted(by_spk)]
+    if len(self.speakers) < self.num_spk:
+      raise ValueError("DynMixTrainSet: %d speaker(s) in %s, a mixture needs %d different ones" % (len(self.speakers), datadir, self.num_spk))
+    n_utts = sum(len(u) for u in self.speakers)
+    self.mixes_per_epoch = int(mixes_per_epoch) if mixes_per_epoch else n_utts // self.num_spk
+    if self.mixes_per_epoch < 1:
+      raise ValueError("DynMixTrainSet: mixes_per_epoch must be at least 1")
+    self.longest = max(n for u in self.speakers for _, n in u)
+    self.collator = DynMixCollator(self.sample_rate, quantize)
+
+  def _at_rate(self, n):
+    """Samples once at sample_rate (sepkern/resample.py's length rule)."""
+    if self.sample_rate is None or self.rate == self.sample_rate:
+      return n
+    from sepkern.resample import out_len
+    return out_len(n, self.rate, self.sample_rate)
+
+  def __len__(self):
+    return self.mixes_per_epoch          # of ONE epoch; any idx >= 0 is an item (MixDraws adds epoch * mixes_per_epoch)
+
+  def frame_counts(self):
+    """An upper bound of every item's frame count (the draw decides the true one); only good for balancing ranks."""
+    n = self._at_rate(self.longest)
+    return [1 + (min(n, self.max_samples) if self.max_samples else n) // 128] * self.mixes_per_epoch
+
+  def draw(self, idx):
+    """What item idx is made of, without touching a file: [(path, crop start, file length)] per source, n, snr dB per source, peak."""
+    rng = np.random.default_rng([self.seed, int(idx)])
+    picks = [self.speakers[k][int(rng.integers(len(self.speakers[k])))] for k in rng.choice(len(self.speakers), self.num_spk, replace=False)]
+    n = min(m for _, m in picks)
+    if self.max_samples:      # (in file samples: at most max_samples once resampled)
+      resampled = self.sample_rate is not None and self.rate != self.sample_rate
+      n = min(n, self.max_samples * self.rate // self.sample_rate if resampled else self.max_samples)
+    starts = [int(rng.integers(0, m - n + 1)) for _, m in picks]
+    snr = [float(v) for v in rng.uniform(-self.snr_db, self.snr_db, self.num_spk)]
+    return [(path, st, m) for (path, m), st in zip(picks, starts)], n, snr, float(rng.uniform(self.peak[0], self.peak[1]))
+
+  def __getitem__(self, idx):
+    import scipy.io.wavfile
+    from sepkern.mixing import snr_to_amp
+    if idx < 0:
+      raise IndexError(idx)
+    picks, n, snr, peak = self.draw(idx)
+    out = {}
+    for s, (path, st, m) in enumerate(picks):
+      _, x = scipy.io.wavfile.read(path, mmap=True)
+      if x.dtype != np.int16 or x.ndim != 1 or len(x) != m:
+        raise ValueError("%s: changed since the set was built (mono 16-bit PCM of %d samples expected)" % (path, m))
+      out['source' + str(s + 1)] = np.array(x[st:st + n])           # only the slice leaves the worker
+    out['amp'] = [float(snr_to_amp(v)) for v in snr]
+    out['peak'] = peak
+    if self.sample_rate is not None:
+      out['rate'] = int(self.rate)
+    return out
+
+
+class DynMixCollator():
+  """WavCollator for DynMixTrainSet's items: sorted by frame count, longest first, the SOURCES' int16 samples as one tensor,
+  key-major ('source1', ...), and what the GPU needs to mix them -- {'pcm': {'flat', 'keys': ['source1', ...], 'lens', 'mixing':
+  {'amp': [S][B], 'peak': [B], 'quantize'}}} (+ 'rate' / 'target_rate' as WavCollator).  The batch holds no 'mix': sepkern.data's
+  front ends make it (mixed_pcm) and go on as they do for a WavCollator batch."""
+
+  def __init__(self, sample_rate=None, quantize=False):
+    self.sample_rate = None if sample_rate is None else int(sample_rate)
+    self.quantize = bool(quantize)
+
+  def __call__(self, batch):
+    keys = sorted((k for k in batch[0] if k.startswith('source') and k[6:].isdigit()), key=lambda k: int(k[6:]))
+    if not keys or keys != ['source' + str(s + 1) for s in range(len(keys))]:
+      raise ValueError("DynMixCollator: an item holds the signals 'source1' .. 'source<S>' (got %r)" % sorted(batch[0]))
+    # ONE list of sample counts describes every key of the flat tensor (see WavCollator): a source of another length is an error
+    for d in batch:
+      for k in keys:
+        if k not in d or len(d[k]) != len(d[keys[0]]):
+          raise ValueError("DynMixCollator: signal %r of a mixture has %s samples, its first source %d -- the sources of a mixture "
+                           "must have one length" % (k, len(d[k]) if k in d else "no", len(d[keys[0]])))
+      if len(d.get('amp', ())) != len(keys) or 'peak' not in d:
+        raise ValueError("DynMixCollator: an item carries one 'amp' per source and a 'peak'")
+    if self.sample_rate is None:
+      rates = None
+      frames = [1 + len(d[keys[0]]) // 128 for d in batch]
+    else:
+      from sepkern.resample import out_len
+      if any('rate' not in d for d in batch):
+        raise ValueError("DynMixCollator(sample_rate=%d): an item does not say at which rate it was recorded ('rate')" % self.sample_rate)
+      rates = [int(d['rate']) for d in batch]
+      frames = [1 + out_len(len(d[keys[0]]), r, self.sample_rate) // 128 for d, r in zip(batch, rates)]
+    order = np.argsort(np.array(frames))[::-1]
+    flat = np.concatenate([batch[i][k] for k in keys for i in order])
+    pcm = {'flat': torch.from_numpy(flat), 'keys': keys, 'lens': [int(len(batch[i][keys[0]])) for i in order],
+           'mixing': {'amp': [[float(batch[i]['amp'][s]) for i in order] for s in range(len(keys))],
+                      'peak': [float(batch[i]['peak']) for i in order], 'quantize': self.quantize}}
+    if rates is not None:
       pcm['rate'] = [rates[i] for i in order]
       pcm['target_rate'] = self.sample_rate
     return {'pcm': pcm}

@@ -61,6 +61,39 @@ def _at_target_rate(pcm, flat):
   return out, outs[:len(ns)]
 
 
+def mixed_pcm(pcm, dev):
+  """A DynMixCollator batch -- pcm carries 'mixing' = {'amp': [S][B], 'peak': [B], 'quantize'} and the int16 samples of the
+  SOURCES only, keys 'source1' .. 'source<S>', no 'mix' -- mixed on the device (ops.dynamic_mix: one sk_dynamic_mix launch;
+  sepkern/mixing.py states the rule) -> an ordinary pcm dict ON the device: 'flat' float32 in WavCollator's layout, 'keys' =
+  ['mix', 'source1', ...], 'lens', no 'rate'.  One pinned H2D copy of the samples.  With 'rate' / 'target_rate' and an utterance
+  at another rate the sources are resampled first (ops.pcm_to_rate) and a mixture is as long as its shortest resampled source.
+  The front ends below start with this and go on as they do for a batch that came mixed from disk; enqueued on the CURRENT
+  stream."""
+  import torch
+  from . import ops
+  mixing, keys = pcm['mixing'], list(pcm['keys'])
+  S, ns = len(keys), [int(n) for n in pcm['lens']]
+  if keys != ['source' + str(s + 1) for s in range(S)]:
+    raise ValueError("mixed_pcm: a batch to be mixed holds the signals 'source1' .. 'source<S>' (got %r)" % keys)
+  flat = pcm['flat']
+  if flat.device != torch.device(dev):
+    flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
+  src = flat
+  total = sum(ns)
+  starts = [sum(ns[:j]) for j in range(len(ns))]
+  offs = [[s * total + st for st in starts] for s in range(S)]
+  rates, target = pcm.get('rate'), pcm.get('target_rate')
+  if rates is not None and target is not None and any(int(r) != int(target) for r in rates):
+    flat, outs = ops.pcm_to_rate(flat, ns * S, [int(r) for r in rates] * S, target)
+    ends = [sum(outs[:k]) for k in range(len(outs))]
+    offs = [ends[s * len(ns):(s + 1) * len(ns)] for s in range(S)]
+    ns = [min(outs[s * len(ns) + j] for s in range(S)) for j in range(len(ns))]
+  out, _ = ops.dynamic_mix(flat, offs, ns, mixing['amp'], mixing['peak'], quantize=bool(mixing.get('quantize', False)))
+  src.record_stream(torch.cuda.current_stream(dev))
+  flat.record_stream(torch.cuda.current_stream(dev))
+  return {'flat': out, 'keys': ['mix'] + keys, 'lens': ns}
+
+
 def features_from_pcm(pcm, dev):
   """The on-GPU feature front end of a wav batch.  pcm = the arch's WavCollator batch: {'flat': int16 tensor
   holding every signal of the batch, key-major ('mix', 'source1', ...), longest utterance first; 'keys'; 'lens': samples per
@@ -70,6 +103,8 @@ def features_from_pcm(pcm, dev):
   import torch
   from . import ops
   from .packing import Packing
+  if 'mixing' in pcm:                                  # DynMixCollator: the mixture is made here, on the device
+    pcm = mixed_pcm(pcm, dev)
   flat = pcm['flat']
   if flat.device != torch.device(dev):
     flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
@@ -100,6 +135,8 @@ def wave_features_from_pcm(pcm, dev, source_mags=True):
   import torch
   from . import ops
   from .packing import Packing
+  if 'mixing' in pcm:                                  # DynMixCollator: the mixture is made here, on the device
+    pcm = mixed_pcm(pcm, dev)
   flat = pcm['flat']
   if flat.device != torch.device(dev):
     flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
@@ -140,6 +177,8 @@ def psa_features_from_pcm(pcm, dev, clamp=False):
   import torch
   from . import ops
   from .packing import Packing
+  if 'mixing' in pcm:                                  # DynMixCollator: the mixture is made here, on the device
+    pcm = mixed_pcm(pcm, dev)
   flat = pcm['flat']
   if flat.device != torch.device(dev):
     flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
@@ -168,7 +207,8 @@ class Prefetcher:
   parallel), stages them through pinned memory and copies them on its own HIP stream, `depth` batches ahead:
     * PackedSequence batches (TrainSet): PackedSequence.data IS the engine's row layout -- one pinned copy + one
       asynchronous H2D per key, no padding anywhere; the batch arrives as {'packed': (mix, [sources], Packing)};
-    * PCM batches (WavTrainSet, --wav-input): the int16 samples are copied and the STFT runs on the copy stream too.
+    * PCM batches (WavTrainSet, --wav-input): the int16 samples are copied and the STFT runs on the copy stream too
+      (DynMixTrainSet, --dynamic-mix: the copy holds the sources only and the mixing runs there as well, mixed_pcm).
   The consumer's stream waits for the batch's event; nothing on the host blocks.  Everything else in a batch (names,
   ...) passes through untouched.
   keep_wave (PCM batches only): the staged batch also carries 'wave' -- the mixture's complex rows and the device PCM

@@ -5,7 +5,7 @@ contract is "same update as one device seeing the global batch" for everything e
 whose BATCH statistics stay per-rank (as under torch's DistributedDataParallel without SyncBatchNorm; DDP keeps the
 RUNNING statistics consistent by re-broadcasting the buffers from rank 0 at every forward -- here the ranks' running
 statistics are averaged once per epoch, before anything is scored or saved: average_bn_buffers):
-  * utterances are sharded by index across ranks (no data-path collective),
+  * utterances are sharded by index across ranks (no data-path collective; EpochShards, or MixDraws for dynamic mixing),
   * the PIT loss of every rank is divided by the GLOBAL norm sum(len)*F (one scalar all-reduce,
     known before the forward pass because it depends on lengths only),
   * the flat fp32 gradient buffer is summed with ONE all-reduce per step, after which every rank
@@ -295,6 +295,53 @@ class EpochShards:
     def __iter__(self):
         for chunk in self.global_batches():
             yield balanced_deal(chunk, self.lengths, self.world)[self.rank]
+
+
+class MixDraws:
+    """A batch sampler for a dataset whose index encodes the epoch (archs/uPIT.py DynMixTrainSet: item idx is a function of
+    (seed, idx) alone, idx = epoch * mixes_per_epoch + i): the batches of THIS rank for one epoch of dynamic mixing.
+
+    Epoch e owns the indices e N .. e N + N - 1, N = mixes_per_epoch.  They are cut, in order, into global batches of batch_size
+    consecutive indices, and batch k goes to rank k % world.  Every rank runs the SAME number of steps (the collectives inside a
+    step always match): the indices left after the last complete round of `world` batches are dealt to the ranks as `world`
+    consecutive, near-equal ranges (when fewer than `world` are left, the round before gives up its indices too, and the two
+    rounds are dealt as 2 world such ranges).  Every index of the epoch is therefore drawn exactly once over all ranks and no two
+    ranks draw the same one -- unless the epoch cannot fill the rounds at all (fewer mixtures than ranks, or batch_size 1 with a
+    remainder): a rank that would go without a batch is topped up from the start of the epoch's range, as EpochShards does.
+    The batches are a function of the epoch alone, so `--start-epoch N` continues exactly where an uninterrupted run would
+    be; there is no shuffling to seed (`seed` belongs to the dataset's draws and is kept here only to say which run these
+    batches are of)."""
+
+    def __init__(self, mixes_per_epoch, batch_size, rank_, world_, seed=0):
+        if mixes_per_epoch <= 0 or batch_size <= 0 or not 0 <= rank_ < world_:
+            raise ValueError("MixDraws: bad arguments")
+        self.n, self.bs, self.rank, self.world = int(mixes_per_epoch), int(batch_size), int(rank_), int(world_)
+        self.seed, self.epoch = int(seed), 0
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        g = self.bs * self.world
+        return (self.n + g - 1) // g
+
+    def global_batches(self):
+        """Per round, the `world` index lists of the ranks."""
+        base, g = self.epoch * self.n, self.bs * self.world
+        full, left = divmod(self.n, g)
+        if 0 < left < self.world and full > 0:       # too few for a round of their own: share the last complete round's
+            full, left = full - 1, left + g
+        for k in range(full):
+            yield [list(range(base + k * g + r * self.bs, base + k * g + (r + 1) * self.bs)) for r in range(self.world)]
+        parts = (len(self) - full) * self.world      # the rest, as consecutive near-equal ranges (none longer than batch_size)
+        cuts = [full * g + (left * j) // parts for j in range(parts + 1)] if parts else []
+        for k in range(len(self) - full):
+            yield [list(range(base + cuts[j], base + cuts[j + 1])) or [base + j % self.n]
+                   for j in range(k * self.world, (k + 1) * self.world)]
+
+    def __iter__(self):
+        for deal in self.global_batches():
+            yield deal[self.rank]
 
 
 def shard_indices_contiguous(n, rank_, world_):

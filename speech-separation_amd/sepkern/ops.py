@@ -426,6 +426,55 @@ def pcm_to_rate(flat, lengths, rates, target):
     return out, outs
 
 
+# ----------------------------------------------------------------------------- dynamic mixing
+def dynamic_mix(flat, src_offs, nsamp, amp, peak, quantize=False, out=None, repeat=1):
+    """Training mixtures made on the device from single-speaker signals in one launch (sk_dynamic_mix; sepkern/mixing.py defines
+    the arithmetic).  flat: ONE 1-D CUDA tensor of samples, float32 or int16 PCM (scaled by 1/32768 in-kernel); src_offs: S lists
+    (source 1 .. S) of B offsets into flat -- mixture u's source s is the nsamp[u] samples at src_offs[s][u], and signals may
+    overlap; amp: S lists of B linear amplitudes; peak: B target peaks.
+    -> (out_flat, gains): out_flat float32 in WavCollator's layout -- key-major ('mix', 'source1', ...), the utterances of every
+    key back to back in the order given, (S + 1) sum(nsamp) samples -- and gains (S, B), the final gain of every source.
+    quantize: every output sample lands on the int16 grid (clip(rint(32768 v)) / 32768).  out: a float32 buffer of that size to
+    write into."""
+    pcm16 = flat.dtype == torch.int16
+    _chk(flat, torch.int16 if pcm16 else torch.float32)
+    ns = [int(n) for n in nsamp]
+    B, dev = len(ns), flat.device
+    src_offs = [[int(o) for o in offs] for offs in src_offs]
+    S = len(src_offs)
+    if flat.dim() != 1 or not flat.is_contiguous() or B == 0 or min(ns) < 1:
+        raise _lib.SepkernError("dynamic_mix needs one contiguous 1-D tensor of samples and at least one mixture of at least one sample")
+    if not 1 <= S <= 4 or any(len(o) != B for o in src_offs):
+        raise _lib.SepkernError("dynamic_mix needs 1..4 lists of %d source offsets (got %d)" % (B, S))
+    if any(o < 0 or o + n > flat.numel() for offs in src_offs for o, n in zip(offs, ns)):
+        raise _lib.SepkernError("dynamic_mix: a source runs past the sample buffer")
+    amp = [[float(a) for a in row] for row in amp]
+    peak = [float(p) for p in peak]
+    if len(amp) != S or any(len(row) != B for row in amp) or len(peak) != B:
+        raise _lib.SepkernError("dynamic_mix needs one amplitude per source signal (%d x %d) and one peak per mixture" % (S, B))
+    total = sum(ns)
+    if out is None:
+        out = torch.empty((S + 1) * total, dtype=torch.float32, device=dev)
+    _chk(out)
+    if out.dim() != 1 or not out.is_contiguous() or out.numel() < (S + 1) * total:
+        raise _lib.SepkernError("dynamic_mix: out must be a contiguous 1-D float32 tensor of (S + 1) * sum(nsamp) samples")
+    starts, at = [], 0
+    for n in ns:
+        starts.append(at)
+        at += n
+    # descriptor arrays must outlive the (asynchronous) launch call: keep references until it returns
+    d64 = _i64([o for offs in src_offs for o in offs] + [q * total + st for q in range(S + 1) for st in starts], dev)
+    d_ns = torch.tensor(ns, dtype=torch.int32, device=dev)
+    d_f = torch.tensor([a for row in amp for a in row] + peak, dtype=torch.float32, device=dev)
+    gains = torch.empty(S, B, dtype=torch.float32, device=dev)
+    # algorithmic bytes: every input sample once, every output sample once
+    with _timed("dynamic_mix_kernel", repeat * float(total) * (S * (2 if pcm16 else 4) + (S + 1) * 4)):
+        for _ in range(repeat):
+            _lib.call("sk_dynamic_mix", _ptr(flat), int(pcm16), _ptr(d64), _ptr(d_ns), B, S, _ptr(d_f), _ptr(d_f[S * B:]),
+                      int(bool(quantize)), _ptr(out), _ptr(d64[S * B:]), _ptr(gains), _stream())
+    return out[:(S + 1) * total], gains
+
+
 def mask_istft_flat(mixcat, maskcat, Ts, S, want_pcm=True, want_float=True, repeat=1):
     """Mask-apply + iSTFT on buffers that crossed PCIe as ONE copy each: mixcat = the utterances' (257, T_u) complex64
     spectra back to back (flattened), maskcat = None or, per utterance and source (utterance-major), the (257, T_u) float32

@@ -22,7 +22,9 @@ What is organised differently here, on the host side only:
     and pack in parallel, a thread copies through pinned memory on its own stream, --prefetch batches deep): the
     reference inflates, packs and copies each batch synchronously in front of its step (:113-117), which at 36 ms per
     step is the bound.  --prefetch 0 --num-workers 1 is the reference's loop.  Every epoch's wall time and frames/s go
-    to stderr.
+    to stderr;
+  * --dynamic-mix (with --wav-input): the training mixtures are not files.  Every epoch draws them afresh from single-speaker
+    utterances and mixes them on the GPU (archs/uPIT.py DynMixTrainSet, sepkern.dist.MixDraws, sk_dynamic_mix).
 """
 import argparse
 import os
@@ -70,8 +72,42 @@ def get_args(argv=None):
   parser.add_argument("--sample-rate", type=int, default=None,
                       help="with --wav-input: the rate the network works at; wav files at another rate are resampled to it on "
                            "the GPU (sk_resample), as the reference's librosa.load(sr=) does.  Default: the files are taken as they are")
-  parser.add_argument("--seed", type=int, default=None, help="seed for weights, shuffling and h0/c0")
-  return parser.parse_args(argv)
+  parser.add_argument("--dynamic-mix", action="store_true",
+                      help="with --wav-input: <data-dir> lists single-speaker utterances (wav.scp + utt2spk) and every training "
+                           "mixture is drawn afresh each epoch -- partners, levels, crops -- and mixed on the GPU (sk_dynamic_mix; "
+                           "arch must provide DynMixTrainSet).  The validation set stays the fixed one of --cv-data-dir")
+  parser.add_argument("--mixes-per-epoch", type=int, default=None, help="with --dynamic-mix: mixtures per epoch (default: utterances / num_spk)")
+  parser.add_argument("--mix-snr-db", type=float, default=2.5,
+                      help="with --dynamic-mix: every source's level is uniform in +-this many dB (2.5: WSJ0-2mix's [-5, 5] dB between two speakers)")
+  parser.add_argument("--mix-peak", type=mix_peak, default=(0.9, 0.9), metavar="LO[,HI]",
+                      help="with --dynamic-mix: the largest magnitude of a mixture and its sources, uniform in [LO, HI]")
+  parser.add_argument("--mix-max-samples", type=int, default=0, help="with --dynamic-mix: crop mixtures to this many samples (0: whole utterances)")
+  parser.add_argument("--mix-quantize", action="store_true",
+                      help="with --dynamic-mix: round the mixed signals to the int16 grid, as a 16-bit wav file of them would hold them")
+  parser.add_argument("--seed", type=int, default=None, help="seed for weights, shuffling, mixture draws and h0/c0")
+  args = parser.parse_args(argv)
+  dynamic_mixing(args)
+  return args
+
+
+def mix_peak(text):
+  """--mix-peak LO[,HI] -> (lo, hi)."""
+  parts = [float(v) for v in text.split(',')]
+  if len(parts) not in (1, 2):
+    raise argparse.ArgumentTypeError("LO or LO,HI expected")
+  return (parts[0], parts[-1])
+
+
+NEEDS_WAV_INPUT = "`--dynamic-mix` needs `--wav-input`: the mixtures are made from waveforms on the GPU"
+
+
+def dynamic_mixing(args):
+  """True with --dynamic-mix.  The mixtures are made from waveforms: without --wav-input the run ends here, not at its first batch."""
+  if not getattr(args, "dynamic_mix", False):
+    return False
+  if not args.wav_input:
+    raise SystemExit(NEEDS_WAV_INPUT)
+  return True
 
 
 # ----------------------------------------------------------------------------------------------- files
@@ -169,10 +205,43 @@ def wav_train_set(m, args, data_dir):
   return m.WavTrainSet(data_dir, sample_rate=args.sample_rate)
 
 
+def mixing_seed(args, rank, world):
+  """The seed of --dynamic-mix's draws: --seed, or one drawn here -- once, by rank 0, for every rank -- and printed, so that the
+  run's mixtures can be had again."""
+  if args.seed is not None:
+    return args.seed
+  box = [int.from_bytes(os.urandom(4), "little") & 0x7fffffff]
+  if world > 1:
+    torch.distributed.broadcast_object_list(box, src=0)
+  if rank == 0:
+    print("dynamic mixing: the mixtures are drawn with seed %d" % box[0], flush=True)
+  return box[0]
+
+
+def dynamic_mix_batches(m, args, rank, world):
+  """--dynamic-mix: the arch's DynMixTrainSet over the single-speaker utterances of data_dir, num_spk from the model conf, and
+  MixDraws, whose batches are a function of the epoch alone (reseed_epoch calls its set_epoch)."""
+  from sepkern import dist as skdist
+  if not hasattr(m, "DynMixTrainSet"):
+    raise SystemExit("--dynamic-mix: the arch %s provides no DynMixTrainSet" % getattr(m, "__name__", m))
+  seed = mixing_seed(args, rank, world)
+  dataset = m.DynMixTrainSet(args.data_dir, int(read_model_conf(args.model_config).get('num_spk', 2)),
+                             mixes_per_epoch=args.mixes_per_epoch, snr_db=args.mix_snr_db, peak=args.mix_peak,
+                             max_samples=args.mix_max_samples, seed=seed, sample_rate=getattr(args, "sample_rate", None),
+                             quantize=args.mix_quantize)
+  draws = skdist.MixDraws(dataset.mixes_per_epoch, args.batch_size, rank, world, seed=seed)
+  workers = loader_workers(args, world)
+  extra = dict(persistent_workers=True, prefetch_factor=2) if workers > 0 else {}
+  loader = DataLoader(dataset, batch_sampler=draws, collate_fn=dataset.collator, num_workers=workers, **extra)
+  return staged(loader, args), draws
+
+
 def training_batches(m, args, rank, world):
   """DataLoader over this rank's share of the training set, and the sampler to re-seed per epoch (or None).
-  One process: the reference's shuffled loader (steps/train_qsub.py:80-81).  Several: EpochShards."""
+  One process: the reference's shuffled loader (steps/train_qsub.py:80-81).  Several: EpochShards.  --dynamic-mix: MixDraws."""
   from sepkern import dist as skdist
+  if dynamic_mixing(args):
+    return dynamic_mix_batches(m, args, rank, world)
   dataset = wav_train_set(m, args, args.data_dir) if args.wav_input else m.TrainSet(args.data_dir, args.train_copy_location)
   seed = args.seed if args.seed is not None else 0
   workers = loader_workers(args, world)
