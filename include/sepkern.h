@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 137
+#define SK_VERSION 138
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -592,6 +592,25 @@ int sk_bss_xcorr(const double* ref, const double* est, const int64_t* offs_host,
                  int taps, void* ws, double* xc, sk_stream_t stream);
 int sk_bss_eval(const double* ref, const double* est, const int64_t* offs_host, const int32_t* lens_host, int U, int S,
                 int taps, void* ws, double* out, int32_t* status, sk_stream_t stream);
+
+/* ---------------------------------------------------------------- STOI (scoring)
+ * Short-time objective intelligibility (Taal et al. 2011) and its extended form ESTOI (Jensen & Taal 2016) as
+ * sepkern/stoi.py defines them, for a batch of U utterances of S sources each: silent-frame removal decided by each
+ * reference (fp64 frame energies, 40 dB), 15 one-third-octave band envelopes of the rebuilt signals (the 512-point FFT of the
+ * STFT front end, fp32), and the correlations over segments of 30 frames (fp64).
+ * ref / est: packed fp32 rows at 10 kHz in sk_bss_eval's layout: utterance u has length lens_host[u] and its source (or
+ * estimate) i starts at element offs_host[u] + i*lens_host[u] of ref (est).  offs_host / lens_host are HOST arrays, copied into
+ * the workspace on `stream`.  1 <= S <= 4, 1 <= lengths <= 2^24, 1 <= U <= 2^20.
+ * out (U, S, S, 2) fp64: [u][k][j] = STOI, ESTOI of estimate k against reference j (under reference j's kept frames).
+ * frames (U, S) int32: T of reference j, the frames left after silent-frame removal minus one; T < 30 gives 1e-5 for both
+ * scores.  A signal without a frame (length <= 256) or an all-zero reference gives T = 0 and 1e-5: no error.
+ * Every score is computed in one fixed order of operations by workgroups that see its own utterance alone: no atomics,
+ * bitwise reproducible, independent of the batch.
+ * ws >= sk_stoi_workspace_bytes(U, S, max_u lens_host[u]) (0 for arguments out of range).  Bad arguments return SK_EINVAL
+ * before anything is launched. */
+size_t sk_stoi_workspace_bytes(int U, int S, int max_len);
+int sk_stoi(const float* ref, const float* est, const int64_t* offs_host, const int32_t* lens_host, int U, int S, void* ws,
+            double* out, int32_t* frames, sk_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -7,5 +7,6 @@
     synth    WSJ0-2mix-shaped synthetic data (wav trees, id lists, HBM-resident batches)
     sisdr    SI-SDR scoring
     bsseval_gpu  batched BSS Eval SDR / SIR / SAR on the device (bsseval: the host function)
+    stoi_gpu     batched STOI / ESTOI on the device (stoi: the definition and the host function)
 """
 from ._lib import SepkernError, load  # noqa: F401

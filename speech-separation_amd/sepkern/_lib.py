@@ -21,7 +21,7 @@ BUILD_FLAG_NAMES = {0x1: "TIMING_ONLY (wrong results by construction)", 0x2: "AR
 def build_flag_names(mask):
     return [n for b, n in sorted(BUILD_FLAG_NAMES.items()) if mask & b] + (["unknown 0x%x" % (mask & ~0xf)] if mask & ~0xf else [])
 
-SK_VERSION = 137
+SK_VERSION = 138
 
 _p, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 
@@ -87,6 +87,8 @@ PROTOTYPES = {
     "sk_bss_workspace_bytes": (_sz, [_i, _i, _i]),
     "sk_bss_xcorr": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "sk_bss_eval": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "sk_stoi_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sk_stoi": (_i, [_p, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
 }
 
 _lib = None

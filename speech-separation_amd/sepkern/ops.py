@@ -1131,3 +1131,28 @@ def bss_eval(ref, est, offs, lens, S, taps):
         _lib.call("sk_bss_eval", _ptr(ref), _ptr(est), h_offs, h_lens, U, S, taps, _ptr(ws), _ptr(out), _ptr(status),
                   _stream())
     return out, status
+
+
+# ----------------------------------------------------------------------------- STOI / ESTOI scoring
+def stoi(ref, est, offs, lens, S):
+    """STOI and ESTOI of every (estimate k, reference j) pair of packed fp32 rows at 10 kHz (sk_bss_eval's layout: utterance
+    u's source / estimate i starts at offs[u] + i*lens[u]): returns (out (U, S, S, 2) fp64, frames (U, S) int32: the T of
+    reference j; T < 30 -> 1e-5).  The definition is sepkern/stoi.py's (include/sepkern.h "STOI")."""
+    _chk(ref)
+    _chk(est)
+    if ref.shape != est.shape or ref.dim() != 1 or not ref.is_contiguous() or not est.is_contiguous():
+        raise _lib.SepkernError("stoi: ref and est must be contiguous 1-D fp32 tensors of one length (packed rows)")
+    offs = [int(o) for o in offs]
+    lens = [int(n) for n in lens]
+    if len(offs) != len(lens) or not lens or any(o + S * n > ref.numel() for o, n in zip(offs, lens)):
+        raise _lib.SepkernError("stoi: offsets / lengths run past the packed rows")
+    U = len(lens)
+    h_offs = (C.c_int64 * U)(*offs)
+    h_lens = (C.c_int32 * U)(*lens)
+    nbytes = _lib.load().sk_stoi_workspace_bytes(U, S, max(lens))
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=ref.device)
+    out = torch.empty(U, max(S, 0), max(S, 0), 2, dtype=torch.float64, device=ref.device)
+    frames = torch.empty(U, max(S, 0), dtype=torch.int32, device=ref.device)
+    with _timed("stoi"):
+        _lib.call("sk_stoi", _ptr(ref), _ptr(est), h_offs, h_lens, U, S, _ptr(ws), _ptr(out), _ptr(frames), _stream())
+    return out, frames

@@ -9,7 +9,8 @@ clip(|S_i| cos(theta_i - theta_M) / |M|, 0, 1) of sepkern/psa.py, its numerator 
 (sk_mask_istft), then the score: BSS Eval SDR / SIR / SAR without permutation search (the reference calls
 mir_eval's bss_eval_sources with compute_permutation=False, steps/evaluate_oracle.py:118,143; here
 sepkern/bsseval.py) into {session,source}_{SDR,SIR,SAR}s.txt + *_stats.txt under
-<data-dir>/oracle_{soft,hard,psm}_mask_eval/, and SI-SDR under its own SISDR names.
+<data-dir>/oracle_{soft,hard,psm}_mask_eval/, and SI-SDR under its own SISDR names.  With --stoi also STOI and ESTOI
+(sepkern/stoi.py, without permutation search; with --gpu in the same batches, sk_stoi) under STOI / ESTOI names.
 """
 import argparse
 import glob
@@ -35,6 +36,8 @@ def get_args(argv=None):
   parser.add_argument("--sample-rate", type=int, help="Audio sample rate", default=8000)
   parser.add_argument("--gpu", action='store_true', default=False,
                       help="Score BSS Eval in batches on the GPU (sepkern/bsseval_gpu.py); SI-SDR stays on the host")
+  parser.add_argument("--stoi", action='store_true', default=False,
+                      help="Also write STOI and ESTOI (sepkern/stoi.py); with --gpu they are scored on the GPU in the same batches")
   parser.add_argument("--batch", type=int, default=256, help="Utterances per GPU batch (with --gpu)")
   return parser.parse_args(argv)
 
@@ -52,7 +55,7 @@ def main(argv=None):
   from evaluate_sources import MetricFiles
   dir_out = args.data_dir + ("/oracle_hard_mask_eval/" if args.hard_mask else "/oracle_psm_mask_eval/" if args.psm else "/oracle_soft_mask_eval/")
   os.makedirs(dir_out, exist_ok=True)
-  out = {m: MetricFiles(dir_out, m) for m in ("SDR", "SIR", "SAR", "SISDR")}
+  out = {m: MetricFiles(dir_out, m) for m in ("SDR", "SIR", "SAR", "SISDR") + (("STOI", "ESTOI") if args.stoi else ())}
   pending = []                                    # --gpu: (id, device fp32 estimates, device references: int16 PCM, or float32 once resampled)
 
   def host_ref(t):
@@ -60,7 +63,13 @@ def main(argv=None):
     x = t.cpu().numpy().astype(np.float64)
     return x / 32768.0 if t.dtype == torch.int16 else x
 
-  def write(reco_id, ests, refs, sdr, sir, sar):
+  def write(reco_id, ests, refs, sdr, sir, sar, intel=None):
+    if args.stoi:
+      if intel is None:
+        from sepkern.stoi import stoi_sources
+        intel = stoi_sources(refs, ests, args.sample_rate, compute_permutation=False)
+      out["STOI"].add(reco_id, intel[0])
+      out["ESTOI"].add(reco_id, intel[1])
     out["SDR"].add(reco_id, sdr)
     out["SIR"].add(reco_id, sir)
     out["SAR"].add(reco_id, sar)
@@ -75,8 +84,12 @@ def main(argv=None):
     scores = bss_eval_sources_batch(refs, ests, compute_permutation=False)
     if scores.n_fallback:
       print("evaluate_oracle.py: %d utterance(s) re-scored on the host" % scores.n_fallback, file=sys.stderr)
-    for (reco_id, _, _), e, r, (sdr, sir, sar, _) in zip(pending, ests, refs, scores):
-      write(reco_id, e.cpu().numpy().astype(np.float64), host_ref(r), sdr, sir, sar)
+    intel = [None] * len(pending)
+    if args.stoi:
+      from sepkern.stoi_gpu import stoi_batch
+      intel = stoi_batch(refs, ests, args.sample_rate, compute_permutation=False)
+    for (reco_id, _, _), e, r, (sdr, sir, sar, _), it in zip(pending, ests, refs, scores, intel):
+      write(reco_id, e.cpu().numpy().astype(np.float64), host_ref(r), sdr, sir, sar, it)
     pending.clear()
 
   with open(args.data_dir + "/wav.scp", 'r') as listF:

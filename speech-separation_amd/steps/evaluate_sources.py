@@ -10,6 +10,9 @@ steps/evaluate_sources.py (:36-110), so that run_eval.sh:88-93 finds results/SDR
       additionally: scale-invariant SDR (Le Roux et al. 2019) under its best permutation and its improvement over
       the unprocessed mixture -- the metric BASELINE.json's +-0.1 dB parity gate names.  Never mixed into the
       SDR files.
+  results/{session,source}_{STOI,ESTOI}s.txt, results/{STOI,ESTOI}_stats.txt
+      with --stoi: short-time objective intelligibility (Taal et al. 2011) and its extended form (Jensen & Taal 2016) under
+      the assignment with the highest mean STOI (sepkern/stoi.py; with --gpu in the BSS Eval batches, sk_stoi).
 Off the hot path: numpy on the host.  Reference and mixture wavs at another rate than the estimates' (--sample-rate) are
 resampled to it first, on the GPU (sk_resample) -- the estimates were made from resampled mixtures.
 """
@@ -33,6 +36,8 @@ def get_args(argv=None):
   parser.add_argument("exp_dir", metavar="exp-dir", type=str, help="Experiment directory")
   parser.add_argument("--gpu", action='store_true', default=False,
                       help="Score BSS Eval in batches on the GPU (sepkern/bsseval_gpu.py); SI-SDR stays on the host")
+  parser.add_argument("--stoi", action='store_true', default=False,
+                      help="Also write STOI and ESTOI (sepkern/stoi.py); with --gpu they are scored on the GPU in the same batches")
   parser.add_argument("--batch", type=int, default=256, help="Utterances per GPU batch (with --gpu)")
   parser.add_argument("--sample-rate", type=int, default=None,
                       help="Rate the estimates were written at (default: read from the first estimate's header); reference "
@@ -109,7 +114,7 @@ def main(argv=None):
   num_src = {k: int(v) for k, v in read_pairs(args.data_dir + "/utt2num_spk")}
   results = args.exp_dir + "/results"
   os.makedirs(results, exist_ok=True)
-  out = {m: MetricFiles(results, m) for m in ("SDR", "SIR", "SAR", "SISDR", "SISDRi")}
+  out = {m: MetricFiles(results, m) for m in ("SDR", "SIR", "SAR", "SISDR", "SISDRi") + (("STOI", "ESTOI") if args.stoi else ())}
   rate = [args.sample_rate]                       # the estimates' rate: references and mixtures are brought to it
 
   def load(utt_id, mix_wav):
@@ -132,6 +137,10 @@ def main(argv=None):
     out["SISDR"].add(utt_id, si)
     out["SISDRi"].add(utt_id, [v - si_sdr(mix, refs[s]) for s, v in enumerate(si)])
 
+  def write_stoi(utt_id, score):
+    out["STOI"].add(utt_id, score[0])
+    out["ESTOI"].add(utt_id, score[1])
+
   pairs = read_pairs(args.data_dir + "/wav.scp")
   if args.gpu:
     from sepkern.bsseval_gpu import bss_eval_sources_batch
@@ -145,6 +154,10 @@ def main(argv=None):
       fallbacks += scores.n_fallback
       for (utt_id, mix_wav), (refs, ests, n), (sdr, sir, sar, _) in zip(chunk, loaded, scores):
         write(utt_id, mix_wav, refs, ests, n, sdr, sir, sar)
+      if args.stoi:
+        from sepkern.stoi_gpu import stoi_batch
+        for (utt_id, _), score in zip(chunk, stoi_batch([l[0] for l in loaded], [l[1] for l in loaded], rate[0])):
+          write_stoi(utt_id, score)
     if fallbacks:
       print("evaluate_sources.py: %d utterance(s) re-scored on the host (Gram matrix not factored on the GPU)" % fallbacks,
             file=sys.stderr)
@@ -153,6 +166,9 @@ def main(argv=None):
       refs, ests, n = load(utt_id, mix_wav)
       sdr, sir, sar, _ = bss_eval_sources(refs, ests)
       write(utt_id, mix_wav, refs, ests, n, sdr, sir, sar)
+      if args.stoi:
+        from sepkern.stoi import stoi_sources
+        write_stoi(utt_id, stoi_sources(refs, ests, rate[0]))
   for files in out.values():
     files.close()
 
