@@ -1,6 +1,6 @@
 // sisdr.hip -- utterance-level PIT on the SI-SDR of time-domain estimates: the statistics and the finalize step
 // (include/sepkern.h "SI-SDR uPIT loss").  The estimates come from sk_mask_istft_rows, the gradient
-// goes back through sk_sisdr_mask_grad (both in stft.hip, beside the FFT they share).
+// goes back through sk_sisdr_mask_grad (both in stft.hip, on the FFT of fft512.h).
 //
 // One streaming pass reads every estimate and every reference sample once and forms, per utterance, the plain sums
 //   sum e_k, sum r_i, sum e_k^2, sum r_i^2, sum e_k r_i        (4 S + S^2 values)

@@ -1,5 +1,5 @@
 """Short-time objective intelligibility: STOI (Taal, Hendriks, Heusdens & Jensen 2011) and its extended form ESTOI
-(Jensen & Taal 2016), defined once.  The kernels (csrc/stft.hip, sk_stoi) and the scoring CLIs compute exactly this.
+(Jensen & Taal 2016), defined once.  The kernels (csrc/stoi.hip, sk_stoi) and the scoring CLIs compute exactly this.
 
 UNPINNED: neither pystoi nor any other implementation is installed where this project is built, and the reference project has
 none, so everything below restates the two papers (and the authors' Matlab framing rule), not a package's output -- exactly as

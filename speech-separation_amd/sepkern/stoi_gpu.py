@@ -1,5 +1,5 @@
 """STOI / ESTOI for a batch of utterances on the GPU: the numbers of sepkern/stoi.py, computed by libsepkern's kernels
-(csrc/stft.hip, sk_stoi; include/sepkern.h "STOI").  Signals at another rate than 10 kHz go through sk_resample first."""
+(csrc/stoi.hip, sk_stoi; include/sepkern.h "STOI").  Signals at another rate than 10 kHz go through sk_resample first."""
 import numpy as np
 import torch
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time of the STOI / ESTOI kernels (csrc/stft.hip, sk_stoi) against the host function (sepkern/stoi.py).
+"""Time of the STOI / ESTOI kernels (csrc/stoi.hip, sk_stoi) against the host function (sepkern/stoi.py).
 
 For a batch of 256 two-speaker utterances of 4 s at 10 kHz (sepkern/synth.py sources, estimates = source + 0.2 other + noise):
   - us per batch of the device-resident call (ops.stoi on packed fp32 rows), HIP events around `reps` calls;

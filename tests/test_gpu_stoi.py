@@ -1,4 +1,4 @@
-"""sk_stoi on the MI355X (csrc/stft.hip; sepkern/stoi_gpu.py; evaluate_sources.py --stoi) against the definition in
+"""sk_stoi on the MI355X (csrc/stoi.hip; sepkern/stoi_gpu.py; evaluate_sources.py --stoi) against the definition in
 sepkern/stoi.py.
 
 The gate is computed here, never fixed: g = 4 x the largest |stoi_host(dtype=float32) - stoi_host(dtype=float64)| over the
