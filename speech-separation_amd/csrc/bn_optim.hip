@@ -6,6 +6,7 @@
 // included); clip_grad_norm_(0.25) + Adam.step() at steps/train_qsub.py:121-122.
 // Every reduction is a fixed-order two-level sum (per-block partials, then one finalize block),
 // so results are reproducible run to run.
+// Shape coverage: tests/test_gpu_streaming.py runs every kernel here at the sizes its loop bounds name, against fp64.
 #include "sk_common.h"
 
 namespace {

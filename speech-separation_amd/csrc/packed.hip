@@ -12,6 +12,7 @@
 //            layout the shift was a constant B rows; packed, it is n_{t-1} / n_t rows and varies with t).
 // `perm` (B entries or NULL): sorted position j holds the caller's utterance perm[j] (callers whose padded
 // batch is not length-sorted).
+// Shape coverage: tests/test_gpu_streaming.py runs every kernel here at the sizes its loop bounds name, against fp64.
 #include "sk_common.h"
 
 namespace {

@@ -10,6 +10,7 @@
 // Row layouts: padded time-major (row of (t, b) = t*B + b, zeros past an utterance's end) or, with an offset table
 // `offs` (T+1 entries), PACKED rows exactly as torch's PackedSequence.data holds them (archs/uPIT.py:46,167: row of
 // (t, b) = offs[t] + b for t < lens[b], lens sorted descending) -- the layout the reference's collator produces.
+// Shape coverage: tests/test_gpu_streaming.py runs every kernel here at the sizes its loop bounds name, against fp64.
 #include "sk_common.h"
 
 namespace {

@@ -7,6 +7,7 @@
 //   update (archs/RSH.py:254-257 train, :278-281 test): combos = relu(combos - [0 | mask])
 //          (no relu at test time); combos = [mixture | attention], (T,B,2F).
 // Streaming, HBM-bound; fixed-order reductions (no atomics).
+// Shape coverage: tests/test_gpu_streaming.py runs every kernel here at the sizes its loop bounds name, against fp64.
 #include "sk_common.h"
 
 namespace {

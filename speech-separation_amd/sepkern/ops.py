@@ -61,6 +61,14 @@ def _chk(t, dtype=torch.float32):
         raise _lib.SepkernError("expected dtype %s, got %s" % (dtype, t.dtype))
 
 
+def _dense(what, *ts):
+    """The wrappers below pass shape[1] as the row stride: a view with any other stride would be read wrong."""
+    for t in ts:
+        _chk(t)
+        if not t.is_contiguous():
+            raise _lib.SepkernError("%s needs contiguous tensors (got strides %s for shape %s)" % (what, tuple(t.stride()), tuple(t.shape)))
+
+
 def workspace(nbytes, tag="default"):
     """A cached per-(device, tag) scratch buffer of at least nbytes (owned by torch's allocator)."""
     key = (torch.cuda.current_device(), tag)
@@ -823,6 +831,7 @@ def bn_ws(R, Ccols, tag="bn"):
 def bn_stats(x2d, mean, var, rows=None, count=None):
     """mean / biased variance per column over `count` rows of which the first `rows` of x2d are stored and the rest are
     zero rows that are not (packed sequences: count = B * T_max); defaults: all of x2d's rows, count = rows."""
+    _dense("bn_stats", x2d, mean, var)
     R, Cc = x2d.shape
     R = R if rows is None else rows
     _lib.call("sk_bn_stats", _ptr(x2d), R, Cc, int(R if count is None else count), _ptr(mean), _ptr(var), _ptr(bn_ws(R, Cc)),
@@ -836,6 +845,7 @@ def bn_update_running(mean, var, rmean, rvar, count, momentum, guard=None):
 
 
 def bn_apply(x2d, mean, var, gamma, beta, out, eps):
+    _dense("bn_apply", x2d, mean, var, gamma, beta, out)
     R, Cc = x2d.shape
     _lib.call("sk_bn_apply", _ptr(x2d), _ptr(mean), _ptr(var), _ptr(gamma), _ptr(beta), _ptr(out), R, Cc, float(eps),
               _stream())
@@ -865,18 +875,21 @@ def bn_unfold_grad(G, dzsum, s, t, dW, accumulate=False):
 
 
 def bn_bwd(dout, x2d, mean, var, gamma, dx, dgamma, dbeta, eps):
+    _dense("bn_bwd", dout, x2d, mean, var, gamma, dx, dgamma, dbeta)
     R, Cc = x2d.shape
     _lib.call("sk_bn_bwd", _ptr(dout), _ptr(x2d), _ptr(mean), _ptr(var), _ptr(gamma), _ptr(dx), _ptr(dgamma),
               _ptr(dbeta), _ptr(bn_ws(R, Cc)), R, Cc, float(eps), _stream())
 
 
 def bn_bwd_sums(dout, x2d, mean, var, dgamma, dbeta, eps):
+    _dense("bn_bwd_sums", dout, x2d, mean, var, dgamma, dbeta)
     R, Cc = x2d.shape
     _lib.call("sk_bn_bwd_sums", _ptr(dout), _ptr(x2d), _ptr(mean), _ptr(var), _ptr(dgamma), _ptr(dbeta),
               _ptr(bn_ws(R, Cc)), R, Cc, float(eps), _stream())
 
 
 def bn_bwd_apply(dout, x2d, mean, var, gamma, dgamma, dbeta, dx, count, eps):
+    _dense("bn_bwd_apply", dout, x2d, mean, var, gamma, dgamma, dbeta, dx)
     R, Cc = x2d.shape
     _lib.call("sk_bn_bwd_apply", _ptr(dout), _ptr(x2d), _ptr(mean), _ptr(var), _ptr(gamma), _ptr(dgamma), _ptr(dbeta),
               _ptr(dx), R, Cc, float(count), float(eps), _stream())
@@ -929,6 +942,7 @@ def hprev_rows(y2d, h0, pk, H, out):
 
 
 def sigmoid_bwd(dmask, m, dz):
+    _dense("sigmoid_bwd", dmask, m, dz)
     _lib.call("sk_sigmoid_bwd", _ptr(dmask), _ptr(m), _ptr(dz), dmask.numel(), _stream())
 
 
