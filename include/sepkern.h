@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 138
+#define SK_VERSION 139
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -102,6 +102,26 @@ int sk_resample(const void* in, int pcm16, const int64_t* in_offs, const int32_t
 int sk_dynamic_mix(const void* in, int pcm16, const int64_t* in_offs, const int32_t* nsamp, int B, int S,
                    const float* amp, const float* peak, int quantize,
                    float* out, const int64_t* out_offs, float* gains, sk_stream_t stream);
+
+/* ---------------------------------------------------------------- room impulse responses (reverberant dynamic mixing)
+ * Convolves J signals with room impulse responses in one call; sepkern/reverb.py defines the result and restates the
+ * arithmetic in numpy float32.  Job j: the nsamp[j] samples x at in + in_offs[j] (elements; float32, or int16 PCM scaled by
+ * 1/32768 when pcm16 != 0, as sk_dynamic_mix takes them) and the ntaps[j] float32 taps h at rir + rir_offs[j]:
+ *   out[out_offs[j] + i] = sum_{k < ntaps[j]} h[k] x[i + delay[j] - k],  0 <= i < nsamp[j],  x = 0 outside [0, nsamp[j])
+ * i.e. np.convolve(x, h)[delay : delay + nsamp]: the output keeps the signal's length, and delay = the index of the direct path
+ * keeps it aligned with the dry signal.  Exactly nsamp[j] floats are written per job.  Jobs may share a signal or a RIR.
+ * Uniformly partitioned overlap-save, partitions of 256 taps, 512-point real transforms (the STFT front end's FFT), fp32: launch
+ * one writes every job's partition and block spectra to ws, launch two accumulates each output block's spectrum over the
+ * partitions in ascending order, inverts and stores.  No atomics, no hand-off between workgroups, one summation order: a
+ * job's bits depend neither on the batch around it nor on the run, and int16 samples give the bits of their float32 copies.
+ * The job arrays (names ending in _host) are HOST arrays, copied into the workspace on `stream`: the grids and the workspace
+ * layout depend on them.  1 <= J <= 65535, 1 <= ntaps <= 8192, 0 <= delay < ntaps, 1 <= nsamp <= 2^30, offsets >= 0; at most
+ * 2^31 - 1 transforms per call.  ws >= sk_fir_workspace_bytes(...) (0 for arguments out of range).  Bad arguments return
+ * SK_EINVAL before anything is launched. */
+size_t sk_fir_workspace_bytes(const int32_t* nsamp_host, const int32_t* ntaps_host, const int32_t* delay_host, int J);
+int sk_fir_convolve(const void* in, int pcm16, const int64_t* in_offs_host, const int32_t* nsamp_host, const float* rir,
+                    const int64_t* rir_offs_host, const int32_t* ntaps_host, const int32_t* delay_host, int J, void* ws,
+                    float* out, const int64_t* out_offs_host, sk_stream_t stream);
 
 /* ---------------------------------------------------------------- mask-apply + iSTFT back end
  * Replaces np.multiply(mix_spec, mask) + librosa.core.istft(hop_length=128) + (*32767).astype(int16)

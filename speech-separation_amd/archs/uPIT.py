@@ -30,7 +30,9 @@ Beyond the reference (all optional, defaults reproduce it):
     (sk_stft_psa).  It needs waveforms too -- or npz features written by steps/extract_feats.py --psa-targets, which train
     with the default loss=mse.  compute_loss returns what it returns for 'mse'.
   * DynMixTrainSet / DynMixCollator (steps/train_qsub.py --dynamic-mix): training mixtures drawn afresh every epoch from
-    single-speaker utterances and mixed on the GPU (sk_dynamic_mix); every loss above trains on them.
+    single-speaker utterances and mixed on the GPU (sk_dynamic_mix); every loss above trains on them.  With rir_scp / rir_synth
+    (--mix-rir-scp / --mix-rir-synth) every source is first convolved with a room impulse response, also on the GPU
+    (sk_fir_convolve; sepkern/reverb.py): reverberant mixtures, reverberant sources as targets.
 """
 import itertools
 import os
@@ -215,10 +217,18 @@ class DynMixTrainSet(Dataset):
   range) and a peak uniform in [peak[0], peak[1]].  Persistent loader workers therefore never need to be told the epoch, and a
   restarted run draws what the uninterrupted one would have.
   -> {'source1': int16[n], ..., 'amp': [10^(snr_s / 20)], 'peak': p} (+ 'rate' with sample_rate: the files' rate; the batch is
-  resampled on the GPU in front of the mixing, and lengths, max_samples and the 257-sample limit count at sample_rate)."""
+  resampled on the GPU in front of the mixing, and lengths, max_samples and the 257-sample limit count at sample_rate).
+
+  Reverberation (rir_scp or rir_synth; sepkern/reverb.py): every source is convolved ON THE GPU (sk_fir_convolve) with a room
+  impulse response before the levels are set, so an item also carries 'rir1' .. 'rir<S>' (float32 taps) and 'rir_delay' (the
+  index of each direct path: the reverberant source stays aligned with the dry one).  Each source independently, with
+  probability rir_prob: a RIR drawn uniformly from rir_scp (lines `<rir-id> <path>` of mono 16-bit wav or 1-D float npy files at
+  the working rate, read once, here), or synthesised with t60 ~ U(rir_synth) seconds and a direct-to-reverberant ratio ~
+  U(rir_drr_db) dB; otherwise the identity [1.0].  These draws come from a generator of their own, seeded (seed, idx, 1): draw(idx)
+  and everything else an item carries are bit for bit what they are without reverberation."""
 
   def __init__(self, datadir, num_spk, mixes_per_epoch=None, snr_db=2.5, peak=(0.9, 0.9), max_samples=0, seed=0, sample_rate=None,
-               quantize=False):
+               quantize=False, rir_scp=None, rir_synth=None, rir_drr_db=(0.0, 15.0), rir_prob=1.0):
     import wave
     self.num_spk, self.seed = int(num_spk), int(seed)
     self.snr_db, self.peak, self.max_samples = float(snr_db), (float(peak[0]), float(peak[1])), int(max_samples)
@@ -258,6 +268,45 @@ class DynMixTrainSet(Dataset):
       raise ValueError("DynMixTrainSet: mixes_per_epoch must be at least 1")
     self.longest = max(n for u in self.speakers for _, n in u)
     self.collator = DynMixCollator(self.sample_rate, quantize)
+    self._init_reverb(rir_scp, rir_synth, rir_drr_db, rir_prob)
+
+  def _init_reverb(self, rir_scp, rir_synth, rir_drr_db, rir_prob):
+    self.rirs, self.rir_synth, self.rir_prob = None, None, float(rir_prob)
+    self.rir_drr_db = (float(rir_drr_db[0]), float(rir_drr_db[1]))
+    self.rir_rate = self.sample_rate if self.sample_rate is not None else self.rate      # the rate the convolution runs at
+    if rir_scp and rir_synth:
+      raise ValueError("DynMixTrainSet: rir_scp and rir_synth are two sources of RIRs; give one of them")
+    if not 0.0 <= self.rir_prob <= 1.0 or self.rir_drr_db[0] > self.rir_drr_db[1]:
+      raise ValueError("DynMixTrainSet: 0 <= rir_prob <= 1 and rir_drr_db[0] <= rir_drr_db[1] expected")
+    if rir_scp:
+      from sepkern.reverb import MAX_TAPS, read_rir_scp
+      self.rirs, cut = read_rir_scp(rir_scp, self.rir_rate)
+      if cut:
+        print("DynMixTrainSet: %d of the %d RIRs of %s are longer than %d taps and were cut to that" % (cut, len(self.rirs), rir_scp, MAX_TAPS))
+    elif rir_synth:
+      self.rir_synth = (float(rir_synth[0]), float(rir_synth[1]))
+      if not 0.0 < self.rir_synth[0] <= self.rir_synth[1] or int(round(self.rir_synth[0] * self.rir_rate)) < 1:
+        raise ValueError("DynMixTrainSet: rir_synth = (lo, hi) seconds of T60 with 0 < lo <= hi, at least one tap long")
+    self.reverb = self.rirs is not None or self.rir_synth is not None
+
+  def draw_rirs(self, idx):
+    """The RIRs of item idx, from a generator of their own: ([float32 taps per source], [delay per source])."""
+    from sepkern.reverb import direct_delay, synthetic_rir
+    rng = np.random.default_rng([self.seed, int(idx), 1])
+    rirs, delays = [], []
+    for _ in range(self.num_spk):
+      if rng.random() >= self.rir_prob:
+        rirs.append(np.ones(1, dtype=np.float32))
+        delays.append(0)
+        continue
+      if self.rirs is not None:
+        h = self.rirs[int(rng.integers(len(self.rirs)))]
+      else:
+        t60, drr = float(rng.uniform(*self.rir_synth)), float(rng.uniform(*self.rir_drr_db))
+        h = synthetic_rir(rng, t60, self.rir_rate, drr)
+      rirs.append(h)
+      delays.append(direct_delay(h))
+    return rirs, delays
 
   def _at_rate(self, n):
     """Samples once at sample_rate (sepkern/resample.py's length rule)."""
@@ -302,6 +351,10 @@ class DynMixTrainSet(Dataset):
     out['peak'] = peak
     if self.sample_rate is not None:
       out['rate'] = int(self.rate)
+    if self.reverb:
+      rirs, out['rir_delay'] = self.draw_rirs(idx)
+      for s, h in enumerate(rirs):
+        out['rir' + str(s + 1)] = h
     return out
 
 
@@ -344,6 +397,20 @@ class DynMixCollator():
     if rates is not None:
       pcm['rate'] = [rates[i] for i in order]
       pcm['target_rate'] = self.sample_rate
+    if any('rir1' in d for d in batch):    # reverberant items: every source's RIR, source-major in the batch's order, as ONE tensor
+      S = len(keys)
+      if any(any('rir' + str(s + 1) not in d for s in range(S)) or len(d.get('rir_delay', ())) != S for d in batch):
+        raise ValueError("DynMixCollator: a reverberant item carries 'rir1' .. 'rir<S>' and one 'rir_delay' per source, and so does every item of its batch")
+      rirs = [[np.asarray(batch[i]['rir' + str(s + 1)], dtype=np.float32) for i in order] for s in range(S)]
+      offs, at = [], 0
+      for row in rirs:
+        offs.append([])
+        for h in row:
+          offs[-1].append(at)
+          at += len(h)
+      pcm['reverb'] = {'flat': torch.from_numpy(np.concatenate([h for row in rirs for h in row])), 'offs': offs,
+                       'taps': [[int(len(h)) for h in row] for row in rirs],
+                       'delay': [[int(batch[i]['rir_delay'][s]) for i in order] for s in range(S)]}
     return {'pcm': pcm}
 
 

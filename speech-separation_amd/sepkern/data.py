@@ -67,6 +67,9 @@ def mixed_pcm(pcm, dev):
   sepkern/mixing.py states the rule) -> an ordinary pcm dict ON the device: 'flat' float32 in WavCollator's layout, 'keys' =
   ['mix', 'source1', ...], 'lens', no 'rate'.  One pinned H2D copy of the samples.  With 'rate' / 'target_rate' and an utterance
   at another rate the sources are resampled first (ops.pcm_to_rate) and a mixture is as long as its shortest resampled source.
+  With 'reverb' = {'flat': float32 tensor of all RIRs, 'offs' / 'taps' / 'delay': [S][B]} every source is then convolved with its
+  RIR (ops.fir_convolve: one sk_fir_convolve call over the S B signals; sepkern/reverb.py) and the levels are set on the
+  reverberant signals: the targets are the reverberant sources.  A batch without 'reverb' takes the path it took before.
   The front ends below start with this and go on as they do for a batch that came mixed from disk; enqueued on the CURRENT
   stream."""
   import torch
@@ -88,6 +91,18 @@ def mixed_pcm(pcm, dev):
     ends = [sum(outs[:k]) for k in range(len(outs))]
     offs = [ends[s * len(ns):(s + 1) * len(ns)] for s in range(S)]
     ns = [min(outs[s * len(ns) + j] for s in range(S)) for j in range(len(ns))]
+  rv = pcm.get('reverb')
+  if rv is not None:      # reverberant sources: ONE sk_fir_convolve launch pair over all S B signals; the levels are set on its result
+    rirs = rv['flat']
+    if rirs.device != torch.device(dev):
+      rirs = (rirs if rirs.is_pinned() else rirs.pin_memory()).to(dev, non_blocking=True)
+    B = len(ns)
+    dry = flat
+    flat, at = ops.fir_convolve(dry, [o for row in offs for o in row], ns * S, rirs, [o for row in rv['offs'] for o in row],
+                                [t for row in rv['taps'] for t in row], [d for row in rv['delay'] for d in row])
+    offs = [at[s * B:(s + 1) * B] for s in range(S)]
+    dry.record_stream(torch.cuda.current_stream(dev))
+    rirs.record_stream(torch.cuda.current_stream(dev))
   out, _ = ops.dynamic_mix(flat, offs, ns, mixing['amp'], mixing['peak'], quantize=bool(mixing.get('quantize', False)))
   src.record_stream(torch.cuda.current_stream(dev))
   flat.record_stream(torch.cuda.current_stream(dev))

@@ -483,6 +483,46 @@ def dynamic_mix(flat, src_offs, nsamp, amp, peak, quantize=False, out=None, repe
     return out[:(S + 1) * total], gains
 
 
+# ----------------------------------------------------------------------------- room impulse responses
+def fir_convolve(flat, in_offs, ns, rir_flat, rir_offs, taps, delay, repeat=1):
+    """Signals convolved with room impulse responses in one call (sk_fir_convolve; sepkern/reverb.py defines the result).  flat:
+    ONE 1-D CUDA tensor of samples, float32 or int16 PCM (scaled by 1/32768 in-kernel); job j: the ns[j] samples at in_offs[j]
+    with the taps[j] float32 taps at rir_offs[j] of rir_flat (1-D CUDA float32), at delay[j] in [0, taps[j]) -- jobs may share a
+    signal or a RIR.  -> (out, offsets): out float32, the jobs' ns[j] output samples back to back, job j's at offsets[j]."""
+    pcm16 = flat.dtype == torch.int16
+    _chk(flat, torch.int16 if pcm16 else torch.float32)
+    _chk(rir_flat)
+    in_offs, ns, rir_offs, taps, delay = ([int(v) for v in a] for a in (in_offs, ns, rir_offs, taps, delay))
+    J = len(ns)
+    if flat.dim() != 1 or rir_flat.dim() != 1 or not flat.is_contiguous() or not rir_flat.is_contiguous():
+        raise _lib.SepkernError("fir_convolve: samples and RIRs must be contiguous 1-D tensors")
+    if J == 0 or not (len(in_offs) == len(rir_offs) == len(taps) == len(delay) == J):
+        raise _lib.SepkernError("fir_convolve: one offset, length, RIR offset, tap count and delay per job")
+    if any(o < 0 or n < 1 or o + n > flat.numel() for o, n in zip(in_offs, ns)) or \
+            any(o < 0 or t < 1 or o + t > rir_flat.numel() for o, t in zip(rir_offs, taps)):
+        raise _lib.SepkernError("fir_convolve: a signal or a RIR runs past its buffer (or is empty)")
+    out_offs, at = [], 0
+    for n in ns:
+        out_offs.append(at)
+        at += n
+    h_in, h_rir, h_out = (C.c_int64 * J)(*in_offs), (C.c_int64 * J)(*rir_offs), (C.c_int64 * J)(*out_offs)
+    h_ns, h_taps, h_delay = (C.c_int32 * J)(*ns), (C.c_int32 * J)(*taps), (C.c_int32 * J)(*delay)
+    nbytes = _lib.load().sk_fir_workspace_bytes(h_ns, h_taps, h_delay, J)
+    if nbytes == 0:
+        raise _lib.SepkernError("fir_convolve: 1..65535 jobs of 1..8192 taps, 0 <= delay < taps and 1..2^30 samples (sk_fir_workspace_bytes refused the jobs)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=flat.device)
+    out = torch.empty(at, dtype=torch.float32, device=flat.device)
+    # 5 N log2 N per 512-point transform (N = 512) and 8 flops per bin and partition product
+    nb = [(d + n - 1) // 256 - d // 256 + 1 for n, d in zip(ns, delay)]
+    kk = [-(-t // 256) for t in taps]
+    flops = sum(5.0 * 512 * 9 * (k + 2 * b) + 8.0 * 257 * k * b for k, b in zip(kk, nb))
+    with _timed("fir_convolve", repeat * flops):
+        for _ in range(repeat):
+            _lib.call("sk_fir_convolve", _ptr(flat), int(pcm16), h_in, h_ns, _ptr(rir_flat), h_rir, h_taps, h_delay, J, _ptr(ws),
+                      _ptr(out), h_out, _stream())
+    return out, out_offs
+
+
 def mask_istft_flat(mixcat, maskcat, Ts, S, want_pcm=True, want_float=True, repeat=1):
     """Mask-apply + iSTFT on buffers that crossed PCIe as ONE copy each: mixcat = the utterances' (257, T_u) complex64
     spectra back to back (flattened), maskcat = None or, per utterance and source (utterance-major), the (257, T_u) float32

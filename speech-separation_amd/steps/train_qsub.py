@@ -24,7 +24,9 @@ What is organised differently here, on the host side only:
     step is the bound.  --prefetch 0 --num-workers 1 is the reference's loop.  Every epoch's wall time and frames/s go
     to stderr;
   * --dynamic-mix (with --wav-input): the training mixtures are not files.  Every epoch draws them afresh from single-speaker
-    utterances and mixes them on the GPU (archs/uPIT.py DynMixTrainSet, sepkern.dist.MixDraws, sk_dynamic_mix).
+    utterances and mixes them on the GPU (archs/uPIT.py DynMixTrainSet, sepkern.dist.MixDraws, sk_dynamic_mix).  With
+    --mix-rir-scp or --mix-rir-synth every source is first convolved with a room impulse response, also on the GPU
+    (sk_fir_convolve, sepkern/reverb.py): the mixtures are reverberant and the targets are the reverberant sources.
 """
 import argparse
 import os
@@ -84,6 +86,14 @@ def get_args(argv=None):
   parser.add_argument("--mix-max-samples", type=int, default=0, help="with --dynamic-mix: crop mixtures to this many samples (0: whole utterances)")
   parser.add_argument("--mix-quantize", action="store_true",
                       help="with --dynamic-mix: round the mixed signals to the int16 grid, as a 16-bit wav file of them would hold them")
+  parser.add_argument("--mix-rir-scp", type=str, default=None, metavar="FILE",
+                      help="with --dynamic-mix: lines of `<rir-id> <path>`: room impulse responses (mono 16-bit wav at the working rate "
+                           "-- --sample-rate, or the corpus's --, or 1-D float npy); every source is convolved with one of them on the "
+                           "GPU (sk_fir_convolve) before the mixture is made")
+  parser.add_argument("--mix-rir-synth", type=rir_synth, default=None, metavar="LO,HI",
+                      help="with --dynamic-mix: synthetic room impulse responses in place of --mix-rir-scp, T60 uniform in [LO, HI] seconds")
+  parser.add_argument("--mix-rir-prob", type=float, default=None, metavar="P",
+                      help="with --mix-rir-scp / --mix-rir-synth: the probability that a source is reverberant (default 1.0)")
   parser.add_argument("--seed", type=int, default=None, help="seed for weights, shuffling, mixture draws and h0/c0")
   args = parser.parse_args(argv)
   dynamic_mixing(args)
@@ -98,15 +108,42 @@ def mix_peak(text):
   return (parts[0], parts[-1])
 
 
+def rir_synth(text):
+  """--mix-rir-synth LO,HI -> (lo, hi) seconds of T60."""
+  parts = [float(v) for v in text.split(',')]
+  if len(parts) != 2 or not 0.0 < parts[0] <= parts[1]:
+    raise argparse.ArgumentTypeError("LO,HI with 0 < LO <= HI expected")
+  return (parts[0], parts[1])
+
+
 NEEDS_WAV_INPUT = "`--dynamic-mix` needs `--wav-input`: the mixtures are made from waveforms on the GPU"
+NEEDS_DYNAMIC_MIX = "`%s` needs `--dynamic-mix`: room impulse responses are applied to the sources of mixtures made on the GPU"
+ONE_RIR_SOURCE = "`--mix-rir-scp` and `--mix-rir-synth` are two sources of room impulse responses: give one of them"
+
+
+def reverb_options(args):
+  """The --mix-rir-* options that were given, as DynMixTrainSet's keyword arguments ({} without any)."""
+  given = {"rir_scp": getattr(args, "mix_rir_scp", None), "rir_synth": getattr(args, "mix_rir_synth", None),
+           "rir_prob": getattr(args, "mix_rir_prob", None)}
+  return {k: v for k, v in given.items() if v is not None}
 
 
 def dynamic_mixing(args):
-  """True with --dynamic-mix.  The mixtures are made from waveforms: without --wav-input the run ends here, not at its first batch."""
+  """True with --dynamic-mix.  The mixtures are made from waveforms: without --wav-input the run ends here, not at its first batch;
+  so does a run with a --mix-rir-* option and no --dynamic-mix, or with both sources of RIRs."""
+  rir = reverb_options(args)
   if not getattr(args, "dynamic_mix", False):
+    if rir:
+      raise SystemExit(NEEDS_DYNAMIC_MIX % ("--mix-" + sorted(rir)[0].replace("_", "-")))
     return False
   if not args.wav_input:
     raise SystemExit(NEEDS_WAV_INPUT)
+  if "rir_scp" in rir and "rir_synth" in rir:
+    raise SystemExit(ONE_RIR_SOURCE)
+  if "rir_prob" in rir and len(rir) == 1:
+    raise SystemExit("`--mix-rir-prob` needs `--mix-rir-scp` or `--mix-rir-synth`: there is no room impulse response to apply")
+  if "rir_prob" in rir and not 0.0 <= rir["rir_prob"] <= 1.0:
+    raise SystemExit("`--mix-rir-prob` is a probability: 0 <= P <= 1")
   return True
 
 
@@ -228,7 +265,7 @@ def dynamic_mix_batches(m, args, rank, world):
   dataset = m.DynMixTrainSet(args.data_dir, int(read_model_conf(args.model_config).get('num_spk', 2)),
                              mixes_per_epoch=args.mixes_per_epoch, snr_db=args.mix_snr_db, peak=args.mix_peak,
                              max_samples=args.mix_max_samples, seed=seed, sample_rate=getattr(args, "sample_rate", None),
-                             quantize=args.mix_quantize)
+                             quantize=args.mix_quantize, **reverb_options(args))      # (an arch without RIRs is given none)
   draws = skdist.MixDraws(dataset.mixes_per_epoch, args.batch_size, rank, world, seed=seed)
   workers = loader_workers(args, world)
   extra = dict(persistent_workers=True, prefetch_factor=2) if workers > 0 else {}
