@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 139
+#define SK_VERSION 140
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -528,6 +528,44 @@ int sk_sisdr_pit_fwd(const float* est, const int64_t* est_offs, const void* ref,
 int sk_sisdr_mask_grad(const float* est, const int64_t* est_offs, const void* ref, int pcm16, const int64_t* ref_offs,
                        const int32_t* nframes, const int32_t* best_perm, const float* coef, const float* gscale,
                        const void* mix_rows_c64, const int32_t* offs, int B, int S, int n_fft, int hop, int max_frames,
+                       float* dmask, int ld, sk_stream_t stream);
+
+/* ---------------------------------------------------------------- mixture-invariant loss (waveform domain, loss=mixit)
+ * Unsupervised training (MixIT, Wisdom et al., NeurIPS 2020): the training mixture is the sum of TWO recordings x_0, x_1, the
+ * network emits M masks, 2 <= M <= 4, and the loss asks only that SOME assignment of the M time-domain estimates
+ * e_k = istft(mask_k * STFT(mix)) to the two recordings sums to them.  No counterpart in the reference; sepkern/mixit.py states
+ * the definition and restates the arithmetic below in numpy fp64.  The estimates are sk_mask_istft_rows' (above, S = M).
+ *
+ * sk_mixit_fwd: est as sk_mask_istft_rows wrote it (est_offs[j*M + k]); reference n of utterance j = nsamp[j] samples at
+ *   ref + ref_offs[j*2 + n] (elements; float32, or int16 PCM scaled by 1/32768 when pcm16 != 0); nsamp[j] = L_j samples of both
+ *   are read.  From the plain sums P_n = sum x_n^2, c_nk = sum x_n e_k, G_kl = sum e_k e_l (no mean removal; fp64, fixed order,
+ *   no atomics: bitwise reproducible, and an utterance's numbers do not depend on what else is in the batch), for every code
+ *   a in [0, 2^M) -- bit k of a = the reference that estimate k is added to; every code is legal, an empty group included --
+ *     err_n(a)   = max(P_n - 2 sum_{k in n} c_nk + sum_{k,l in n} G_kl, 0)          (= |x_n - sum_{k in n} e_k|^2)
+ *     score_n(a) = 10 log10((P_n + eps) / (err_n(a) + tau P_n + eps)) dB,  eps = 1e-30,  tau = 10^(-snr_max / 10)
+ *     assign_score (2^M,B): assign_score[a][j] = (score_0(a) + score_1(a)) / 2;   best_code (B) = argMAX (first maximum)
+ *     out[0] = loss = -(1/count) sum_j best score, out[1] = count, out[2] = sum_j best score;  count = B, or count_dev[0]
+ *              (device scalar, may be NULL: the GLOBAL utterance count of a data-parallel step)
+ *     coef (B,2): D_0, D_1 of d loss / d e_k[t] = D_n (m_n[t] - x_n[t]), n = bit k of the best code, m_n = sum_{l in n} e_l:
+ *              D_n = kappa / (count (err_n + tau P_n + eps)), kappa = 10/ln 10; 0 where err_n + tau P_n <= 0 (a silent
+ *              reference met exactly): never NaN or Inf.
+ *   max_samples >= max_j nsamp[j] sizes the grid; ws >= sk_mixit_workspace_bytes(B, M, max_samples) (0 for bad arguments). */
+size_t sk_mixit_workspace_bytes(int B, int M, int max_samples);
+int sk_mixit_fwd(const float* est, const int64_t* est_offs, const void* ref, int pcm16, const int64_t* ref_offs,
+                 const int32_t* nsamp, int B, int M, int max_samples, const float* count_dev, double tau,
+                 float* assign_score, int32_t* best_code, float* out, float* coef, void* ws, sk_stream_t stream);
+/* sk_mixit_mask_grad: dmask = gscale[0] * d loss / d mask, as sk_sisdr_mask_grad takes its gradient back (one kernel: the
+ *   adjoint of mask-apply + iSTFT is a forward STFT of the gradient signal).  The signal is the SAME for every estimate of a
+ *   group, so ONE transform per (utterance, reference n) serves the column blocks of all members:
+ *   g_n[p] = D_n gscale (sum_{l in n} e_l[t] - x_n[t]) / wss[p] at p = t + n_fft/2, t in [0, L_j), zero elsewhere (the member
+ *   sum in fp32, l ascending from the first member), framed WITHOUT reflection, U_n its windowed transform,
+ *     dmask[offs[t] + j][k*257 + f] = (c_f / n_fft) (Re X[t][f] Re U_n[t][f] + Im X[t][f] Im U_n[t][f])  for every k in group n,
+ *   c_f = 1 for f in {0, 256}, else 2, X = mix_rows_c64.  An empty group launches no work.  The groups partition the estimates:
+ *   every column < M*257 of every row offs[t] + j, t < T_j, is written exactly once, by one lane; nothing else is written
+ *   (dmask (>= R, ld >= M*257)).  The column blocks of one group hold the same bits. */
+int sk_mixit_mask_grad(const float* est, const int64_t* est_offs, const void* ref, int pcm16, const int64_t* ref_offs,
+                       const int32_t* nframes, const int32_t* best_code, const float* coef, const float* gscale,
+                       const void* mix_rows_c64, const int32_t* offs, int B, int M, int n_fft, int hop, int max_frames,
                        float* dmask, int ld, sk_stream_t stream);
 
 /* ---------------------------------------------------------------- phase-sensitive uPIT targets (loss=psa / tpsa)

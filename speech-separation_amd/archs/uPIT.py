@@ -29,6 +29,11 @@ Beyond the reference (all optional, defaults reproduce it):
     |S_s| cos(theta_s - theta_mix) in place of |S_s| ('tpsa': held to [0, |mix|]), made from the waveforms by one kernel
     (sk_stft_psa).  It needs waveforms too -- or npz features written by steps/extract_feats.py --psa-targets, which train
     with the default loss=mse.  compute_loss returns what it returns for 'mse'.
+    'mixit': mixture-invariant training (Wisdom et al. 2020; sepkern/mixit.py, include/sepkern.h "mixture-invariant loss"):
+    the batch's mixture is the sum of TWO recordings, 'source1' and 'source2', the network emits num_spk = M masks, 2..4, and
+    the best of the 2^M assignments of the M time-domain estimates to the two recordings is scored (SNR with the soft
+    threshold of conf key mixit_snr_max, default 30 dB).  No isolated sources are needed.  It needs waveforms;
+    compute_loss returns (mean negative score per utterance in dB, number of utterances).
   * DynMixTrainSet / DynMixCollator (steps/train_qsub.py --dynamic-mix): training mixtures drawn afresh every epoch from
     single-speaker utterances and mixed on the GPU (sk_dynamic_mix); every loss above trains on them.  With rir_scp / rir_synth
     (--mix-rir-scp / --mix-rir-synth) every source is first convolved with a room impulse response, also on the GPU
@@ -436,13 +441,15 @@ class _PitFn(torch.autograd.Function):
 
 LOSSES = ('mse', 'sisdr', 'psa', 'tpsa')
 PSA_LOSSES = ('psa', 'tpsa')       # PIT-MSE on phase-sensitive targets (sepkern/psa.py); 'tpsa' holds them to [0, |mix|]
+MIXIT_LOSSES = ('mixit',)          # mixture-invariant training (sepkern/mixit.py): num_spk masks against the TWO mixed recordings
+WAVE_LOSSES = ('sisdr',) + MIXIT_LOSSES      # computed from the batch's waveforms (the driver keeps them with the staged batch)
 
 
 def parse_loss(value):
-  """The conf key `loss`: 'mse' (default), 'sisdr', 'psa' or 'tpsa'."""
+  """The conf key `loss`: 'mse' (default), 'sisdr', 'psa', 'tpsa' or 'mixit'."""
   value = str(value).strip().lower()
-  if value not in LOSSES:
-    raise ValueError("conf key loss: %r is not one of %s" % (value, " / ".join(repr(v) for v in LOSSES)))
+  if value not in LOSSES + MIXIT_LOSSES:
+    raise ValueError("conf key loss: %r is not one of %s" % (value, " / ".join(repr(v) for v in LOSSES + MIXIT_LOSSES)))
   return value
 
 
@@ -477,12 +484,39 @@ class _SisdrFn(torch.autograd.Function):
     return dmask, None, None, None, None, None
 
 
+class _MixitFn(torch.autograd.Function):
+  """out = [-mean_j best MixIT score, count, sum_j best score] from the packed mask rows: mask-apply + iSTFT of the M
+  estimates, the sums and the search over the 2^M assignments forward; the group gradients and the iSTFT's adjoint fused in
+  one kernel backward (one transform per utterance and reference)."""
+
+  @staticmethod
+  def forward(ctx, mask, pk, wave, desc, count_dev, M, tau):
+    est, est_offs, _ = ops.mask_istft_rows(wave['mixc'], mask, pk, M, est_offs=desc['est_offs'])
+    ref_offs = desc['ref_offs']
+    res = ops.mixit_fwd(est, est_offs, wave['flat'], ref_offs, desc['nsamp'], M, 128 * (pk.T - 1), tau, count_dev)
+    ctx.save_for_backward(est, est_offs, ref_offs, res["best_code"], res["coef"], wave['mixc'], wave['flat'])
+    ctx.pk, ctx.M, ctx.shape = pk, M, tuple(mask.shape)
+    ctx.mark_non_differentiable(res["best_code"])
+    return res["out"], res["best_code"]
+
+  @staticmethod
+  def backward(ctx, gout, _gcode):
+    est, est_offs, ref_offs, best, coef, mixc, flat = ctx.saved_tensors
+    dmask = torch.empty(ctx.shape, dtype=torch.float32, device=est.device)
+    dmask[ctx.pk.R:].zero_()               # tail rows of an (Rp, .) buffer stay zero
+    ops.mixit_mask_grad(est, est_offs, flat, ref_offs, best, coef, gout[0:1].contiguous(), mixc, ctx.pk, ctx.M, out=dmask)
+    return dmask, None, None, None, None, None, None
+
+
 class SepDNN(SepDNNBase):
   def __init__(self, gpuid, **kwargs):
     super(SepDNN, self).__init__()
     self.feat_dim = int(kwargs.get('feat_dim', 257))
     self.num_spk = int(kwargs.get('num_spk', 2))
     self.loss_kind = parse_loss(kwargs.get('loss', 'mse'))
+    self.mixit_snr_max = float(kwargs.get('mixit_snr_max', 30.0))     # dB, read by loss=mixit only (sepkern/mixit.py: tau)
+    if self.loss_kind in MIXIT_LOSSES and not 2 <= self.num_spk <= 4:
+      raise ValueError("loss=mixit: num_spk = %d estimates per mixture is outside 2..4" % self.num_spk)
     for key in kwargs.keys():
       print('modelparam:', key, kwargs[key])
     # the reference hard-codes 2 x 600 (archs/uPIT.py:115-119); hidden_dim / num_layers widen it
@@ -586,6 +620,34 @@ def compute_loss_wave(model, mix, pk, wave):
   return out[0], out[1].detach()
 
 
+def compute_loss_mixit(model, mix, pk, wave):
+  """The loss=mixit route: mix (R,F) packed magnitude rows (the network's input), wave as wave_features_from_pcm made it, with
+  exactly the two mixed recordings as 'source1' and 'source2'; the network's num_spk = M masks are the estimates.
+  Returns (mean negative MixIT score per utterance in dB, number of utterances)."""
+  M = model.num_spk
+  if not 2 <= M <= 4:
+    raise ValueError("loss=mixit: num_spk = %d estimates per mixture is outside 2..4" % M)
+  have = sorted(k for k in wave['sig_offs'] if k != 'mix')
+  missing = [k for k in ('source1', 'source2') if k not in have]
+  if missing:
+    raise ValueError("loss=mixit: the batch holds no waveform %s (the two mixed recordings are the references)" % ", ".join(missing))
+  if have != ['source1', 'source2']:
+    raise ValueError("loss=mixit: the batch holds the waveforms %s; the references are exactly source1 and source2 "
+                     "(num_spk = %d counts the masks)" % (", ".join(have), M))
+  model.zero_grad()
+  model.hidden = model.init_hidden(pk.B)
+  # data-parallel: divide by the GLOBAL utterance count (None = single process: the kernel uses B), while training only
+  training_step = model.training and torch.is_grad_enabled()
+  count = skdist.global_norm(pk.lens.new_full((1,), pk.B), 1) if training_step else None
+  desc = ops.mixit_descriptors(pk, wave['sig_offs'], M)       # (uploaded before the network is enqueued, not behind it)
+  mask_out = model.forward_packed(mix, pk)
+  tau = 10.0 ** (-float(getattr(model, 'mixit_snr_max', 30.0)) / 10.0)
+  out, best = _MixitFn.apply(mask_out, pk, wave, desc, count, M, tau)
+  model.last_best_code = best.detach()      # arg-max assignment per utterance: bit k = the reference estimate k is added to
+  model.step_frames = pk.R                  # (the norm counts utterances: the driver's frames/s line reads this)
+  return out[0], out[1].detach()
+
+
 def compute_loss_padded(model, mix, sources, lens, plotdir=""):
   """compute_loss on zero-padded time-major inputs resident on the GPU: mix (T,B,F), sources [(T,B,F)]*S float32,
   lens int32 (B) in any order.  They are packed (sk_pack_rows; a view when all lengths are equal) and go the packed way."""
@@ -618,14 +680,14 @@ def compute_loss(model, epoch, batch_sample, plotdir=""):
     if len(targets) < model.num_spk:
       raise ValueError("loss=%s: the batch holds %d source waveforms (num_spk = %d)" % (kind, len(targets), model.num_spk))
     return compute_loss_packed(model, mix, targets[:model.num_spk], pk, plotdir)
-  if kind == 'sisdr':
+  if kind in WAVE_LOSSES:
     if 'pcm' in batch_sample:
       mix, _, pk, wave = _wave_features_from_pcm(batch_sample['pcm'], dev, source_mags=False)
     elif 'packed' in batch_sample and 'wave' in batch_sample:     # staged by Prefetcher(keep_wave=True)
       (mix, _, pk), wave = batch_sample['packed'], batch_sample['wave']
     else:                                                         # npz feature batches hold magnitudes only
-      raise ValueError(NEEDS_WAVEFORMS)
-    return compute_loss_wave(model, mix, pk, wave)
+      raise ValueError(needs_waveforms(kind))
+    return compute_loss_mixit(model, mix, pk, wave) if kind in MIXIT_LOSSES else compute_loss_wave(model, mix, pk, wave)
   if 'pcm' in batch_sample:        # WavTrainSet batches: features are computed on the GPU
     mix, sources, pk = _features_from_pcm(batch_sample['pcm'], dev)
     return compute_loss_packed(model, mix, sources[:model.num_spk], pk, plotdir)

@@ -6,6 +6,7 @@
     optim    fused clip_grad_norm_ + Adam over the flat buffers
     synth    WSJ0-2mix-shaped synthetic data (wav trees, id lists, HBM-resident batches)
     sisdr    SI-SDR scoring
+    mixit    the mixture-invariant training loss (loss=mixit), stated once in numpy fp64
     bsseval_gpu  batched BSS Eval SDR / SIR / SAR on the device (bsseval: the host function)
     stoi_gpu     batched STOI / ESTOI on the device (stoi: the definition and the host function)
 """

@@ -753,6 +753,85 @@ def sisdr_mask_grad(est, est_offs, ref, ref_offs, best_perm, coef, gscale, mixc,
     return out
 
 
+# ----------------------------------------------------------------------------- mixture-invariant loss (waveform domain)
+MIXIT_NREF = 2
+
+
+def mixit_descriptors(pk, sig_offs, M):
+    """The small device tables of one batch's mixture-invariant loss, uploaded in one go BEFORE the network runs: est_offs (B*M)
+    int64 as mask_istft_rows lays the M estimates out, ref_offs (B*2) int64 from sig_offs = {'source1' / 'source2': [offset of
+    utterance j]}, nsamp (B) int32 = 128 (T_j - 1)."""
+    offsets, _ = _est_offsets(pk, M)
+    refs = [int(sig_offs["source%d" % (n + 1)][j]) for j in range(pk.B) for n in range(MIXIT_NREF)]
+    both = _i64(offsets + refs, pk.device)
+    return dict(est_offs=both[:pk.B * M], ref_offs=both[pk.B * M:], nsamp=(pk.lens - 1) * 128)
+
+
+def mixit_fwd(est, est_offs, ref, ref_offs, nsamp, M, max_samples, tau, count_dev=None, repeat=1):
+    """The mixture-invariant loss (sk_mixit_fwd; sepkern/mixit.py defines it).  est: flat float32 estimates at est_offs (int64
+    device, B*M: j * M + k); ref: flat references, float32 or int16 PCM (scaled by 1/32768), reference n of utterance j at
+    ref_offs[j * 2 + n]; nsamp int32 device (B): samples per utterance; tau = 10^(-snr_max/10); count_dev: optional device
+    scalar replacing B (the global utterance count under data parallelism) ->
+    dict(out (3,) = [-mean best score, count, sum of best scores], assign_score (2^M,B) dB, best_code (B), coef (B,2))."""
+    _chk(est)
+    pcm16 = ref.dtype == torch.int16
+    _chk(ref, torch.int16 if pcm16 else torch.float32)
+    _chk(est_offs, torch.int64)
+    _chk(ref_offs, torch.int64)
+    _chk(nsamp, torch.int32)
+    _chk(count_dev)
+    B = int(nsamp.numel())
+    if est_offs.numel() != B * M or ref_offs.numel() != B * MIXIT_NREF:
+        raise _lib.SepkernError("mixit_fwd: need B*M estimate offsets and B*2 reference offsets")
+    dev = est.device
+    score = torch.empty(1 << M, B, device=dev)
+    best = torch.empty(B, dtype=torch.int32, device=dev)
+    out = torch.empty(3, device=dev)
+    coef = torch.empty(B, MIXIT_NREF, device=dev)
+    ws = workspace(_lib.load().sk_mixit_workspace_bytes(B, M, int(max_samples)), "mixit")
+    # algorithmic bytes: every estimate and both reference samples once
+    nref = float(est.numel()) / M * MIXIT_NREF
+    with _timed("mixit_fwd", repeat * (float(est.numel()) * 4 + nref * (2 if pcm16 else 4))):
+        for _ in range(repeat):
+            _lib.call("sk_mixit_fwd", _ptr(est), _ptr(est_offs), _ptr(ref), int(pcm16), _ptr(ref_offs), _ptr(nsamp), B, M,
+                      int(max_samples), _ptr(count_dev), float(tau), _ptr(score), _ptr(best), _ptr(out), _ptr(coef), _ptr(ws),
+                      _stream())
+    return dict(out=out, assign_score=score, best_code=best, coef=coef)
+
+
+def mixit_mask_grad(est, est_offs, ref, ref_offs, best_code, coef, gscale, mixc, pk, M, ld=None, out=None, repeat=1):
+    """dmask (Rp, ld) = gscale * d loss / d mask of the mixture-invariant loss (sk_mixit_mask_grad): one transform per
+    (utterance, reference) whose result lands in the column block of every estimate of that reference's group.  Rows of the
+    batch's frames are written, columns < M*257; the tail rows of a fresh buffer are zeroed; `out` (>= R rows) is written in
+    place and otherwise left alone."""
+    pcm16 = ref.dtype == torch.int16
+    _chk(est)
+    _chk(ref, torch.int16 if pcm16 else torch.float32)
+    _chk(mixc, torch.complex64)
+    _chk(gscale)
+    _chk(coef)
+    _chk(best_code, torch.int32)
+    _chk(est_offs, torch.int64)
+    _chk(ref_offs, torch.int64)
+    if est_offs.numel() != pk.B * M or ref_offs.numel() != pk.B * MIXIT_NREF or best_code.numel() != pk.B or coef.numel() != pk.B * MIXIT_NREF:
+        raise _lib.SepkernError("mixit_mask_grad: need B*M estimate offsets, B*2 reference offsets and coefficients, B codes")
+    if out is None:
+        ld = M * 257 if ld is None else int(ld)
+        out = torch.empty(pk.Rp, ld, dtype=torch.float32, device=est.device)
+        if pk.Rp > pk.R:
+            out[pk.R:].zero_()
+    _chk(out)
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < pk.R or mixc.shape[0] < pk.R or not mixc.is_contiguous():
+        raise _lib.SepkernError("mixit_mask_grad: dmask / mixture rows do not cover the batch")
+    # algorithmic bytes per frame: M + 1 x 128 new samples and the mixture's complex row per reference at most, M x 257 gradients out
+    with _timed("mixit_bwd", repeat * float(pk.R) * (128 * (4 * M + MIXIT_NREF * (2 if pcm16 else 4)) + MIXIT_NREF * 257 * 8 + M * 257 * 4)):
+        for _ in range(repeat):
+            _lib.call("sk_mixit_mask_grad", _ptr(est), _ptr(est_offs), _ptr(ref), int(pcm16), _ptr(ref_offs), _ptr(pk.lens),
+                      _ptr(best_code), _ptr(coef), _ptr(gscale), _ptr(mixc), _ptr(pk.offs), pk.B, M, 512, 128, pk.T, _ptr(out),
+                      int(out.stride(0)), _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- phase-sensitive targets (loss=psa / tpsa)
 def stft_psa(flat, sig_offs, nsamp, S, pk=None, clamp=False, out=None, repeat=1):
     """The network's input and the phase-sensitive targets of a batch of waveforms in one launch (sk_stft_psa; sepkern/psa.py

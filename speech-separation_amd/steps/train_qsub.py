@@ -26,7 +26,10 @@ What is organised differently here, on the host side only:
   * --dynamic-mix (with --wav-input): the training mixtures are not files.  Every epoch draws them afresh from single-speaker
     utterances and mixes them on the GPU (archs/uPIT.py DynMixTrainSet, sepkern.dist.MixDraws, sk_dynamic_mix).  With
     --mix-rir-scp or --mix-rir-synth every source is first convolved with a room impulse response, also on the GPU
-    (sk_fir_convolve, sepkern/reverb.py): the mixtures are reverberant and the targets are the reverberant sources.
+    (sk_fir_convolve, sepkern/reverb.py): the mixtures are reverberant and the targets are the reverberant sources;
+  * conf key loss=mixit (with --wav-input): mixture-invariant training on recordings without isolated sources
+    (sepkern/mixit.py).  With --dynamic-mix every example is a mixture of TWO recordings, whatever num_spk (the number of
+    masks, 2..4) is; fixed files mix / source1 / source2 with mix = source1 + source2 work too (the validation pass).
 """
 import argparse
 import os
@@ -78,7 +81,7 @@ def get_args(argv=None):
                       help="with --wav-input: <data-dir> lists single-speaker utterances (wav.scp + utt2spk) and every training "
                            "mixture is drawn afresh each epoch -- partners, levels, crops -- and mixed on the GPU (sk_dynamic_mix; "
                            "arch must provide DynMixTrainSet).  The validation set stays the fixed one of --cv-data-dir")
-  parser.add_argument("--mixes-per-epoch", type=int, default=None, help="with --dynamic-mix: mixtures per epoch (default: utterances / num_spk)")
+  parser.add_argument("--mixes-per-epoch", type=int, default=None, help="with --dynamic-mix: mixtures per epoch (default: utterances / num_spk; utterances / 2 with loss=mixit)")
   parser.add_argument("--mix-snr-db", type=float, default=2.5,
                       help="with --dynamic-mix: every source's level is uniform in +-this many dB (2.5: WSJ0-2mix's [-5, 5] dB between two speakers)")
   parser.add_argument("--mix-peak", type=mix_peak, default=(0.9, 0.9), metavar="LO[,HI]",
@@ -210,14 +213,25 @@ def read_model_conf(path):
 
 
 def waveform_loss(m, args):
-  """True when the conf file selects a loss that works on waveforms (archs/uPIT.py: loss=sisdr).  Such a loss cannot be
-  computed from npz magnitude features: without --wav-input the run ends here, not at its first batch."""
+  """True when the conf file selects a loss that works on waveforms (archs/uPIT.py: loss=sisdr, loss=mixit).  Such a loss
+  cannot be computed from npz magnitude features: without --wav-input the run ends here, not at its first batch."""
   if not hasattr(m, "parse_loss"):
     return False
   kind = m.parse_loss(read_model_conf(args.model_config).get('loss', 'mse'))
-  if kind == 'sisdr' and not args.wav_input:
-    raise SystemExit(m.NEEDS_WAVEFORMS)
-  return kind == 'sisdr'
+  wave = kind in getattr(m, "WAVE_LOSSES", ('sisdr',))
+  if wave and not args.wav_input:
+    raise SystemExit(m.needs_waveforms(kind))
+  return wave
+
+
+def mixed_recordings(m, args):
+  """How many recordings --dynamic-mix draws per training example: num_spk from the model conf -- except with loss=mixit, whose
+  example is always a mixture of TWO recordings (the references), whatever number of masks num_spk asks the network for.  The
+  "speaker" of utt2spk is then whatever must not be mixed with itself: a session, a room, a channel."""
+  conf = read_model_conf(args.model_config)
+  if hasattr(m, "parse_loss") and m.parse_loss(conf.get('loss', 'mse')) in getattr(m, "MIXIT_LOSSES", ()):
+    return 2
+  return int(conf.get('num_spk', 2))
 
 
 def prefetch_targets(m, args):
@@ -256,13 +270,14 @@ def mixing_seed(args, rank, world):
 
 
 def dynamic_mix_batches(m, args, rank, world):
-  """--dynamic-mix: the arch's DynMixTrainSet over the single-speaker utterances of data_dir, num_spk from the model conf, and
-  MixDraws, whose batches are a function of the epoch alone (reseed_epoch calls its set_epoch)."""
+  """--dynamic-mix: the arch's DynMixTrainSet over the single-speaker utterances of data_dir, num_spk from the model conf (two
+  recordings with loss=mixit: mixed_recordings), and MixDraws, whose batches are a function of the epoch alone (reseed_epoch
+  calls its set_epoch)."""
   from sepkern import dist as skdist
   if not hasattr(m, "DynMixTrainSet"):
     raise SystemExit("--dynamic-mix: the arch %s provides no DynMixTrainSet" % getattr(m, "__name__", m))
   seed = mixing_seed(args, rank, world)
-  dataset = m.DynMixTrainSet(args.data_dir, int(read_model_conf(args.model_config).get('num_spk', 2)),
+  dataset = m.DynMixTrainSet(args.data_dir, mixed_recordings(m, args),
                              mixes_per_epoch=args.mixes_per_epoch, snr_db=args.mix_snr_db, peak=args.mix_peak,
                              max_samples=args.mix_max_samples, seed=seed, sample_rate=getattr(args, "sample_rate", None),
                              quantize=args.mix_quantize, **reverb_options(args))      # (an arch without RIRs is given none)
