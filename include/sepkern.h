@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 140
+#define SK_VERSION 141
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -135,6 +135,40 @@ int sk_mask_istft(const void* mix_c64, const int64_t* mix_offs, const int64_t* m
                   const int32_t* nframes, int nutt, int S, int n_fft, int hop,
                   float* wav_out, int16_t* pcm_out, const int64_t* out_offs, int max_frames,
                   sk_stream_t stream);
+
+/* ---------------------------------------------------------------- stitching windowed masks (long recordings)
+ * A recording of T frames, too long for one pass of the network, is separated on overlapping windows of W frames every Hn
+ * frames (W/2 <= Hn < W: at most two windows cover a frame, O = W - Hn >= 1 frames are shared); sk_stitch aligns the output
+ * order of neighbouring windows on the frames they share and cross-fades them into one (T, S*257) mask.  No counterpart in the
+ * reference; sepkern/stitch.py states the definition and restates the arithmetic below in numpy.
+ * K = 1 + ceil(max(T - W, 0) / Hn) windows; window k starts at frame k Hn and has min(W, T - k Hn) frames (all but the last are
+ * full; for K >= 2 the last has more than O).  Element (t, c) of window k, t local, c < S*257 with output s in columns
+ * s*257 .. s*257+256, is mask[win_offs[k] + t*win_st[k] + c] (elements; the per-item offset / stride convention of sk_stft and
+ * sk_mask_istft): the windows stay where the network wrote them -- window j of a uniform packed batch of B windows with
+ * leading dimension ld has offset base + j*ld and stride B*ld, and windows of different batches mix freely (offsets are signed:
+ * a batch allocated below `mask` has negative ones).
+ * mag_rows (T, ld_mag >= 257): the magnitude rows of the WHOLE recording, as sk_stft writes them.
+ *   cost (K-1, S, S) fp64: cost[k][i][j] = sum_{o < O, f < 257} (X[(k+1) Hn + o][f] (m_k[Hn + o][i*257 + f] - m_{k+1}[o][j*257 + f]))^2,
+ *        every operand widened to fp64 first -- the PIT-MSE loss's magnitude-weighted distance, between two windows
+ *   p_k = the first permutation p in itertools.permutations order that minimises sum_i cost[k][i][p(i)] (the PIT kernels' tie
+ *        rule: a silent overlap gives the identity);  PI_0 = identity, PI_{k+1}(s) = p_k(PI_k(s));  perms (K, S) int32 = PI
+ *   out (T, ld_out >= S*257): stream s of frame t = output PI_k(s) of the window(s) k that cover t.  One window: a copy.  Two:
+ *        a + ramp[o] (b - a) with a the earlier and b the later window's value and o = t - (the later window's start); the
+ *        subtraction, the product and the sum are fp32, each rounded (no fused multiply-add: numpy float32 gives the same
+ *        bits), so a == b returns a.  ramp: O floats in [0, 1], the weight of the LATER window.
+ * Three launches on `stream`, no host synchronisation: (1) boundaries x chunks of 16 overlap frames, fp64 partial sums into
+ * fixed slots of ws; (2) one workgroup adds each boundary's chunks in ascending order, searches the S! permutations and
+ * composes PI along the chain; (3) output frames x columns: every element of out in rows < T, columns < S*257 is written
+ * exactly once, by one lane, and nothing else is; every mask element is read at most once per launch, and nothing outside the
+ * windows' min(W, T - k Hn) x S*257 elements is read.  No atomics, no hand-off between workgroups: bitwise reproducible, and a
+ * recording's bits do not depend on the descriptors' layout.  K = 1 is a copy (mag_rows, ramp, cost and ws may be NULL);
+ * S = 1 skips the search.  All pointers are device pointers, the descriptors K entries each.
+ * SK_EINVAL before anything is launched: S outside 1..4, T < 1, Hn outside [W/2, W), ws NULL where K > 1 (its size is the
+ * caller's to honour: ws >= sk_stitch_workspace_bytes(T, W, Hn, S), which is 0 for arguments out of range). */
+size_t sk_stitch_workspace_bytes(int T, int W, int Hn, int S);
+int sk_stitch(const float* mag_rows, int ld_mag, const float* mask, const int64_t* win_offs, const int64_t* win_st,
+              int T, int W, int Hn, int S, const float* ramp, float* out, int ld_out, int32_t* perms, double* cost,
+              void* ws, sk_stream_t stream);
 
 /* ---------------------------------------------------------------- fp32 GEMM (matrix cores)
  * C[M,N] (ldc) = act( opA(A) * opB(B) + bias[n] + (accumulate ? C : 0) ).

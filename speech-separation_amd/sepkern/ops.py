@@ -587,6 +587,86 @@ def mask_istft(mix_specs, masks=None, want_pcm=True, want_float=True, repeat=1):
     return split(wav), split(pcm)
 
 
+def mask_istft_frames(mixc, mask, S, want_pcm=True, want_float=True, repeat=1):
+    """Mask-apply + iSTFT of ONE recording held frame-major: mixc (T, 257) complex64 (sk_stft's rows), mask (T, ld >= S*257)
+    float32 with source s in columns s*257 .. (unit column stride; None = all ones, S = 1) -- sk_mask_istft with row strides,
+    nothing is transposed.  Returns (wav (S, 128 (T - 1)) float32 or None, pcm likewise int16 or None)."""
+    _chk(mixc, torch.complex64)
+    _chk(mask)
+    T = int(mixc.shape[0])
+    if mixc.dim() != 2 or mixc.shape[1] != 257 or not mixc.is_contiguous() or T < 2:
+        raise _lib.SepkernError("mask_istft_frames: mixc must be (T >= 2, 257) contiguous complex64")
+    if mask is not None and (mask.dim() != 2 or mask.stride(1) != 1 or mask.shape[0] < T or mask.shape[1] < S * 257):
+        raise _lib.SepkernError("mask_istft_frames: mask must be (>= T, >= S*257) with unit column stride")
+    dev, L = mixc.device, 128 * (T - 1)
+    wav = torch.empty(S, L, dtype=torch.float32, device=dev) if want_float else None
+    pcm = torch.empty(S, L, dtype=torch.int16, device=dev) if want_pcm else None
+    ld = int(mask.stride(0)) if mask is not None else 0
+    # [mix_offs | mix_st | mix_sf | mask_st | mask_sf | mask_offs (S) | out_offs (S)]; they must outlive the (asynchronous) launch call
+    d = _i64([0, 257, 1, ld, 1] + [s * 257 for s in range(S)] + [s * L for s in range(S)], dev)
+    d_T = torch.tensor([T], dtype=torch.int32, device=dev)
+    per = 257 * 8 + (257 * 4 if mask is not None else 0) + 128 * ((2 if want_pcm else 0) + (4 if want_float else 0))
+    with _timed("istft_kernel", repeat * float(T) * S * per):
+        for _ in range(repeat):
+            _lib.call("sk_mask_istft", _ptr(mixc), _ptr(d[0:1]), _ptr(d[1:2]), _ptr(d[2:3]),
+                      _ptr(mask), _ptr(d[5:5 + S]) if mask is not None else None, _ptr(d[3:4]) if mask is not None else None,
+                      _ptr(d[4:5]) if mask is not None else None, _ptr(d_T), 1, S, 512, 128, _ptr(wav), _ptr(pcm),
+                      _ptr(d[5 + S:]), T, _stream())
+    return wav, pcm
+
+
+# ----------------------------------------------------------------------------- stitching windowed masks
+def stitch(mag, windows, T, W, Hn, S, ramp, out=None, ws=None, repeat=1):
+    """The masks of the overlapping windows of one recording aligned and cross-faded (sk_stitch; sepkern/stitch.py defines the
+    result).  mag: (>= T, ld >= 257) float32 magnitude rows of the whole recording with unit column stride; windows: one
+    (tensor, element offset, row stride) per window -- element (t, c) of window k is tensor.view(-1)[offset + t * stride + c];
+    the tensors may be different allocations (the outputs of different batches: they stay where the network wrote them; the
+    caller keeps them alive until the launches have run); ramp: (W - Hn) float32, the weight of the later window.
+    out: a (>= T, >= S*257) float32 buffer with unit column stride to write into (rows < T, columns < S*257 only).
+    ws: a uint8 workspace of the caller's instead of the cached one.
+    -> (out (T, .), perms (K, S) int32, cost (K - 1, S, S) float64); nothing synchronises with the host."""
+    lib = _lib.load()
+    T, W, Hn, S = int(T), int(W), int(Hn), int(S)
+    nbytes = lib.sk_stitch_workspace_bytes(T, W, Hn, S)
+    K = 1 + -(-max(T - W, 0) // Hn) if Hn > 0 else 1
+    if nbytes and len(windows) != K:
+        raise _lib.SepkernError("stitch: %d windows given, T = %d, W = %d, Hn = %d make %d" % (len(windows), T, W, Hn, K))
+    _chk(mag)
+    _chk(ramp)
+    if nbytes and K > 1 and (mag.dim() != 2 or mag.stride(1) != 1 or mag.shape[0] < T or mag.shape[1] < 257 or ramp.numel() != W - Hn
+                             or not ramp.is_contiguous()):
+        raise _lib.SepkernError("stitch: mag must be (>= T, >= 257) with unit column stride, ramp W - Hn contiguous floats")
+    base = windows[0][0]
+    dev = base.device
+    offs = []
+    for t, off, _ in windows:
+        _chk(t)
+        delta = t.data_ptr() - base.data_ptr()          # in bytes; float32 storage: a multiple of 4
+        offs.append(delta // 4 + int(off))
+    if out is None:
+        out = torch.empty(max(T, 1), S * 257, dtype=torch.float32, device=dev)
+    _chk(out)
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < T or out.shape[1] < S * 257:
+        raise _lib.SepkernError("stitch: out must be (>= T, >= S*257) float32 with unit column stride")
+    if ws is None:
+        ws = workspace(nbytes, "stitch")
+    elif nbytes and (ws.dtype != torch.uint8 or ws.numel() < nbytes):
+        raise _lib.SepkernError("stitch: workspace of %d bytes, %d expected" % (ws.numel(), nbytes))
+    perms = torch.empty(max(K, 1), max(S, 1), dtype=torch.int32, device=dev)
+    cost = torch.empty(max(K - 1, 0), max(S, 1), max(S, 1), dtype=torch.float64, device=dev)
+    # descriptor arrays must outlive the (asynchronous) launch call: keep references until it returns
+    d = _i64(offs + [int(st) for _, _, st in windows], dev)
+    # algorithmic bytes: the cost launch reads both windows' O overlap frames and the mixture's; the blend launch reads every
+    # window element once and writes every output element once
+    ov = max(K - 1, 0) * max(W - Hn, 0)
+    with _timed("stitch", repeat * 4.0 * 257 * (ov * (2 * S + 1) + (T + ov) * S + T * S)):
+        for _ in range(repeat):
+            _lib.call("sk_stitch", _ptr(mag), int(mag.stride(0)) if mag is not None and mag.dim() == 2 else 0, _ptr(base), _ptr(d[:len(windows)]),
+                      _ptr(d[len(windows):]), T, W, Hn, S, _ptr(ramp), _ptr(out), int(out.stride(0)), _ptr(perms), _ptr(cost),
+                      _ptr(ws), _stream())
+    return out[:T], perms, cost
+
+
 # ----------------------------------------------------------------------------- PIT-MSE
 def pit_mse_fwd(mask, mix, srcs, lens, norm_dev=None, packing=None, repeat=1):
     """mask (T,B,S*F), mix (T,B,F), srcs list of S (T,B,F), lens int32 (B), norm_dev: optional device

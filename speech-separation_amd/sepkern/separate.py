@@ -1,0 +1,88 @@
+"""Separating a recording of any length: windowed inference with stitched masks, PCM in and PCM out on the device.
+
+The network is trained on chunks of a few hundred frames from a random initial state; a recording of minutes or hours is
+therefore cut into overlapping windows of that length, which run through the network as uniform batches (the shape the
+recurrence kernels are tuned for), and sk_stitch (sepkern/stitch.py) lines the windows' output orders up and cross-fades them.
+One STFT of the WHOLE recording feeds every window (a per-window STFT would reflect-pad at every window edge), and one
+mask-apply + iSTFT of the stitched masks gives the waveforms.  All window masks stay resident until they are stitched:
+stitch.memory_bytes(T, W, Hn, S) = K W S 257 4 bytes, about 0.9 GB for an hour at S = 2.
+"""
+import numpy as np
+import torch
+
+from . import ops
+from . import stitch as st
+from ._lib import SepkernError
+from .packing import Packing
+
+WORKING_RATE = 8000      # Hz: the rate the recipe's data (wav8k) and therefore its models work at
+
+
+def window_masks(model, mag, window_frames, hop_frames, batch_windows):
+    """The network on every window of mag (T, 257): -> [(tensor, offset, row stride)] per window, the descriptors ops.stitch
+    takes.  Full windows go in uniform batches of up to batch_windows (window j of a batch of B is offset j * ld, stride B * ld
+    of its packed output); a short last window runs as a batch of its own."""
+    T, dev = int(mag.shape[0]), mag.device
+    starts = st.window_starts(T, window_frames, hop_frames)
+    lens = [min(window_frames, T - s0) for s0 in starts]
+    full = [k for k in range(len(starts)) if lens[k] == window_frames]
+    batches = [full[i:i + batch_windows] for i in range(0, len(full), batch_windows)]
+    if len(full) < len(starts):
+        batches.append([len(starts) - 1])
+    windows = [None] * len(starts)
+    for ks in batches:
+        B, n = len(ks), lens[ks[0]]
+        pk = Packing(np.full(B, n, dtype=np.int32), dev)
+        # row (t, j) of the packed batch = frame starts[ks[j]] + t of the recording (an index copy: plumbing, no arithmetic)
+        idx = (torch.arange(n, device=dev).unsqueeze(1) + torch.tensor([starts[k] for k in ks], device=dev).unsqueeze(0)).reshape(-1)
+        x = pk.rows(mag.shape[1])
+        torch.index_select(mag, 0, idx, out=x[:pk.R])
+        model.hidden = model.init_hidden(B)
+        mask = model.forward_packed(x, pk)
+        ld = int(mask.stride(0))
+        for j, k in enumerate(ks):
+            windows[k] = (mask, j * ld, B * ld)
+    return windows
+
+
+def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=200, batch_windows=32, ramp=None,
+                       working_rate=WORKING_RATE, want_float=True, want_pcm=False, return_details=False):
+    """model: a uPIT SepDNN on the GPU; pcm: 1-D tensor of the recording's samples, int16 PCM or float32, at sample_rate Hz
+    (moved to the model's device if it is not there; resampled on the device when sample_rate is not working_rate, the rate the
+    model was trained at).  -> (wav (S, L) float32 or None, pcm16 (S, L) int16 or None) at working_rate,
+    L = 128 (T - 1) samples for the T = 1 + n // 128 frames of the n samples at working_rate; the int16 conversion is sk_mask_istft's
+    (the reference's: truncated, wrapping).  ramp: (window_frames - hop_frames) float32 weights of the later window, default
+    (o + 1) / (O + 1).  return_details: a third value, dict(masks = the window descriptors, stitched (T, S*257), perms, cost,
+    mag, mixc).  Nothing synchronises with the host between PCM in and PCM out."""
+    if not hasattr(model, "forward_packed"):
+        raise SepkernError("separate_recording needs a model with forward_packed (the uPIT arch)")
+    st.check_geometry(1, window_frames, hop_frames)
+    if batch_windows < 1:
+        raise ValueError("separate_recording: batch_windows = %d, at least 1 expected" % batch_windows)
+    dev = model.lin.weight.device
+    pcm = torch.as_tensor(pcm)
+    if pcm.dim() != 1 or pcm.dtype not in (torch.int16, torch.float32):
+        raise SepkernError("separate_recording: pcm must be a 1-D int16 or float32 tensor")
+    pcm = pcm.to(dev, non_blocking=True)
+    if int(sample_rate) != int(working_rate):
+        if pcm.dtype == torch.int16:
+            pcm, _ = ops.pcm_to_rate(pcm, [pcm.numel()], [int(sample_rate)], int(working_rate))
+        else:
+            pcm, _ = ops.resample_batch(pcm, [pcm.numel()], int(sample_rate), int(working_rate))
+    mixc = ops.stft_batch([pcm], want_complex=True)[0]          # (T, 257) complex64 rows of the whole recording
+    mag = ops.stft_batch([pcm], want_complex=False)[0]          # (T, 257): the bits the network was trained on
+    T, S = int(mag.shape[0]), int(model.num_spk)
+    O = window_frames - hop_frames
+    ramp = torch.from_numpy(st.default_ramp(O)).to(dev) if ramp is None else torch.as_tensor(ramp, dtype=torch.float32).to(dev).contiguous()
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            windows = window_masks(model, mag, window_frames, hop_frames, batch_windows)
+    finally:
+        model.train(was_training)
+    stitched, perms, cost = ops.stitch(mag, windows, T, window_frames, hop_frames, S, ramp)
+    wav, pcm16 = ops.mask_istft_frames(mixc, stitched, S, want_pcm=want_pcm, want_float=want_float)
+    if return_details:
+        return wav, pcm16, dict(masks=windows, stitched=stitched, perms=perms, cost=cost, mag=mag, mixc=mixc)
+    return wav, pcm16

@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Separate recordings of any length: wav in, wav out.  No counterpart in the reference, whose test stage runs whole
+utterances through the network (steps/eval_qsub.py) and reads its masks back from npz files (steps/reconstruct_sources.py).
+
+For every line `<ID> <path>` of wav-scp (mono 16-bit PCM wav at any rate): resample to --sample-rate, one STFT of the whole
+recording, the network on overlapping windows of --window-frames every --hop-frames as uniform batches of --batch-windows,
+the windows' output orders aligned and cross-faded (sk_stitch), mask-apply + iSTFT -> <out-dir>/s<k>/<ID>.wav (int16, at --sample-rate;
+the int16 conversion is reconstruct_sources.py's).  Everything between the PCM going in and the PCM coming out runs on the GPU
+(sepkern/separate.py).  The arch file is given by path, as to steps/eval_qsub.py; it must be the uPIT arch (fp32 or bf16
+models) -- an arch module whose SepDNN has no forward_packed (the RSH arch) is refused.  One recording per sk_stitch call,
+one GPU.
+"""
+import argparse
+import concurrent.futures
+import os
+import sys
+import time
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+PKG = os.path.abspath(os.path.join(HERE, ".."))
+os.environ.setdefault("SEPKERN_HOME", PKG)      # a frozen arch.py finds the sepkern package through it
+for p in (PKG, HERE):
+  if p not in sys.path:
+    sys.path.append(p)
+
+NO_FORWARD_PACKED = "separate_wav: the arch module %s has no SepDNN.forward_packed; windowed separation runs the uPIT arch only"
+
+
+def get_args(argv=None):
+  parser = argparse.ArgumentParser(description="""This separates wav recordings of any length into wav files""")
+  parser.add_argument("arch_file", metavar="arch-file", type=str, help="DNN architecture file (uPIT)")
+  parser.add_argument("gpu_id", metavar="gpu-id", type=int, help="GPU ID")
+  parser.add_argument("model", type=str, help="Trained model to use")
+  parser.add_argument("wav_scp", metavar="wav-scp", type=str, help="lines of `<ID> <path to a mono 16-bit wav file>`")
+  parser.add_argument("out_dir", metavar="out-dir", type=str, help="Output directory: <out-dir>/s<k>/<ID>.wav")
+  parser.add_argument("--model-config", type=str, help="Config file for DNN", default="")
+  parser.add_argument("--window-frames", type=int, default=400, help="window length in frames (the training chunk length)")
+  parser.add_argument("--hop-frames", type=int, default=200, help="window hop in frames, in [window/2, window)")
+  parser.add_argument("--batch-windows", type=int, default=32, help="windows per pass of the network")
+  parser.add_argument("--sample-rate", type=int, default=8000, help="rate the network works at: files at another rate are resampled to it on the GPU, the output is written at it")
+  parser.add_argument("--seed", type=int, default=None, help="seed for the random h0/c0 of every window (archs/uPIT.py:121-127)")
+  parser.add_argument("--writers", type=int, default=8, help="threads that read the wav inputs and write the wav outputs")
+  return parser.parse_args(argv)
+
+
+def main(argv=None):
+  args = get_args(argv)
+  import eval_qsub
+  m = eval_qsub.load_arch(args.arch_file)
+  if not hasattr(getattr(m, "SepDNN", None), "forward_packed"):
+    print(NO_FORWARD_PACKED % os.path.basename(args.arch_file), file=sys.stderr)
+    return 1
+  import scipy.io.wavfile
+  import torch
+  from sepkern import stitch as st
+  from sepkern.data import host_threads
+  from sepkern.separate import separate_recording
+  try:
+    st.check_geometry(1, args.window_frames, args.hop_frames)
+  except ValueError as e:
+    print("separate_wav: %s" % e, file=sys.stderr)
+    return 1
+  torch.cuda.set_device(args.gpu_id)
+  host_threads()
+  model = eval_qsub.restore_model(m, args, args.gpu_id)
+
+  entries = []
+  with open(args.wav_scp) as f:
+    for line in f:
+      if line.strip():
+        ID, path = line.rstrip('\n').split(' ', 1)
+        entries.append((ID, path))
+
+  def load(path):
+    fs, x = scipy.io.wavfile.read(path)
+    if x.dtype.name != 'int16' or x.ndim != 1:
+      raise ValueError("%s: only mono 16-bit PCM wav is supported" % path)
+    return int(fs), torch.from_numpy(x).pin_memory()
+
+  def write_wav(path, samples):
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    scipy.io.wavfile.write(path, args.sample_rate, samples)
+
+  t_start, n_frames, n_samples = time.perf_counter(), 0, 0
+  with concurrent.futures.ThreadPoolExecutor(max_workers=max(1, args.writers)) as pool:
+    loading = pool.submit(load, entries[0][1]) if entries else None
+    writing = []
+    for i, (ID, _) in enumerate(entries):
+      rate, pcm = loading.result()
+      loading = pool.submit(load, entries[i + 1][1]) if i + 1 < len(entries) else None      # read under this recording's GPU work
+      _, pcm16 = separate_recording(model, pcm, rate, args.window_frames, args.hop_frames, args.batch_windows,
+                                    working_rate=args.sample_rate, want_float=False, want_pcm=True)
+      out_h = torch.empty(pcm16.shape, dtype=torch.int16).pin_memory()
+      out_h.copy_(pcm16, non_blocking=True)
+      torch.cuda.synchronize()
+      samples = out_h.numpy()
+      n_frames += 1 + samples.shape[1] // 128
+      n_samples += samples.shape[1]
+      for s in range(samples.shape[0]):
+        writing.append(pool.submit(write_wav, os.path.join(args.out_dir, "s%d" % (s + 1), ID + ".wav"), samples[s]))
+    for w in writing:
+      w.result()                                # re-raise a writer's exception
+  model.check_status()
+  dt = max(time.perf_counter() - t_start, 1e-9)
+  print("separate_wav: %d recordings, %d frames in %.2f s = %.0f frames/s, real-time factor %.5f"
+        % (len(entries), n_frames, dt, n_frames / dt, dt / max(n_samples / float(args.sample_rate), 1e-9)), file=sys.stderr)
+  return 0
+
+
+if __name__ == '__main__':
+  sys.exit(main())
