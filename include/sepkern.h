@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 141
+#define SK_VERSION 142
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -169,6 +169,37 @@ size_t sk_stitch_workspace_bytes(int T, int W, int Hn, int S);
 int sk_stitch(const float* mag_rows, int ld_mag, const float* mask, const int64_t* win_offs, const int64_t* win_st,
               int T, int W, int Hn, int S, const float* ramp, float* out, int ld_out, int32_t* perms, double* cost,
               void* ws, sk_stream_t stream);
+
+/* ---------------------------------------------------------------- mask-based MVDR beamforming (multi-channel recordings)
+ * The stitched masks of one microphone steer one MVDR beamformer per separated stream over all C microphones (Souden et al.
+ * 2010; Heymann et al. 2016; the CSS recipe of Yoshioka et al. 2018).  No counterpart in the reference; sepkern/mvdr.py states
+ * the definition and restates the arithmetic below in numpy fp64.
+ * Y: complex64 spectra, element (c, t, f) at Y[c*y_chan_stride + t*y_row_stride + f] (elements; unit bin stride, F = 257 bins,
+ * y_row_stride >= 257); mask (T, ld_mask >= S*257) float32 with stream s in columns s*257 .. s*257+256 (sk_stitch's output).
+ * nblk = ceil(T / block_frames) blocks; block j holds frames [j Lb, min(T, (j+1) Lb)), Lb = block_frames.
+ *   A_j[s][f]   = sum_t mask[t][s*257 + f] y y^H, y = Y[:, t, f], t ascending over the block, every operand widened to fp64 first
+ *                 (Hermitian: the upper triangle is computed, the diagonal is real)
+ *   PHI_s[j][f] = sum of A_j'[s][f] over j' in [max(0, j - R), min(nblk - 1, j + R)], j' ascending, R = context_blocks
+ *                 (R >= nblk - 1: one time-invariant beamformer)
+ *   N_s         = sum_{s' != s} PHI_s', s' ascending (summed, not total minus own); then N_s += (loading * Re tr N_s / C) I
+ *   G = N_s^-1 PHI_s (fp64 Cholesky factorisation and C solves), d = Re tr G, W_s[j][f] = G[:, ref] / d;
+ *                 W_s[j][f] = e_ref (the reference channel passed through) where Re tr PHI_s == 0, Re tr N_s == 0 or not d > 1e-12
+ *   weights (nblk, S, 257, C) complex64 = W;  scm_out (nblk, S, 257, C, C) complex128 = PHI_s before any loading (may be NULL)
+ *   Z (S, T, 257) complex64: Z_s[t][f] = sum_c conj(W_s[t / Lb][f][c]) Y[c][t][f], fp32 fused multiply-adds, c ascending
+ * (a post-mask is sk_mask_istft's mask argument).  Three launches on `stream`, no host synchronisation: (1) blocks x groups of
+ * 64 bins, the upper triangle spread over the waves of a workgroup, into fixed slots of ws; (2) per (block, s, f) the context
+ * sum, N_s, the factorisation and the solves on registers; (3) frames x bins: every element of Z and of weights is written
+ * exactly once, nothing else is written, and nothing of Y outside its C x T x 257 elements or of mask outside its T x S*257 is
+ * read.  No atomics, no hand-off between workgroups, every sum in one fixed order: bitwise reproducible, and the bits do not
+ * depend on the strides.  The summation order inside a block is the definition's for bins 0..255; bin 256 adds 64 interleaved
+ * partial sums.  Launch 2 reads (2 R + 1) blocks' statistics per block.  All pointers are device pointers.
+ * SK_EINVAL before anything is launched: C outside 2..8, S outside 2..4, T < 1, block_frames < 1, context_blocks < 0, ref
+ * outside [0, C), loading negative or NaN, ld_mask < S*257, y_row_stride < 257, a NULL Y, mask, weights, Z or ws (its size is
+ * the caller's to honour: ws >= sk_mvdr_workspace_bytes(T, C, S, block_frames), which is 0 for arguments out of range). */
+size_t sk_mvdr_workspace_bytes(int T, int C, int S, int block_frames);
+int sk_mvdr(const void* Y_c64, int64_t y_chan_stride, int64_t y_row_stride, const float* mask, int ld_mask, int T, int C, int S,
+            int block_frames, int context_blocks, int ref, double loading, void* weights_c64, void* Z_c64, void* scm_out_c128,
+            void* ws, sk_stream_t stream);
 
 /* ---------------------------------------------------------------- fp32 GEMM (matrix cores)
  * C[M,N] (ldc) = act( opA(A) * opB(B) + bias[n] + (accumulate ? C : 0) ).

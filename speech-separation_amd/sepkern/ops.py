@@ -667,6 +667,83 @@ def stitch(mag, windows, T, W, Hn, S, ramp, out=None, ws=None, repeat=1):
     return out[:T], perms, cost
 
 
+# ----------------------------------------------------------------------------- mask-based MVDR beamforming
+def mvdr(Y, mask, S, block_frames, context_blocks, ref, loading, want_scm=False, weights=None, Z=None, ws=None, repeat=1):
+    """One MVDR beamformer per stream and block of frames, steered by the masks (sk_mvdr; sepkern/mvdr.py defines the result).
+    Y: (C, T, >= 257) complex64 spectra with unit bin stride (any channel and row stride: a view is read where it lies);
+    mask: (>= T, >= S*257) float32 with unit column stride, stream s in columns s*257 .. (ops.stitch's output).
+    weights / Z: contiguous complex64 buffers of (nblk, S, 257, C) / (S, T, 257) to write into; ws: a uint8 workspace of the
+    caller's instead of the cached one.
+    -> (weights (nblk, S, 257, C) complex64, Z (S, T, 257) complex64, scm (nblk, S, 257, C, C) complex128 or None); nothing
+    synchronises with the host."""
+    lib = _lib.load()
+    _chk(Y, torch.complex64)
+    _chk(mask)
+    if Y.dim() != 3 or Y.shape[2] < 257 or Y.stride(2) != 1:
+        raise _lib.SepkernError("mvdr: Y must be (C, T, >= 257) complex64 with unit bin stride")
+    C, T = int(Y.shape[0]), int(Y.shape[1])
+    S, Lb, R, ref = int(S), int(block_frames), int(context_blocks), int(ref)
+    if mask.dim() != 2 or mask.stride(1) != 1 or mask.shape[0] < T or mask.shape[1] < S * 257:
+        raise _lib.SepkernError("mvdr: mask must be (>= T, >= S*257) float32 with unit column stride")
+    nbytes = lib.sk_mvdr_workspace_bytes(T, C, S, Lb)
+    nblk = -(-T // Lb) if Lb > 0 else 1
+    dev = Y.device
+    if weights is None:
+        weights = torch.empty(nblk, S, 257, C, dtype=torch.complex64, device=dev)
+    if Z is None:
+        Z = torch.empty(S, T, 257, dtype=torch.complex64, device=dev)
+    _chk(weights, torch.complex64)
+    _chk(Z, torch.complex64)
+    if tuple(weights.shape) != (nblk, S, 257, C) or tuple(Z.shape) != (S, T, 257) or not weights.is_contiguous() or not Z.is_contiguous():
+        raise _lib.SepkernError("mvdr: weights must be (nblk, S, 257, C) and Z (S, T, 257), contiguous complex64")
+    scm = torch.empty(nblk, S, 257, C, C, dtype=torch.complex128, device=dev) if want_scm else None
+    if ws is None:
+        ws = workspace(nbytes, "mvdr")
+    elif nbytes and (ws.dtype != torch.uint8 or ws.numel() < nbytes):
+        raise _lib.SepkernError("mvdr: workspace of %d bytes, %d expected" % (ws.numel(), nbytes))
+    # algorithmic bytes: Y and the mask read by the statistics launch, Y read again and Z written by the apply launch, the
+    # block statistics written once and read 2 R + 1 times, the weights written and read
+    stats = float(nbytes)
+    per = float(T) * 257 * (2 * C * 8 + S * 4 + S * 8)
+    with _timed("mvdr", repeat * (per + stats * (1 + min(2 * R + 1, nblk)) + 2.0 * nblk * S * 257 * C * 8)):
+        for _ in range(repeat):
+            _lib.call("sk_mvdr", _ptr(Y), int(Y.stride(0)), int(Y.stride(1)), _ptr(mask), int(mask.stride(0)), T, C, S, Lb, R, ref,
+                      float(loading), _ptr(weights), _ptr(Z), _ptr(scm), _ptr(ws), _stream())
+    return weights, Z, scm
+
+
+def mask_istft_streams(Z, mask, S, want_pcm=True, want_float=True, repeat=1):
+    """iSTFT of S spectra held frame-major, each with its own column block of one mask: Z (S, T, 257) contiguous complex64
+    (ops.mvdr's output), mask None or (>= T, ld >= S*257) float32 with unit column stride, stream s in columns s*257 .. --
+    sk_mask_istft over S one-source items, descriptors only.  Returns (wav (S, 128 (T - 1)) float32 or None, pcm likewise
+    int16 or None)."""
+    _chk(Z, torch.complex64)
+    _chk(mask)
+    S = int(S)
+    if Z.dim() != 3 or Z.shape[0] != S or Z.shape[2] != 257 or not Z.is_contiguous() or Z.shape[1] < 2:
+        raise _lib.SepkernError("mask_istft_streams: Z must be (S, T >= 2, 257) contiguous complex64")
+    T = int(Z.shape[1])
+    if mask is not None and (mask.dim() != 2 or mask.stride(1) != 1 or mask.shape[0] < T or mask.shape[1] < S * 257):
+        raise _lib.SepkernError("mask_istft_streams: mask must be (>= T, >= S*257) with unit column stride")
+    dev, L = Z.device, 128 * (T - 1)
+    wav = torch.empty(S, L, dtype=torch.float32, device=dev) if want_float else None
+    pcm = torch.empty(S, L, dtype=torch.int16, device=dev) if want_pcm else None
+    ld = int(mask.stride(0)) if mask is not None else 0
+    # [mix_offs | mix_st | mix_sf | mask_offs | mask_st | mask_sf | out_offs], S entries each; they must outlive the (asynchronous) launch call
+    d = _i64([s * T * 257 for s in range(S)] + [257] * S + [1] * S + [s * 257 for s in range(S)] + [ld] * S + [1] * S
+             + [s * L for s in range(S)], dev)
+    d_T = torch.tensor([T] * S, dtype=torch.int32, device=dev)
+    part = lambda k: _ptr(d[k * S:(k + 1) * S])
+    has = mask is not None
+    per = 257 * 8 + (257 * 4 if has else 0) + 128 * ((2 if want_pcm else 0) + (4 if want_float else 0))
+    with _timed("istft_kernel", repeat * float(T) * S * per):
+        for _ in range(repeat):
+            _lib.call("sk_mask_istft", _ptr(Z), part(0), part(1), part(2), _ptr(mask), part(3) if has else None,
+                      part(4) if has else None, part(5) if has else None, _ptr(d_T), S, 1, 512, 128, _ptr(wav), _ptr(pcm),
+                      part(6), T, _stream())
+    return wav, pcm
+
+
 # ----------------------------------------------------------------------------- PIT-MSE
 def pit_mse_fwd(mask, mix, srcs, lens, norm_dev=None, packing=None, repeat=1):
     """mask (T,B,S*F), mix (T,B,F), srcs list of S (T,B,F), lens int32 (B), norm_dev: optional device

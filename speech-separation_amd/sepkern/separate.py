@@ -10,6 +10,7 @@ stitch.memory_bytes(T, W, Hn, S) = K W S 257 4 bytes, about 0.9 GB for an hour a
 import numpy as np
 import torch
 
+from . import mvdr as mv
 from . import ops
 from . import stitch as st
 from ._lib import SepkernError
@@ -46,14 +47,21 @@ def window_masks(model, mag, window_frames, hop_frames, batch_windows):
 
 
 def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=200, batch_windows=32, ramp=None,
-                       working_rate=WORKING_RATE, want_float=True, want_pcm=False, return_details=False):
+                       working_rate=WORKING_RATE, want_float=True, want_pcm=False, return_details=False, ref_channel=0,
+                       mvdr_block_frames=200, mvdr_context_blocks=1, mvdr_loading=1e-3, mvdr_postmask=False):
     """model: a uPIT SepDNN on the GPU; pcm: 1-D tensor of the recording's samples, int16 PCM or float32, at sample_rate Hz
     (moved to the model's device if it is not there; resampled on the device when sample_rate is not working_rate, the rate the
     model was trained at).  -> (wav (S, L) float32 or None, pcm16 (S, L) int16 or None) at working_rate,
     L = 128 (T - 1) samples for the T = 1 + n // 128 frames of the n samples at working_rate; the int16 conversion is sk_mask_istft's
     (the reference's: truncated, wrapping).  ramp: (window_frames - hop_frames) float32 weights of the later window, default
     (o + 1) / (O + 1).  return_details: a third value, dict(masks = the window descriptors, stitched (T, S*257), perms, cost,
-    mag, mixc).  Nothing synchronises with the host between PCM in and PCM out."""
+    mag, mixc).  Nothing synchronises with the host between PCM in and PCM out.
+    pcm of shape (C, n), 2 <= C <= 8: the C microphones of an array, sample-aligned.  The network, the windows and sk_stitch see
+    channel ref_channel only (its bits are those of the 1-D call on that channel); the stitched masks then steer one MVDR
+    beamformer per stream and block of mvdr_block_frames frames over all channels (sk_mvdr, sepkern/mvdr.py: a context of
+    mvdr_context_blocks blocks on either side, diagonal loading mvdr_loading), and the beamformed spectra are inverted --
+    multiplied by the masks once more with mvdr_postmask.  The defaults (3.2 s blocks, 9.6 s of context) follow the segment
+    lengths of the CSS literature; they are not tuned.  The details gain Y (C, T, 257), weights and Z."""
     if not hasattr(model, "forward_packed"):
         raise SepkernError("separate_recording needs a model with forward_packed (the uPIT arch)")
     st.check_geometry(1, window_frames, hop_frames)
@@ -61,15 +69,33 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
         raise ValueError("separate_recording: batch_windows = %d, at least 1 expected" % batch_windows)
     dev = model.lin.weight.device
     pcm = torch.as_tensor(pcm)
-    if pcm.dim() != 1 or pcm.dtype not in (torch.int16, torch.float32):
-        raise SepkernError("separate_recording: pcm must be a 1-D int16 or float32 tensor")
+    if pcm.dim() not in (1, 2) or pcm.dtype not in (torch.int16, torch.float32):
+        raise SepkernError("separate_recording: pcm must be a 1-D, or for an array a (C, n), int16 or float32 tensor")
     pcm = pcm.to(dev, non_blocking=True)
-    if int(sample_rate) != int(working_rate):
-        if pcm.dtype == torch.int16:
-            pcm, _ = ops.pcm_to_rate(pcm, [pcm.numel()], [int(sample_rate)], int(working_rate))
-        else:
-            pcm, _ = ops.resample_batch(pcm, [pcm.numel()], int(sample_rate), int(working_rate))
-    mixc = ops.stft_batch([pcm], want_complex=True)[0]          # (T, 257) complex64 rows of the whole recording
+    Y = None
+    if pcm.dim() == 2:
+        C, n = int(pcm.shape[0]), int(pcm.shape[1])
+        mv.check_arguments(C, int(model.num_spk), 1, int(mvdr_block_frames), int(mvdr_context_blocks), int(ref_channel), float(mvdr_loading))
+        flat = pcm.contiguous().view(-1)
+        if int(sample_rate) != int(working_rate):           # all channels in one call
+            if flat.dtype == torch.int16:
+                flat, outs = ops.pcm_to_rate(flat, [n] * C, [int(sample_rate)] * C, int(working_rate))
+            else:
+                flat, outs = ops.resample_batch(flat, [n] * C, int(sample_rate), int(working_rate))
+            n = int(outs[0])
+        Tn = 1 + n // 128
+        Y = torch.empty(C, Tn, 257, dtype=torch.complex64, device=dev)
+        ops.stft_batch(flat, want_complex=True, out=Y.view(-1), out_offs=[c * Tn * 257 for c in range(C)], stride_t=[257] * C,
+                       stride_f=[1] * C, lengths=[n] * C)
+        pcm = flat[int(ref_channel) * n:(int(ref_channel) + 1) * n]
+        mixc = Y[int(ref_channel)]
+    else:
+        if int(sample_rate) != int(working_rate):
+            if pcm.dtype == torch.int16:
+                pcm, _ = ops.pcm_to_rate(pcm, [pcm.numel()], [int(sample_rate)], int(working_rate))
+            else:
+                pcm, _ = ops.resample_batch(pcm, [pcm.numel()], int(sample_rate), int(working_rate))
+        mixc = ops.stft_batch([pcm], want_complex=True)[0]          # (T, 257) complex64 rows of the whole recording
     mag = ops.stft_batch([pcm], want_complex=False)[0]          # (T, 257): the bits the network was trained on
     T, S = int(mag.shape[0]), int(model.num_spk)
     O = window_frames - hop_frames
@@ -82,7 +108,13 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
     finally:
         model.train(was_training)
     stitched, perms, cost = ops.stitch(mag, windows, T, window_frames, hop_frames, S, ramp)
-    wav, pcm16 = ops.mask_istft_frames(mixc, stitched, S, want_pcm=want_pcm, want_float=want_float)
+    details = dict(masks=windows, stitched=stitched, perms=perms, cost=cost, mag=mag, mixc=mixc)
+    if Y is None:
+        wav, pcm16 = ops.mask_istft_frames(mixc, stitched, S, want_pcm=want_pcm, want_float=want_float)
+    else:
+        weights, Z, _ = ops.mvdr(Y, stitched, S, mvdr_block_frames, mvdr_context_blocks, ref_channel, mvdr_loading)
+        wav, pcm16 = ops.mask_istft_streams(Z, stitched if mvdr_postmask else None, S, want_pcm=want_pcm, want_float=want_float)
+        details.update(Y=Y, weights=weights, Z=Z)
     if return_details:
-        return wav, pcm16, dict(masks=windows, stitched=stitched, perms=perms, cost=cost, mag=mag, mixc=mixc)
+        return wav, pcm16, details
     return wav, pcm16

@@ -9,6 +9,11 @@ the int16 conversion is reconstruct_sources.py's).  Everything between the PCM g
 (sepkern/separate.py).  The arch file is given by path, as to steps/eval_qsub.py; it must be the uPIT arch (fp32 or bf16
 models) -- an arch module whose SepDNN has no forward_packed (the RSH arch) is refused.  One recording per sk_stitch call,
 one GPU.
+
+--mvdr admits microphone-array recordings: a multi-channel wav file per ID, or one wav.scp per channel with the same IDs
+(--mvdr-channel-scps, the way the CHiME-5 and Mixer-6 arrays lie on disk; wav-scp is then channel 0).  The network runs on
+--ref-channel; its stitched masks steer one MVDR beamformer per stream over all channels (sk_mvdr, sepkern/mvdr.py), and the
+beamformed streams are written.  The channels of an ID must share one rate and are cut to the shortest.
 """
 import argparse
 import concurrent.futures
@@ -31,7 +36,7 @@ def get_args(argv=None):
   parser.add_argument("arch_file", metavar="arch-file", type=str, help="DNN architecture file (uPIT)")
   parser.add_argument("gpu_id", metavar="gpu-id", type=int, help="GPU ID")
   parser.add_argument("model", type=str, help="Trained model to use")
-  parser.add_argument("wav_scp", metavar="wav-scp", type=str, help="lines of `<ID> <path to a mono 16-bit wav file>`")
+  parser.add_argument("wav_scp", metavar="wav-scp", type=str, help="lines of `<ID> <path to a mono 16-bit wav file>` (with --mvdr: any number of channels)")
   parser.add_argument("out_dir", metavar="out-dir", type=str, help="Output directory: <out-dir>/s<k>/<ID>.wav")
   parser.add_argument("--model-config", type=str, help="Config file for DNN", default="")
   parser.add_argument("--window-frames", type=int, default=400, help="window length in frames (the training chunk length)")
@@ -39,17 +44,28 @@ def get_args(argv=None):
   parser.add_argument("--batch-windows", type=int, default=32, help="windows per pass of the network")
   parser.add_argument("--sample-rate", type=int, default=8000, help="rate the network works at: files at another rate are resampled to it on the GPU, the output is written at it")
   parser.add_argument("--seed", type=int, default=None, help="seed for the random h0/c0 of every window (archs/uPIT.py:121-127)")
+  parser.add_argument("--mvdr", action="store_true", help="beamform multi-channel recordings with the masks (2..8 channels)")
+  parser.add_argument("--mvdr-channel-scps", type=str, default="", help="F1[,F2,...]: further wav.scp files with the same IDs, one per extra channel; wav-scp is then channel 0")
+  parser.add_argument("--ref-channel", type=int, default=0, help="the channel the network sees and the beamformers keep undistorted")
+  parser.add_argument("--mvdr-block-frames", type=int, default=200, help="frames per block of beamformer weights")
+  parser.add_argument("--mvdr-context-blocks", type=int, default=1, help="blocks on either side whose statistics a block's weights use")
+  parser.add_argument("--mvdr-loading", type=float, default=1e-3, help="diagonal loading of the noise matrix, relative to its mean diagonal")
+  parser.add_argument("--mvdr-postmask", action="store_true", help="multiply the beamformed spectra by the masks")
   parser.add_argument("--writers", type=int, default=8, help="threads that read the wav inputs and write the wav outputs")
   return parser.parse_args(argv)
 
 
 def main(argv=None):
   args = get_args(argv)
+  if args.mvdr_channel_scps and not args.mvdr:
+    print("separate_wav: --mvdr-channel-scps needs --mvdr", file=sys.stderr)
+    return 1
   import eval_qsub
   m = eval_qsub.load_arch(args.arch_file)
   if not hasattr(getattr(m, "SepDNN", None), "forward_packed"):
     print(NO_FORWARD_PACKED % os.path.basename(args.arch_file), file=sys.stderr)
     return 1
+  import numpy as np
   import scipy.io.wavfile
   import torch
   from sepkern import stitch as st
@@ -64,18 +80,40 @@ def main(argv=None):
   host_threads()
   model = eval_qsub.restore_model(m, args, args.gpu_id)
 
-  entries = []
-  with open(args.wav_scp) as f:
-    for line in f:
-      if line.strip():
-        ID, path = line.rstrip('\n').split(' ', 1)
-        entries.append((ID, path))
+  def read_scp(scp):
+    out = []
+    with open(scp) as f:
+      for line in f:
+        if line.strip():
+          ID, path = line.rstrip('\n').split(' ', 1)
+          out.append((ID, path))
+    return out
 
-  def load(path):
-    fs, x = scipy.io.wavfile.read(path)
-    if x.dtype.name != 'int16' or x.ndim != 1:
-      raise ValueError("%s: only mono 16-bit PCM wav is supported" % path)
-    return int(fs), torch.from_numpy(x).pin_memory()
+  entries = [(ID, [path]) for ID, path in read_scp(args.wav_scp)]
+  for scp in [f for f in args.mvdr_channel_scps.split(',') if f]:
+    more = dict(read_scp(scp))
+    missing = [ID for ID, _ in entries if ID not in more]
+    if missing:
+      print("separate_wav: %s lacks %d of wav-scp's IDs (%s ...)" % (scp, len(missing), missing[0]), file=sys.stderr)
+      return 1
+    for ID, paths in entries:
+      paths.append(more[ID])
+
+  def load(paths):
+    """-> (rate, pinned int16 samples: (n,) for a mono recording, (C, n) for an array)"""
+    rates, chans = [], []
+    for path in paths:
+      fs, x = scipy.io.wavfile.read(path)
+      if x.dtype.name != 'int16' or x.ndim > 2 or (x.ndim == 2 and not args.mvdr):
+        raise ValueError("%s: only mono 16-bit PCM wav is supported" % path)
+      rates.append(int(fs))
+      chans += [x] if x.ndim == 1 else [x[:, c] for c in range(x.shape[1])]
+    if len(set(rates)) != 1:
+      raise ValueError("%s: the channels' files have different rates %s" % (paths[0], sorted(set(rates))))
+    if len(chans) == 1:
+      return rates[0], torch.from_numpy(chans[0]).pin_memory()
+    n = min(len(c) for c in chans)
+    return rates[0], torch.from_numpy(np.stack([c[:n] for c in chans])).pin_memory()
 
   def write_wav(path, samples):
     os.makedirs(os.path.dirname(path), exist_ok=True)
@@ -89,7 +127,9 @@ def main(argv=None):
       rate, pcm = loading.result()
       loading = pool.submit(load, entries[i + 1][1]) if i + 1 < len(entries) else None      # read under this recording's GPU work
       _, pcm16 = separate_recording(model, pcm, rate, args.window_frames, args.hop_frames, args.batch_windows,
-                                    working_rate=args.sample_rate, want_float=False, want_pcm=True)
+                                    working_rate=args.sample_rate, want_float=False, want_pcm=True, ref_channel=args.ref_channel,
+                                    mvdr_block_frames=args.mvdr_block_frames, mvdr_context_blocks=args.mvdr_context_blocks,
+                                    mvdr_loading=args.mvdr_loading, mvdr_postmask=args.mvdr_postmask)
       out_h = torch.empty(pcm16.shape, dtype=torch.int16).pin_memory()
       out_h.copy_(pcm16, non_blocking=True)
       torch.cuda.synchronize()
