@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 142
+#define SK_VERSION 143
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -200,6 +200,35 @@ size_t sk_mvdr_workspace_bytes(int T, int C, int S, int block_frames);
 int sk_mvdr(const void* Y_c64, int64_t y_chan_stride, int64_t y_row_stride, const float* mask, int ld_mask, int T, int C, int S,
             int block_frames, int context_blocks, int ref, double loading, void* weights_c64, void* Z_c64, void* scm_out_c128,
             void* ws, sk_stream_t stream);
+
+/* ---------------------------------------------------------------- WPE dereverberation (multi-channel recordings)
+ * Weighted prediction error (Nakatani et al. 2010; Yoshioka & Nakatani 2012): per bin, the late reverberation of every channel
+ * is predicted from all channels' past, taps frames starting delay frames back, and subtracted.  No counterpart in the
+ * reference; sepkern/wpe.py states the definition and restates the arithmetic below in numpy fp64.
+ * Y: complex64 spectra, element (c, t, f) at Y[c*y_chan_stride + t*y_row_stride + f] (elements; unit bin stride, F = 257 bins,
+ * y_row_stride >= 257); X likewise with strides of its own; X must not overlap Y.  D = C*taps <= 80.
+ * nblk = ceil(T / Lb) blocks, Lb = block_frames; block j holds frames [j Lb, min(T, (j+1) Lb)), its window is
+ * [max(0, j Lb - Lc), min(T, (j+1) Lb + Lc)), Lc = context_frames, Lb + 2 Lc <= 4096.  Per (block, bin), on the window, with
+ * y~(t)[k C + c] = Y[c][t - delay - k][f] (0 before frame 0; the recording's frames before the window), x = y at first:
+ *   lambda(t) = (sum_c |x_c(t)|^2) / C, c ascending, fp64; lambda(t) <- max(lambda(t), 1e-10 max_t lambda); w(t) = 1 / lambda(t)
+ *   R = sum_t (w y~) y~^H (upper triangle, real diagonal), P = sum_t (w y~) y(t)^H, t ascending; R += (loading Re tr R / D) I
+ *   G = R^-1 P: fp64 Cholesky factorisation R = U^H U and two triangular solves per column;   x(t) = y(t) - G^H y~(t)
+ * `iterations` times.  The cell is passed through -- X = Y's own bits, G = 0 -- when in any iteration max lambda == 0,
+ * Re tr R == 0 before the loading, or a component of G is not finite (a matrix that is not positive definite leaves NaN).
+ *   X[c][t][f] = complex64(x_c(t)) for t in the block;  mag_out (T, ld_mag >= 257) float32 = |X[ref][t][f]| of the rounded value
+ *   (may be NULL);  G_out (nblk, 257, D, C) complex128 = the last iteration's G (may be NULL).
+ * One launch on `stream`, one workgroup per (block, bin) with R, P, G and the window's weights in LDS (up to 121 KB), no
+ * host synchronisation, no atomics, no hand-off between workgroups, every sum in one fixed order: bitwise reproducible, and
+ * the bits do not depend on the strides.  Every element of X (and of mag_out, G_out) is written exactly once, nothing else is
+ * written, and nothing of Y outside its C x T x 257 elements is read.  All pointers are device pointers.
+ * SK_EINVAL before anything is launched: C outside 1..8, taps < 1, delay < 1, C*taps > 80, iterations outside 1..8, T < 1,
+ * block_frames < 1, context_frames < 0, block_frames + 2 context_frames > 4096, ref outside [0, C), loading negative or NaN,
+ * y_row_stride or x_row_stride < 257, ld_mag < 257 with a mag_out, a NULL Y or X.  ws: sk_wpe keeps nothing in device memory
+ * between its passes; sk_wpe_workspace_bytes is 0 and ws may be NULL. */
+size_t sk_wpe_workspace_bytes(int T, int C, int taps, int block_frames, int context_frames);
+int sk_wpe(const void* Y_c64, int64_t y_chan_stride, int64_t y_row_stride, int T, int C, int taps, int delay, int iterations,
+           int block_frames, int context_frames, int ref, double loading, void* X_c64, int64_t x_chan_stride, int64_t x_row_stride,
+           float* mag_out, int ld_mag, void* G_out_c128, void* ws, sk_stream_t stream);
 
 /* ---------------------------------------------------------------- fp32 GEMM (matrix cores)
  * C[M,N] (ldc) = act( opA(A) * opB(B) + bias[n] + (accumulate ? C : 0) ).

@@ -744,6 +744,40 @@ def mask_istft_streams(Z, mask, S, want_pcm=True, want_float=True, repeat=1):
     return wav, pcm
 
 
+# ----------------------------------------------------------------------------- WPE dereverberation
+def wpe(Y, taps, delay, iterations, block_frames, context_frames, loading, ref=0, want_mag=False, want_G=False, X=None, repeat=1):
+    """Dereverberation by weighted prediction error, per block of frames and bin (sk_wpe; sepkern/wpe.py defines the result).
+    Y: (C, T, >= 257) complex64 spectra with unit bin stride (any channel and row stride: a view is read where it lies), 1 <= C
+    <= 8, C * taps <= 80.  X: a complex64 (C, T, >= 257) buffer with unit bin stride to write into (not overlapping Y).
+    -> (X (C, T, 257) complex64, mag (T, 257) float32 = |X[ref]| or None, G (nblk, 257, C*taps, C) complex128 or None); nothing
+    synchronises with the host."""
+    _lib.load()
+    _chk(Y, torch.complex64)
+    if Y.dim() != 3 or Y.shape[2] < 257 or Y.stride(2) != 1:
+        raise _lib.SepkernError("wpe: Y must be (C, T, >= 257) complex64 with unit bin stride")
+    C, T = int(Y.shape[0]), int(Y.shape[1])
+    K, dl, I, Lb, Lc, ref = int(taps), int(delay), int(iterations), int(block_frames), int(context_frames), int(ref)
+    dev = Y.device
+    if X is None:
+        X = torch.empty(C, T, 257, dtype=torch.complex64, device=dev)
+    _chk(X, torch.complex64)
+    if X.dim() != 3 or tuple(X.shape[:2]) != (C, T) or X.shape[2] < 257 or X.stride(2) != 1:
+        raise _lib.SepkernError("wpe: X must be (C, T, >= 257) complex64 with unit bin stride")
+    nblk = -(-T // Lb) if Lb > 0 else 1
+    D = C * K
+    mag = torch.empty(T, 257, dtype=torch.float32, device=dev) if want_mag else None
+    G = torch.empty(nblk, 257, max(D, 0), C, dtype=torch.complex128, device=dev) if want_G else None
+    # algorithmic bytes: every iteration reads its window twice (the weights, then the sums), the block is read once more and X
+    # written; the windows overlap by the context
+    win = float(min(T, Lb + 2 * max(Lc, 0))) * nblk if Lb > 0 else 0.0
+    per = 257.0 * C * 8 * (2 * max(I, 0) * win + 2 * T) + (257.0 * 4 * T if want_mag else 0.0) + (257.0 * nblk * D * C * 16 if want_G else 0.0)
+    with _timed("wpe", repeat * per):
+        for _ in range(repeat):
+            _lib.call("sk_wpe", _ptr(Y), int(Y.stride(0)), int(Y.stride(1)), T, C, K, dl, I, Lb, Lc, ref, float(loading), _ptr(X),
+                      int(X.stride(0)), int(X.stride(1)), _ptr(mag), 257, _ptr(G), None, _stream())
+    return X[:, :, :257], mag, G
+
+
 # ----------------------------------------------------------------------------- PIT-MSE
 def pit_mse_fwd(mask, mix, srcs, lens, norm_dev=None, packing=None, repeat=1):
     """mask (T,B,S*F), mix (T,B,F), srcs list of S (T,B,F), lens int32 (B), norm_dev: optional device

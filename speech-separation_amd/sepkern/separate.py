@@ -13,6 +13,7 @@ import torch
 from . import mvdr as mv
 from . import ops
 from . import stitch as st
+from . import wpe as wp
 from ._lib import SepkernError
 from .packing import Packing
 
@@ -48,7 +49,9 @@ def window_masks(model, mag, window_frames, hop_frames, batch_windows):
 
 def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=200, batch_windows=32, ramp=None,
                        working_rate=WORKING_RATE, want_float=True, want_pcm=False, return_details=False, ref_channel=0,
-                       mvdr_block_frames=200, mvdr_context_blocks=1, mvdr_loading=1e-3, mvdr_postmask=False):
+                       mvdr_block_frames=200, mvdr_context_blocks=1, mvdr_loading=1e-3, mvdr_postmask=False, mvdr=True,
+                       wpe=False, wpe_taps=10, wpe_delay=3, wpe_iterations=3, wpe_block_frames=600, wpe_context_frames=0,
+                       wpe_loading=1e-3):
     """model: a uPIT SepDNN on the GPU; pcm: 1-D tensor of the recording's samples, int16 PCM or float32, at sample_rate Hz
     (moved to the model's device if it is not there; resampled on the device when sample_rate is not working_rate, the rate the
     model was trained at).  -> (wav (S, L) float32 or None, pcm16 (S, L) int16 or None) at working_rate,
@@ -61,7 +64,14 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
     beamformer per stream and block of mvdr_block_frames frames over all channels (sk_mvdr, sepkern/mvdr.py: a context of
     mvdr_context_blocks blocks on either side, diagonal loading mvdr_loading), and the beamformed spectra are inverted --
     multiplied by the masks once more with mvdr_postmask.  The defaults (3.2 s blocks, 9.6 s of context) follow the segment
-    lengths of the CSS literature; they are not tuned.  The details gain Y (C, T, 257), weights and Z."""
+    lengths of the CSS literature; they are not tuned.  The details gain Y (C, T, 257), weights and Z.
+    wpe: the spectra are dereverberated first (sk_wpe, sepkern/wpe.py: wpe_taps frames of every channel's past from wpe_delay
+    frames back, wpe_iterations iterations, one filter per block of wpe_block_frames frames estimated on the block and
+    wpe_context_frames on either side, loading wpe_loading).  A 1-D pcm becomes a (1, T, 257) spectrum; X = sk_wpe's output
+    replaces Y everywhere downstream: the network sees |X[ref_channel]| (sk_wpe's mag_out), the masks are applied to
+    X[ref_channel] (mixc), MVDR runs on X.  The details gain X and keep the untouched Y.  The defaults (10 taps, a delay of 3,
+    3 iterations, 9.6 s blocks) are the literature's; they are not tuned.  mvdr=False with wpe and a (C, n) pcm dereverberates
+    with all channels and masks the reference channel instead of beamforming.  Without wpe the calls are those of before."""
     if not hasattr(model, "forward_packed"):
         raise SepkernError("separate_recording needs a model with forward_packed (the uPIT arch)")
     st.check_geometry(1, window_frames, hop_frames)
@@ -72,10 +82,16 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
     if pcm.dim() not in (1, 2) or pcm.dtype not in (torch.int16, torch.float32):
         raise SepkernError("separate_recording: pcm must be a 1-D, or for an array a (C, n), int16 or float32 tensor")
     pcm = pcm.to(dev, non_blocking=True)
+    if wpe:
+        wp.check_arguments(int(pcm.shape[0]) if pcm.dim() == 2 else 1, 1, int(wpe_taps), int(wpe_delay), int(wpe_iterations),
+                           int(wpe_block_frames), int(wpe_context_frames), int(ref_channel) if pcm.dim() == 2 else 0, float(wpe_loading))
     Y = None
     if pcm.dim() == 2:
         C, n = int(pcm.shape[0]), int(pcm.shape[1])
-        mv.check_arguments(C, int(model.num_spk), 1, int(mvdr_block_frames), int(mvdr_context_blocks), int(ref_channel), float(mvdr_loading))
+        if mvdr:
+            mv.check_arguments(C, int(model.num_spk), 1, int(mvdr_block_frames), int(mvdr_context_blocks), int(ref_channel), float(mvdr_loading))
+        elif not wpe:
+            raise ValueError("separate_recording: a (C, n) pcm needs mvdr or wpe")
         flat = pcm.contiguous().view(-1)
         if int(sample_rate) != int(working_rate):           # all channels in one call
             if flat.dtype == torch.int16:
@@ -96,7 +112,15 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
             else:
                 pcm, _ = ops.resample_batch(pcm, [pcm.numel()], int(sample_rate), int(working_rate))
         mixc = ops.stft_batch([pcm], want_complex=True)[0]          # (T, 257) complex64 rows of the whole recording
-    mag = ops.stft_batch([pcm], want_complex=False)[0]          # (T, 257): the bits the network was trained on
+    X = None
+    if wpe:
+        ref = int(ref_channel) if Y is not None else 0
+        Yw = Y if Y is not None else mixc.unsqueeze(0)
+        X, mag, _ = ops.wpe(Yw, wpe_taps, wpe_delay, wpe_iterations, wpe_block_frames, wpe_context_frames, wpe_loading, ref=ref,
+                            want_mag=True)
+        mixc = X[ref]
+    else:
+        mag = ops.stft_batch([pcm], want_complex=False)[0]          # (T, 257): the bits the network was trained on
     T, S = int(mag.shape[0]), int(model.num_spk)
     O = window_frames - hop_frames
     ramp = torch.from_numpy(st.default_ramp(O)).to(dev) if ramp is None else torch.as_tensor(ramp, dtype=torch.float32).to(dev).contiguous()
@@ -109,10 +133,12 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
         model.train(was_training)
     stitched, perms, cost = ops.stitch(mag, windows, T, window_frames, hop_frames, S, ramp)
     details = dict(masks=windows, stitched=stitched, perms=perms, cost=cost, mag=mag, mixc=mixc)
-    if Y is None:
+    if X is not None:
+        details.update(X=X, Y=Yw)
+    if Y is None or not mvdr:
         wav, pcm16 = ops.mask_istft_frames(mixc, stitched, S, want_pcm=want_pcm, want_float=want_float)
     else:
-        weights, Z, _ = ops.mvdr(Y, stitched, S, mvdr_block_frames, mvdr_context_blocks, ref_channel, mvdr_loading)
+        weights, Z, _ = ops.mvdr(Y if X is None else X, stitched, S, mvdr_block_frames, mvdr_context_blocks, ref_channel, mvdr_loading)
         wav, pcm16 = ops.mask_istft_streams(Z, stitched if mvdr_postmask else None, S, want_pcm=want_pcm, want_float=want_float)
         details.update(Y=Y, weights=weights, Z=Z)
     if return_details:

@@ -14,6 +14,10 @@ one GPU.
 (--mvdr-channel-scps, the way the CHiME-5 and Mixer-6 arrays lie on disk; wav-scp is then channel 0).  The network runs on
 --ref-channel; its stitched masks steer one MVDR beamformer per stream over all channels (sk_mvdr, sepkern/mvdr.py), and the
 beamformed streams are written.  The channels of an ID must share one rate and are cut to the shortest.
+
+--wpe dereverberates the spectra first (sk_wpe, sepkern/wpe.py: weighted prediction error over all channels), with or without
+--mvdr and on mono files too; without --mvdr a multi-channel recording is dereverberated with all its channels and the masks
+are applied to --ref-channel.
 """
 import argparse
 import concurrent.futures
@@ -36,7 +40,7 @@ def get_args(argv=None):
   parser.add_argument("arch_file", metavar="arch-file", type=str, help="DNN architecture file (uPIT)")
   parser.add_argument("gpu_id", metavar="gpu-id", type=int, help="GPU ID")
   parser.add_argument("model", type=str, help="Trained model to use")
-  parser.add_argument("wav_scp", metavar="wav-scp", type=str, help="lines of `<ID> <path to a mono 16-bit wav file>` (with --mvdr: any number of channels)")
+  parser.add_argument("wav_scp", metavar="wav-scp", type=str, help="lines of `<ID> <path to a mono 16-bit wav file>` (with --mvdr or --wpe: any number of channels)")
   parser.add_argument("out_dir", metavar="out-dir", type=str, help="Output directory: <out-dir>/s<k>/<ID>.wav")
   parser.add_argument("--model-config", type=str, help="Config file for DNN", default="")
   parser.add_argument("--window-frames", type=int, default=400, help="window length in frames (the training chunk length)")
@@ -51,13 +55,20 @@ def get_args(argv=None):
   parser.add_argument("--mvdr-context-blocks", type=int, default=1, help="blocks on either side whose statistics a block's weights use")
   parser.add_argument("--mvdr-loading", type=float, default=1e-3, help="diagonal loading of the noise matrix, relative to its mean diagonal")
   parser.add_argument("--mvdr-postmask", action="store_true", help="multiply the beamformed spectra by the masks")
+  parser.add_argument("--wpe", action="store_true", help="dereverberate the spectra by weighted prediction error first (1..8 channels)")
+  parser.add_argument("--wpe-taps", type=int, default=10, help="frames of every channel's past the prediction uses (channels * taps <= 80)")
+  parser.add_argument("--wpe-delay", type=int, default=3, help="frames between the present and the newest frame the prediction uses")
+  parser.add_argument("--wpe-iterations", type=int, default=3, help="re-estimations of the weights (1..8)")
+  parser.add_argument("--wpe-block-frames", type=int, default=600, help="frames per block of prediction filters")
+  parser.add_argument("--wpe-context-frames", type=int, default=0, help="frames on either side of a block its filters are estimated on as well")
+  parser.add_argument("--wpe-loading", type=float, default=1e-3, help="diagonal loading of the covariance matrix, relative to its mean diagonal")
   parser.add_argument("--writers", type=int, default=8, help="threads that read the wav inputs and write the wav outputs")
   return parser.parse_args(argv)
 
 
 def main(argv=None):
   args = get_args(argv)
-  if args.mvdr_channel_scps and not args.mvdr:
+  if args.mvdr_channel_scps and not (args.mvdr or args.wpe):
     print("separate_wav: --mvdr-channel-scps needs --mvdr", file=sys.stderr)
     return 1
   import eval_qsub
@@ -104,7 +115,7 @@ def main(argv=None):
     rates, chans = [], []
     for path in paths:
       fs, x = scipy.io.wavfile.read(path)
-      if x.dtype.name != 'int16' or x.ndim > 2 or (x.ndim == 2 and not args.mvdr):
+      if x.dtype.name != 'int16' or x.ndim > 2 or (x.ndim == 2 and not (args.mvdr or args.wpe)):
         raise ValueError("%s: only mono 16-bit PCM wav is supported" % path)
       rates.append(int(fs))
       chans += [x] if x.ndim == 1 else [x[:, c] for c in range(x.shape[1])]
@@ -129,7 +140,10 @@ def main(argv=None):
       _, pcm16 = separate_recording(model, pcm, rate, args.window_frames, args.hop_frames, args.batch_windows,
                                     working_rate=args.sample_rate, want_float=False, want_pcm=True, ref_channel=args.ref_channel,
                                     mvdr_block_frames=args.mvdr_block_frames, mvdr_context_blocks=args.mvdr_context_blocks,
-                                    mvdr_loading=args.mvdr_loading, mvdr_postmask=args.mvdr_postmask)
+                                    mvdr_loading=args.mvdr_loading, mvdr_postmask=args.mvdr_postmask, mvdr=args.mvdr or not args.wpe,
+                                    wpe=args.wpe, wpe_taps=args.wpe_taps, wpe_delay=args.wpe_delay, wpe_iterations=args.wpe_iterations,
+                                    wpe_block_frames=args.wpe_block_frames, wpe_context_frames=args.wpe_context_frames,
+                                    wpe_loading=args.wpe_loading)
       out_h = torch.empty(pcm16.shape, dtype=torch.int16).pin_memory()
       out_h.copy_(pcm16, non_blocking=True)
       torch.cuda.synchronize()
