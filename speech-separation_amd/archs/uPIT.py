@@ -39,6 +39,7 @@ Beyond the reference (all optional, defaults reproduce it):
     (--mix-rir-scp / --mix-rir-synth) every source is first convolved with a room impulse response, also on the GPU
     (sk_fir_convolve; sepkern/reverb.py): reverberant mixtures, reverberant sources as targets.
 """
+import collections
 import itertools
 import os
 import sys
@@ -461,51 +462,37 @@ def needs_waveforms(kind):
   return NEEDS_WAVEFORMS.replace("loss=sisdr", "loss=" + kind)
 
 
-class _SisdrFn(torch.autograd.Function):
-  """out = [-mean_j best SI-SDR score, count, sum_j best score] from the packed mask rows: mask-apply + iSTFT, the SI-SDR
-  sums and PIT forward; the SI-SDR gradient and the iSTFT's adjoint fused in one kernel backward."""
+# A waveform loss as _WaveLossFn runs it: forward op (est, est_offs, ref, ref_offs, nsamp, n_est, max_samples, *extra, count),
+# backward op (est, est_offs, ref, ref_offs, choice, coef, gscale, mixc, pk, n_est, out=dmask), the forward result's key of the
+# per-utterance choice the backward needs.
+_WaveLoss = collections.namedtuple('_WaveLoss', 'fwd bwd choice')
+_SISDR = _WaveLoss(ops.sisdr_pit_fwd, ops.sisdr_mask_grad, 'best_perm')     # arg-max permutation; no extra arguments
+_MIXIT = _WaveLoss(ops.mixit_fwd, ops.mixit_mask_grad, 'best_code')         # arg-max assignment code; extra = (tau,)
+
+
+class _WaveLossFn(torch.autograd.Function):
+  """out = [-mean_j best score, count, sum_j best score] from the packed mask rows: mask-apply + iSTFT of the n_est estimates,
+  the loss's sums and its search (permutations / assignments) forward; the loss's gradient and the iSTFT's adjoint fused in
+  one kernel backward."""
 
   @staticmethod
-  def forward(ctx, mask, pk, wave, desc, count_dev, S):
-    est, est_offs, _ = ops.mask_istft_rows(wave['mixc'], mask, pk, S, est_offs=desc['est_offs'])
+  def forward(ctx, mask, pk, wave, desc, count_dev, n_est, loss, extra):
+    est, est_offs, _ = ops.mask_istft_rows(wave['mixc'], mask, pk, n_est, est_offs=desc['est_offs'])
     ref_offs = desc['ref_offs']
-    res = ops.sisdr_pit_fwd(est, est_offs, wave['flat'], ref_offs, desc['nsamp'], S, 128 * (pk.T - 1), count_dev)
-    ctx.save_for_backward(est, est_offs, ref_offs, res["best_perm"], res["coef"], wave['mixc'], wave['flat'])
-    ctx.pk, ctx.S, ctx.shape = pk, S, tuple(mask.shape)
-    ctx.mark_non_differentiable(res["best_perm"])
-    return res["out"], res["best_perm"]
+    res = loss.fwd(est, est_offs, wave['flat'], ref_offs, desc['nsamp'], n_est, 128 * (pk.T - 1), *extra, count_dev)
+    best = res[loss.choice]
+    ctx.save_for_backward(est, est_offs, ref_offs, best, res["coef"], wave['mixc'], wave['flat'])
+    ctx.pk, ctx.n_est, ctx.loss, ctx.shape = pk, n_est, loss, tuple(mask.shape)
+    ctx.mark_non_differentiable(best)
+    return res["out"], best
 
   @staticmethod
-  def backward(ctx, gout, _gperm):
+  def backward(ctx, gout, _gbest):
     est, est_offs, ref_offs, best, coef, mixc, flat = ctx.saved_tensors
     dmask = torch.empty(ctx.shape, dtype=torch.float32, device=est.device)
     dmask[ctx.pk.R:].zero_()               # tail rows of an (Rp, .) buffer stay zero
-    ops.sisdr_mask_grad(est, est_offs, flat, ref_offs, best, coef, gout[0:1].contiguous(), mixc, ctx.pk, ctx.S, out=dmask)
-    return dmask, None, None, None, None, None
-
-
-class _MixitFn(torch.autograd.Function):
-  """out = [-mean_j best MixIT score, count, sum_j best score] from the packed mask rows: mask-apply + iSTFT of the M
-  estimates, the sums and the search over the 2^M assignments forward; the group gradients and the iSTFT's adjoint fused in
-  one kernel backward (one transform per utterance and reference)."""
-
-  @staticmethod
-  def forward(ctx, mask, pk, wave, desc, count_dev, M, tau):
-    est, est_offs, _ = ops.mask_istft_rows(wave['mixc'], mask, pk, M, est_offs=desc['est_offs'])
-    ref_offs = desc['ref_offs']
-    res = ops.mixit_fwd(est, est_offs, wave['flat'], ref_offs, desc['nsamp'], M, 128 * (pk.T - 1), tau, count_dev)
-    ctx.save_for_backward(est, est_offs, ref_offs, res["best_code"], res["coef"], wave['mixc'], wave['flat'])
-    ctx.pk, ctx.M, ctx.shape = pk, M, tuple(mask.shape)
-    ctx.mark_non_differentiable(res["best_code"])
-    return res["out"], res["best_code"]
-
-  @staticmethod
-  def backward(ctx, gout, _gcode):
-    est, est_offs, ref_offs, best, coef, mixc, flat = ctx.saved_tensors
-    dmask = torch.empty(ctx.shape, dtype=torch.float32, device=est.device)
-    dmask[ctx.pk.R:].zero_()               # tail rows of an (Rp, .) buffer stay zero
-    ops.mixit_mask_grad(est, est_offs, flat, ref_offs, best, coef, gout[0:1].contiguous(), mixc, ctx.pk, ctx.M, out=dmask)
-    return dmask, None, None, None, None, None, None
+    ctx.loss.bwd(est, est_offs, flat, ref_offs, best, coef, gout[0:1].contiguous(), mixc, ctx.pk, ctx.n_est, out=dmask)
+    return dmask, None, None, None, None, None, None, None
 
 
 class SepDNN(SepDNNBase):
@@ -600,6 +587,22 @@ def compute_loss_packed(model, mix, sources, pk, plotdir=""):
   return loss, norm
 
 
+def _wave_loss(model, mix, pk, wave, loss, descriptors, extra=()):
+  """The head the waveform losses share: a fresh state, the global count, the descriptors, the network, the loss ->
+  (out = [loss, count, sum], the per-utterance choice)."""
+  n_est = model.num_spk
+  model.zero_grad()
+  model.hidden = model.init_hidden(pk.B)
+  # data-parallel: divide by the GLOBAL utterance count (None = single process: the kernel uses B), while training only
+  training_step = model.training and torch.is_grad_enabled()
+  count = skdist.global_norm(pk.lens.new_full((1,), pk.B), 1) if training_step else None
+  desc = descriptors(pk, wave['sig_offs'], n_est)       # (uploaded before the network is enqueued, not behind it)
+  mask_out = model.forward_packed(mix, pk)
+  out, best = _WaveLossFn.apply(mask_out, pk, wave, desc, count, n_est, loss, extra)
+  model.step_frames = pk.R                  # (the norm counts utterances: the driver's frames/s line reads this)
+  return out, best.detach()
+
+
 def compute_loss_wave(model, mix, pk, wave):
   """The loss=sisdr route: mix (R,F) packed magnitude rows (the network's input), wave as wave_features_from_pcm made it.
   Returns (mean negative SI-SDR per utterance in dB, number of utterances)."""
@@ -607,16 +610,8 @@ def compute_loss_wave(model, mix, pk, wave):
   missing = [k for k in ('source' + str(i + 1) for i in range(S)) if k not in wave['sig_offs']]
   if missing:
     raise ValueError("loss=sisdr: the batch holds no waveform %s (num_spk = %d)" % (", ".join(missing), S))
-  model.zero_grad()
-  model.hidden = model.init_hidden(pk.B)
-  # data-parallel: divide by the GLOBAL utterance count (None = single process: the kernel uses B), while training only
-  training_step = model.training and torch.is_grad_enabled()
-  count = skdist.global_norm(pk.lens.new_full((1,), pk.B), 1) if training_step else None
-  desc = ops.sisdr_descriptors(pk, wave['sig_offs'], S)       # (uploaded before the network is enqueued, not behind it)
-  mask_out = model.forward_packed(mix, pk)
-  out, best = _SisdrFn.apply(mask_out, pk, wave, desc, count, S)
-  model.last_best_perm = best.detach()      # arg-max permutation per utterance (index into itertools.permutations)
-  model.step_frames = pk.R                  # (the norm counts utterances: the driver's frames/s line reads this)
+  out, model.last_best_perm = _wave_loss(model, mix, pk, wave, _SISDR, ops.sisdr_descriptors)
+  # (last_best_perm: arg-max permutation per utterance, index into itertools.permutations)
   return out[0], out[1].detach()
 
 
@@ -634,17 +629,9 @@ def compute_loss_mixit(model, mix, pk, wave):
   if have != ['source1', 'source2']:
     raise ValueError("loss=mixit: the batch holds the waveforms %s; the references are exactly source1 and source2 "
                      "(num_spk = %d counts the masks)" % (", ".join(have), M))
-  model.zero_grad()
-  model.hidden = model.init_hidden(pk.B)
-  # data-parallel: divide by the GLOBAL utterance count (None = single process: the kernel uses B), while training only
-  training_step = model.training and torch.is_grad_enabled()
-  count = skdist.global_norm(pk.lens.new_full((1,), pk.B), 1) if training_step else None
-  desc = ops.mixit_descriptors(pk, wave['sig_offs'], M)       # (uploaded before the network is enqueued, not behind it)
-  mask_out = model.forward_packed(mix, pk)
   tau = 10.0 ** (-float(getattr(model, 'mixit_snr_max', 30.0)) / 10.0)
-  out, best = _MixitFn.apply(mask_out, pk, wave, desc, count, M, tau)
-  model.last_best_code = best.detach()      # arg-max assignment per utterance: bit k = the reference estimate k is added to
-  model.step_frames = pk.R                  # (the norm counts utterances: the driver's frames/s line reads this)
+  out, model.last_best_code = _wave_loss(model, mix, pk, wave, _MIXIT, ops.mixit_descriptors, (tau,))
+  # (last_best_code: arg-max assignment per utterance, bit k = the reference estimate k is added to)
   return out[0], out[1].detach()
 
 

@@ -4,11 +4,9 @@
 //
 // One streaming pass reads every estimate and both reference samples once and forms, per utterance, the plain sums
 //   P_n = sum x_n^2,  c_nk = sum x_n e_k,  G_kl = sum e_k e_l (k <= l)        (NQ = 2 + 2 M + M (M + 1) / 2 values)
-// in fp64, exactly as sisdr.hip forms its sums: a thread adds its samples in index order, a workgroup (one chunk of CHUNK
-// samples) adds its threads by a fixed shuffle tree, and the finalize kernel adds the chunks of an utterance in chunk order.
-// No atomics; the chunk grid of an utterance depends on its own length only, so each value has one order of operations
-// whatever else is in the batch.  The error of every one of the 2^M assignments follows from these sums alone.
-#include "sk_common.h"
+// in fp64, on the sums skeleton of wave_loss.h (which states the order of operations), as sisdr.hip forms its sums.  The
+// error of every one of the 2^M assignments follows from these sums alone.
+#include "wave_loss.h"
 
 #include <math.h>
 
@@ -16,18 +14,11 @@ namespace {
 
 constexpr int MAXM = SK_MAXS;
 constexpr int NREF = 2;
-constexpr int CHUNK = 4096;               // samples per workgroup: 16 per thread
 constexpr int NQMAX = 2 + 2 * MAXM + MAXM * (MAXM + 1) / 2;
 
 __host__ __device__ constexpr int nq_of(int M) { return 2 + 2 * M + M * (M + 1) / 2; }
 // index of G_kl, k <= l, in the row-major upper triangle that follows P and c
 __host__ __device__ constexpr int g_index(int M, int k, int l) { return 2 + 2 * M + k * M - k * (k - 1) / 2 + (l - k); }
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // partial[(u * nch + ch) * NQ + q]: [P_0 P_1 | c_0k (M) | c_1k (M) | G_kl, k <= l, row-major]
 template <int M>
@@ -37,7 +28,6 @@ __global__ __launch_bounds__(256) void mixit_sums_kernel(const float* __restrict
                                                          const int32_t* __restrict__ nsamp, int nch,
                                                          double* __restrict__ partial) {
   constexpr int NQ = nq_of(M);
-  __shared__ double red[4][NQ];
   const int u = blockIdx.y, ch = blockIdx.x;
   const int L = nsamp[u];
   const int n0 = ch * CHUNK;
@@ -57,8 +47,7 @@ __global__ __launch_bounds__(256) void mixit_sums_kernel(const float* __restrict
 #pragma unroll
     for (int k = 0; k < M; ++k) e[k] = (double)ep[k][i];
 #pragma unroll
-    for (int n = 0; n < NREF; ++n)  // int16 PCM scaled by 2^-15: exact in fp32 and in fp64
-      x[n] = pcm16 ? (double)((const int16_t*)ref)[ro[n] + i] * (1.0 / 32768.0) : (double)((const float*)ref)[ro[n] + i];
+    for (int n = 0; n < NREF; ++n) x[n] = ref_f64(ref, pcm16, ro[n], i);
 #pragma unroll
     for (int n = 0; n < NREF; ++n) {
       acc[n] += x[n] * x[n];
@@ -70,23 +59,12 @@ __global__ __launch_bounds__(256) void mixit_sums_kernel(const float* __restrict
 #pragma unroll
       for (int l = k; l < M; ++l) acc[g_index(M, k, l)] += e[k] * e[l];
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    const double v = wave_sum_f64(acc[q]);
-    if (lane == 0) red[wave][q] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NQ) {
-    const int q = threadIdx.x;
-    partial[((int64_t)u * nch + ch) * NQ + q] = (red[0][q] + red[1][q]) + (red[2][q] + red[3][q]);
-  }
+  chunk_store<NQ>(acc, partial + ((int64_t)u * nch + ch) * NQ);
 }
 
-// First one thread per (utterance, sum) adds that sum's chunks in chunk order; then one thread per utterance walks the 2^M
-// assignment codes (bit k of a code = the reference estimate k is added to) in code order: the two errors from the sums, the
-// two thresholded scores, their mean; the first maximum wins and leaves its two gradient coefficients.  Thread 0 finally adds
-// the best scores in utterance order.  The utterance's sums are indexed at run time and live in the workspace.
+// Between gather_chunks and tally_scores, one thread per utterance walks the 2^M assignment codes (bit k of a code = the
+// reference estimate k is added to) in code order: the two errors from the sums, the two thresholded scores, their mean; the
+// first maximum wins and leaves its two gradient coefficients.  The utterance's sums are indexed at run time and live in the workspace.
 __global__ __launch_bounds__(256) void mixit_finalize_kernel(const double* __restrict__ partial, int nch,
                                                              const int32_t* __restrict__ nsamp, int B, int M, double tau,
                                                              const float* __restrict__ count_dev, double* __restrict__ best_score,
@@ -97,14 +75,7 @@ __global__ __launch_bounds__(256) void mixit_finalize_kernel(const double* __res
   const int ncode = 1 << M;
   const double count = count_dev ? (double)count_dev[0] : (double)B;
   const double eps = 1e-30, kappa = 10.0 / log(10.0);
-  for (int idx = threadIdx.x; idx < B * NQ; idx += 256) {
-    const int u = idx / NQ, q = idx - u * NQ;
-    const int mych = (nsamp[u] + CHUNK - 1) / CHUNK;
-    double a = 0.0;
-    for (int c = 0; c < mych; ++c) a += partial[((int64_t)u * nch + c) * NQ + q];
-    sums[idx] = a;
-  }
-  __syncthreads();
+  gather_chunks(partial, nch, nsamp, B, NQ, sums);
   for (int u = threadIdx.x; u < B; u += 256) {
     const double* const s = sums + (int64_t)u * NQ;
     // err_n(code) = max(P_n - 2 sum_{k in n} c_nk + sum_{k,l in n} G_kl, 0): members ascending, G_kk then 2 G_kl for l > k
@@ -138,25 +109,14 @@ __global__ __launch_bounds__(256) void mixit_finalize_kernel(const double* __res
       coef[u * NREF + n] = den > 0.0 ? (float)(kappa / (count * (den + eps))) : 0.0f;  // a silent reference met exactly: no gradient
     }
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double tot = 0.0;
-    for (int u = 0; u < B; ++u) tot += best_score[u];
-    out[0] = (float)(-tot / count);
-    out[1] = (float)count;
-    out[2] = (float)tot;
-  }
-}
-
-size_t partial_bytes(int B, int M, int max_samples) {
-  return sk_align((size_t)B * sk_cdiv(max_samples, CHUNK) * nq_of(M) * sizeof(double), 256);
+  tally_scores(best_score, B, count, out);
 }
 
 }  // namespace
 
 extern "C" size_t sk_mixit_workspace_bytes(int B, int M, int max_samples) {
   if (B <= 0 || M < 2 || M > MAXM || max_samples <= 0) return 0;
-  return partial_bytes(B, M, max_samples) + sk_align((size_t)B * (1 + NQMAX) * sizeof(double), 256);  // + best scores, sums
+  return partial_bytes(B, nq_of(M), max_samples) + sk_align((size_t)B * (1 + NQMAX) * sizeof(double), 256);  // + best scores, sums
 }
 
 extern "C" int sk_mixit_fwd(const float* est, const int64_t* est_offs, const void* ref, int pcm16, const int64_t* ref_offs,
@@ -169,18 +129,12 @@ extern "C" int sk_mixit_fwd(const float* est, const int64_t* est_offs, const voi
   SK_CHECK_ARG(tau >= 0.0 && tau <= 1.0, "sk_mixit_fwd: tau %g outside 0..1", tau);
   const int nch = (int)sk_cdiv(max_samples, CHUNK);
   double* partial = (double*)ws;
-  double* best_score = (double*)((char*)ws + partial_bytes(B, M, max_samples));
+  double* best_score = (double*)((char*)ws + partial_bytes(B, nq_of(M), max_samples));
   double* sums = best_score + B;  // B x NQ <= B x NQMAX
   dim3 grid((unsigned)nch, (unsigned)B);
   hipStream_t st = (hipStream_t)stream;
-#define SK_MIXIT_SUMS(NM) \
-  hipLaunchKernelGGL(mixit_sums_kernel<NM>, grid, dim3(256), 0, st, est, est_offs, ref, pcm16, ref_offs, nsamp, nch, partial)
-  switch (M) {
-    case 2: SK_MIXIT_SUMS(2); break;
-    case 3: SK_MIXIT_SUMS(3); break;
-    default: SK_MIXIT_SUMS(4); break;
-  }
-#undef SK_MIXIT_SUMS
+  const sums_kernel_t sums_kernel[MAXM - 1] = {mixit_sums_kernel<2>, mixit_sums_kernel<3>, mixit_sums_kernel<4>};
+  hipLaunchKernelGGL(sums_kernel[M - 2], grid, dim3(256), 0, st, est, est_offs, ref, pcm16, ref_offs, nsamp, nch, partial);
   SK_CHECK_LAUNCH("mixit_sums_kernel");
   hipLaunchKernelGGL(mixit_finalize_kernel, dim3(1), dim3(256), 0, st, partial, nch, nsamp, B, M, tau, count_dev, best_score,
                      sums, assign_score, best_code, out, coef);

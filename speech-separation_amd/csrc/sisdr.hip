@@ -4,23 +4,16 @@
 //
 // One streaming pass reads every estimate and every reference sample once and forms, per utterance, the plain sums
 //   sum e_k, sum r_i, sum e_k^2, sum r_i^2, sum e_k r_i        (4 S + S^2 values)
-// in fp64: a thread adds its samples in index order, a workgroup (one chunk of CHUNK samples) adds its threads by a fixed
-// shuffle tree, and the finalize kernel adds the chunks of an utterance in chunk order.  No atomics; the chunk grid of an
-// utterance depends on its own length only, so each value has one order of operations whatever else is in the batch.
-#include "sk_common.h"
+// in fp64, on the sums skeleton of wave_loss.h (which states the order of operations).
+#include "wave_loss.h"
 
 #include <math.h>
 
 namespace {
 
 constexpr int MAXS = SK_MAXS;
-constexpr int CHUNK = 4096;               // samples per workgroup: 16 per thread
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+__host__ __device__ constexpr int nq_of(int S) { return 4 * S + S * S; }
 
 // partial[(u * nch + ch) * NQ + q], NQ = 4 S + S^2: [sum e (S) | sum r (S) | sum e^2 (S) | sum r^2 (S) | sum e_k r_i (k-major)]
 template <int S>
@@ -29,8 +22,7 @@ __global__ __launch_bounds__(256) void sisdr_sums_kernel(const float* __restrict
                                                          const int64_t* __restrict__ ref_offs,
                                                          const int32_t* __restrict__ nsamp, int nch,
                                                          double* __restrict__ partial) {
-  constexpr int NQ = 4 * S + S * S;
-  __shared__ double red[4][NQ];
+  constexpr int NQ = nq_of(S);
   const int u = blockIdx.y, ch = blockIdx.x;
   const int L = nsamp[u];
   const int n0 = ch * CHUNK;
@@ -51,8 +43,7 @@ __global__ __launch_bounds__(256) void sisdr_sums_kernel(const float* __restrict
 #pragma unroll
     for (int s = 0; s < S; ++s) {
       e[s] = (double)ep[s][n];
-      // int16 PCM scaled by 2^-15: exact in fp32 and in fp64
-      r[s] = pcm16 ? (double)((const int16_t*)ref)[ro[s] + n] * (1.0 / 32768.0) : (double)((const float*)ref)[ro[s] + n];
+      r[s] = ref_f64(ref, pcm16, ro[s], n);
     }
 #pragma unroll
     for (int s = 0; s < S; ++s) {
@@ -64,42 +55,24 @@ __global__ __launch_bounds__(256) void sisdr_sums_kernel(const float* __restrict
       for (int i = 0; i < S; ++i) acc[4 * S + s * S + i] += e[s] * r[i];
     }
   }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int q = 0; q < NQ; ++q) {
-    const double v = wave_sum_f64(acc[q]);
-    if (lane == 0) red[wave][q] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < NQ) {
-    const int q = threadIdx.x;
-    partial[((int64_t)u * nch + ch) * NQ + q] = (red[0][q] + red[1][q]) + (red[2][q] + red[3][q]);
-  }
+  chunk_store<NQ>(acc, partial + ((int64_t)u * nch + ch) * NQ);
 }
 
-// First one thread per (utterance, sum) adds that sum's chunks in chunk order; then one thread per utterance: zero-mean
-// inner products -> pair (dB), permutation scores, arg-max, the gradient's three coefficients per estimate; thread 0 finally
-// adds the best scores in utterance order.  Values that are indexed at run time (the utterance's sums, the pair matrix in
-// fp64, the best scores) live in the workspace, not in registers.
+// Between gather_chunks and tally_scores, one thread per utterance: zero-mean inner products -> pair (dB), permutation
+// scores, arg-max, the gradient's three coefficients per estimate.  Values that are indexed at run time (the utterance's
+// sums, the pair matrix in fp64, the best scores) live in the workspace, not in registers.
 __global__ __launch_bounds__(256) void sisdr_finalize_kernel(const double* __restrict__ partial, int nch,
                                                              const int32_t* __restrict__ nsamp, int B, int S,
                                                              const float* __restrict__ count_dev, double* __restrict__ best_score,
                                                              double* __restrict__ pair64, double* __restrict__ sums, float* __restrict__ pair,
                                                              float* __restrict__ perm_score, int32_t* __restrict__ best_perm,
                                                              float* __restrict__ out, float* __restrict__ coef) {
-  const int NQ = 4 * S + S * S;
+  const int NQ = nq_of(S);
   int nperm = 1;
   for (int i = 2; i <= S; ++i) nperm *= i;
   const double count = count_dev ? (double)count_dev[0] : (double)B;
   const double eps = 1e-30, kappa = 10.0 / log(10.0);
-  for (int idx = threadIdx.x; idx < B * NQ; idx += 256) {
-    const int u = idx / NQ, q = idx - u * NQ;
-    const int mych = (nsamp[u] + CHUNK - 1) / CHUNK;
-    double a = 0.0;
-    for (int c = 0; c < mych; ++c) a += partial[((int64_t)u * nch + c) * NQ + q];
-    sums[idx] = a;
-  }
-  __syncthreads();
+  gather_chunks(partial, nch, nsamp, B, NQ, sums);
   for (int u = threadIdx.x; u < B; u += 256) {
     const double n = (double)nsamp[u];
     auto total = [&](int q) { return sums[u * NQ + q]; };
@@ -159,25 +132,14 @@ __global__ __launch_bounds__(256) void sisdr_finalize_kernel(const double* __res
       co[2] = (float)cC;
     }
   }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double tot = 0.0;
-    for (int u = 0; u < B; ++u) tot += best_score[u];
-    out[0] = (float)(-tot / count);
-    out[1] = (float)count;
-    out[2] = (float)tot;
-  }
-}
-
-size_t partial_bytes(int B, int S, int max_samples) {
-  return sk_align((size_t)B * sk_cdiv(max_samples, CHUNK) * (4 * S + S * S) * sizeof(double), 256);
+  tally_scores(best_score, B, count, out);
 }
 
 }  // namespace
 
 extern "C" size_t sk_sisdr_workspace_bytes(int B, int S, int max_samples) {
   if (B <= 0 || S < 1 || S > MAXS || max_samples <= 0) return 0;
-  return partial_bytes(B, S, max_samples) + sk_align((size_t)B * (1 + 3 * MAXS * MAXS) * sizeof(double), 256);  // + best scores, fp64 pair matrix, sums
+  return partial_bytes(B, nq_of(S), max_samples) + sk_align((size_t)B * (1 + 3 * MAXS * MAXS) * sizeof(double), 256);  // + best scores, fp64 pair matrix, sums
 }
 
 extern "C" int sk_sisdr_pit_fwd(const float* est, const int64_t* est_offs, const void* ref, int pcm16,
@@ -190,20 +152,13 @@ extern "C" int sk_sisdr_pit_fwd(const float* est, const int64_t* est_offs, const
   SK_CHECK_ARG(B > 0 && B <= 65535 && max_samples > 0, "sk_sisdr_pit_fwd: bad sizes");
   const int nch = (int)sk_cdiv(max_samples, CHUNK);
   double* partial = (double*)ws;
-  double* best_score = (double*)((char*)ws + partial_bytes(B, S, max_samples));
+  double* best_score = (double*)((char*)ws + partial_bytes(B, nq_of(S), max_samples));
   double* pair64 = best_score + B;
   double* sums = pair64 + (size_t)B * MAXS * MAXS;  // B x (4 S + S^2) <= B x 2 MAXS^2
   dim3 grid((unsigned)nch, (unsigned)B);
   hipStream_t st = (hipStream_t)stream;
-#define SK_SISDR_SUMS(NS) \
-  hipLaunchKernelGGL(sisdr_sums_kernel<NS>, grid, dim3(256), 0, st, est, est_offs, ref, pcm16, ref_offs, nsamp, nch, partial)
-  switch (S) {
-    case 1: SK_SISDR_SUMS(1); break;
-    case 2: SK_SISDR_SUMS(2); break;
-    case 3: SK_SISDR_SUMS(3); break;
-    default: SK_SISDR_SUMS(4); break;
-  }
-#undef SK_SISDR_SUMS
+  const sums_kernel_t sums_kernel[MAXS] = {sisdr_sums_kernel<1>, sisdr_sums_kernel<2>, sisdr_sums_kernel<3>, sisdr_sums_kernel<4>};
+  hipLaunchKernelGGL(sums_kernel[S - 1], grid, dim3(256), 0, st, est, est_offs, ref, pcm16, ref_offs, nsamp, nch, partial);
   SK_CHECK_LAUNCH("sisdr_sums_kernel");
   hipLaunchKernelGGL(sisdr_finalize_kernel, dim3(1), dim3(256), 0, st, partial, nch, nsamp, B, S, count_dev, best_score, pair64, sums, pair,
                      perm_score, best_perm, out, coef);

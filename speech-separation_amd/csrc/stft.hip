@@ -9,13 +9,15 @@
 // engine's packed rows, and sisdr_grad_kernel, its adjoint fused with the SI-SDR gradient -- the STFT kernel with another
 // sample loader and another epilogue (2 x 128 samples + 257 complex bins in, 257 gradients out per frame and source).
 // The mixture-invariant loss (mixit.hip) adds mixit_grad_kernel, the same adjoint with one transform per (utterance, reference)
-// whose result goes to the column block of every estimate assigned to that reference.
+// whose result goes to the column block of every estimate assigned to that reference.  Both are grad_tiles, the one tile
+// loop of the adjoint, called with the loss's own sample formula and store.
 // The phase-sensitive loss adds stft_psa_kernel, the STFT kernel over the S + 1 signals of an utterance.  STOI scoring, which
 // shares the FFT alone, is stoi.hip.
 //
 // Reference semantics restated: librosa.core.stft / istft as used at
 // steps/extract_feats.py:85-89,104-105 and steps/reconstruct_sources.py:39-42 (see oracle/stft.py).
 #include "fft512.h"
+#include "wave_loss.h"
 
 namespace {
 
@@ -499,61 +501,53 @@ __global__ __launch_bounds__(256, 3) void istft_rows_kernel(const float2* __rest
   }
 }
 
-// ---- adjoint of mask-apply + iSTFT, fused with the SI-SDR gradient (include/sepkern.h, sk_sisdr_mask_grad).
-// stft_kernel<frame-major> with another sample loader and another epilogue: the "signal" of (utterance j, estimate k) is
-//   g[p] = (A e_k[n] + B r_i[n] + C) * gscale / wss[p],  n = p - 256 in [0, L_j), 0 elsewhere, i = best permutation's source,
+// ---- adjoint of mask-apply + iSTFT, fused with a waveform loss's gradient: the tile loop of sisdr_grad_kernel and
+// mixit_grad_kernel.  stft_kernel<frame-major> with another sample loader and another epilogue: the "signal" of utterance u is
+//   g[p] = sample(n) / wss[p],  n = p - 256 in [0, L_u), 0 elsewhere   (sample: the loss's gradient at n, gscale included),
 // framed WITHOUT reflection (frame t = g[tH .. tH + 512)); each bin U[t][f] of its windowed transform is contracted with the
-// mixture's bin on the way out: dmask[offs[t] + j][k * 257 + f] = (c_f / 512) (Re X Re U + Im X Im U), c_f = 1 at f = 0, 256, else 2.
-__global__ __launch_bounds__(256, 4) void sisdr_grad_kernel(const float* __restrict__ est, const int64_t* __restrict__ est_offs,
-                                                            const void* __restrict__ ref, int pcm16,
-                                                            const int64_t* __restrict__ ref_offs,
-                                                            const int32_t* __restrict__ nframes,
-                                                            const int32_t* __restrict__ best_perm, const float* __restrict__ coef,
-                                                            const float* __restrict__ gscale, const float2* __restrict__ mix,
-                                                            const int32_t* __restrict__ offs, int S, float* __restrict__ dmask,
-                                                            int ld) {
+// mixture's bin on the way out: put(at, (c_f / 512) (Re X Re U + Im X Im U)), c_f = 1 at f = 0, 256, else 2, where `at` is
+// column f of dmask's row offs[t] + u; put adds the column block(s) of the estimate(s) the signal belongs to.
+// A block transforms tiles tile0 .. tile0 + TPB - 1 (tile0 * FPB < T is the caller's check); all 256 threads arrive together.
+template <class Sample, class Put>
+__device__ __forceinline__ void grad_tiles(int u, int T, int tile0, const float2* __restrict__ mix, const int32_t* __restrict__ offs,
+                                           float* __restrict__ dmask, int ld, Sample sample, Put put) {
   __shared__ __attribute__((aligned(16))) float smp[NFFT + (FPB - 1) * HOP];
   __shared__ __attribute__((aligned(16))) float win[NFFT];
   __shared__ float2 tw[NFFT];
   __shared__ float2 t256[256];
   __shared__ float xch[16][16 * XLD];
 
-  const int us = blockIdx.y;
-  const int u = us / S, ks = us - u * S;
-  const int T = nframes[u];
   const int L = HOP * (T - 1);
-  const int tile0 = blockIdx.x * TPB;
-  if (tile0 * FPB >= T) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int perm[SK_MAXS];
-  sk_nth_perm(best_perm[u], S, perm);
-  int src = perm[0];
-#pragma unroll
-  for (int q = 1; q < SK_MAXS; ++q) src = (q < S && ks == q) ? perm[q] : src;
-  const float gs = gscale[0];
-  const float cA = coef[3 * us] * gs, cB = coef[3 * us + 1] * gs * (pcm16 ? 1.0f / 32768.0f : 1.0f), cC = coef[3 * us + 2] * gs;
-  const float* const ep = est + est_offs[us];
-  const int64_t roff = ref_offs[u * S + src];
   constexpr int SPAN = NFFT + (FPB - 1) * HOP, SPT = (SPAN + 255) / 256;
 
-  // every sample a thread loads has the same position m0 inside its hop (tiles start on hop boundaries, 256 = 2 hops)
+  // Every sample a thread loads has the same position m0 inside its hop (tiles start on hop boundaries, 256 = 2 hops).
+  // The window-sum-square of a hop that four frames cover is ((w3^2 + w2^2) + w1^2) + w0^2 with w2^2 rounded and the three
+  // other squares fused into their adds -- the contraction the compiler chose for this sum from the start (it may as well fuse
+  // w2^2 and round w3^2: another last bit in every sample), written out here; edge hops add the rounded squares.  Nothing
+  // in the loader is left to the file's contraction setting.
   const int m0 = tid & (HOP - 1);
-  float wsq[4];
+  float wsq[4], inv_full;
+  {
+#pragma clang fp contract(off)
+    float w[4];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float w = g_hann512[q * HOP + m0];
-    wsq[q] = w * w;
+    for (int q = 0; q < 4; ++q) {
+      w[q] = g_hann512[q * HOP + m0];
+      wsq[q] = w[q] * w[q];
+    }
+    inv_full = 1.0f / __builtin_fmaf(w[0], w[0], __builtin_fmaf(w[1], w[1], __builtin_fmaf(w[3], w[3], wsq[2])));
   }
-  const float inv_full = 1.0f / (((wsq[3] + wsq[2]) + wsq[1]) + wsq[0]);  // the order istft_overlap_add sums in
 
   auto fetch = [&](int t0, float (&r)[SPT]) {
+#pragma clang fp contract(off)
 #pragma unroll
     for (int q = 0; q < SPT; ++q) {
       const int i = tid + 256 * q;
       const int p = t0 * HOP + i, n = p - NFFT / 2;
       float v = 0.f;
       if (i < SPAN && n >= 0 && n < L) {
-        const float rv = pcm16 ? (float)((const int16_t*)ref)[roff + n] : ((const float*)ref)[roff + n];
+        const float sv = sample(n);
         const int hp = p >> 7;  // frames hp - 3 .. hp cover p
         float inv = inv_full;
         if (hp < 3 || hp >= T) {
@@ -563,7 +557,7 @@ __global__ __launch_bounds__(256, 4) void sisdr_grad_kernel(const float* __restr
             if (hp - qq >= 0 && hp - qq < T) wss += wsq[qq];
           inv = wss > 1.17549435e-38f ? 1.0f / wss : 1.0f;
         }
-        v = (cA * ep[n] + cB * rv + cC) * inv;
+        v = sv * inv;
       }
       r[q] = v;
     }
@@ -609,179 +603,8 @@ __global__ __launch_bounds__(256, 4) void sisdr_grad_kernel(const float* __restr
     const int64_t row = active ? (int64_t)offs[t0 + fr] + u : 0;
     const float2* const xlo = mix + row * NBIN + j;
     const float2* const xhi = mix + row * NBIN + (256 - j);
-    float* const dlo = dmask + row * ld + ks * NBIN + j;
-    float* const dhi = dmask + row * ld + ks * NBIN + (256 - j);
-    if (active) {
-#pragma unroll
-      for (int k2 = 0; k2 < 8; ++k2) {
-        v2f zc;
-        zc.x = __shfl(z[15 - k2].x, partner, 64);
-        zc.y = __shfl(z[15 - k2].y, partner, 64);
-        if (j == 0) zc = z[(16 - k2) & 15];
-        const v2f zk = z[k2], cz = conj(zc);
-        const int k = j + 16 * k2;
-        const v2f A = 0.5f * (zk + cz), Bt = cmul(ld2(&tw[k]), 0.5f * mul_mi(zk - cz));
-        const v2f ua = A + Bt, ub = conj(A - Bt);  // U[k], U[256 - k]
-        const v2f xa = ld2(xlo + 16 * k2), xb = ld2(xhi - 16 * k2);
-        const float sa = (k == 0) ? 1.0f / 512.0f : 2.0f / 512.0f;  // bin 256 - k is the Nyquist bin exactly when k == 0
-        dlo[16 * k2] = sa * (xa.x * ua.x + xa.y * ua.y);
-        dhi[-16 * k2] = sa * (xb.x * ub.x + xb.y * ub.y);
-      }
-      if (j == 0) {  // bin 128 pairs with itself
-        const v2f zk = z[8], cz = conj(zk);
-        const v2f ua = 0.5f * (zk + cz) + cmul(ld2(&tw[128]), 0.5f * mul_mi(zk - cz));
-        const v2f xa = ld2(xlo + 128);
-        dlo[128] = (2.0f / 512.0f) * (xa.x * ua.x + xa.y * ua.y);
-      }
-    }
-    __syncthreads();  // every wave is done with smp
-    if (more) {
-      stash(pre);
-      __syncthreads();
-    }
-  }
-}
-
-// ---- adjoint of mask-apply + iSTFT, fused with the mixture-invariant loss's gradient (include/sepkern.h, sk_mixit_mask_grad).
-// sisdr_grad_kernel with another sample loader and another epilogue.  The gradient signal of reference n's group,
-//   g[p] = (D_n gscale) (sum_{l in n} e_l[t] - x_n[t]) / wss[p],  t = p - 256 in [0, L_j), 0 elsewhere,
-// is the same for every estimate of the group, and so is its contraction with the mixture's spectrum: blockIdx.y = j * 2 + n,
-// ONE transform, and the epilogue stores each contracted bin into the column block of every member.  The members (bits of
-// best_code[j] equal to n, ascending) and their sample streams are wavefront-uniform; an empty group leaves before the first
-// barrier.  The groups partition the estimates, so every column < M * 257 of a row is written once, by one lane.
-__global__ __launch_bounds__(256, 4) void mixit_grad_kernel(const float* __restrict__ est, const int64_t* __restrict__ est_offs,
-                                                            const void* __restrict__ ref, int pcm16,
-                                                            const int64_t* __restrict__ ref_offs,
-                                                            const int32_t* __restrict__ nframes,
-                                                            const int32_t* __restrict__ best_code, const float* __restrict__ coef,
-                                                            const float* __restrict__ gscale, const float2* __restrict__ mix,
-                                                            const int32_t* __restrict__ offs, int M, float* __restrict__ dmask,
-                                                            int ld) {
-  __shared__ __attribute__((aligned(16))) float smp[NFFT + (FPB - 1) * HOP];
-  __shared__ __attribute__((aligned(16))) float win[NFFT];
-  __shared__ float2 tw[NFFT];
-  __shared__ float2 t256[256];
-  __shared__ float xch[16][16 * XLD];
-
-  const int un = blockIdx.y;
-  const int u = un >> 1, grp = un & 1;
-  const int T = nframes[u];
-  const int L = HOP * (T - 1);
-  const int tile0 = blockIdx.x * TPB;
-  if (tile0 * FPB >= T) return;
-  // the group's members, ascending: their sample streams and their column blocks (slots >= nm repeat the first member)
-  const int code = __builtin_amdgcn_readfirstlane(best_code[u]);
-  int nm = 0, col[SK_MAXS];
-  const float* ep[SK_MAXS];
-#pragma unroll
-  for (int q = 0; q < SK_MAXS; ++q) {
-    col[q] = 0;
-    ep[q] = est;
-  }
-#pragma unroll
-  for (int k = SK_MAXS - 1; k >= 0; --k)  // descending, each member pushed to the front: slot 0 ends as the first member
-    if (k < M && ((code >> k) & 1) == grp) {
-#pragma unroll
-      for (int q = SK_MAXS - 1; q > 0; --q) {
-        col[q] = col[q - 1];
-        ep[q] = ep[q - 1];
-      }
-      col[0] = k * NBIN;
-      ep[0] = est + est_offs[u * M + k];
-      ++nm;
-    }
-  if (nm == 0) return;  // block-uniform: nobody waits at a barrier
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float cD = coef[un] * gscale[0];
-  const float xs = pcm16 ? 1.0f / 32768.0f : 1.0f;
-  const int64_t roff = ref_offs[un];
-  constexpr int SPAN = NFFT + (FPB - 1) * HOP, SPT = (SPAN + 255) / 256;
-
-  // every sample a thread loads has the same position m0 inside its hop (tiles start on hop boundaries, 256 = 2 hops)
-  const int m0 = tid & (HOP - 1);
-  float wsq[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const float w = g_hann512[q * HOP + m0];
-    wsq[q] = w * w;
-  }
-  const float inv_full = 1.0f / (((wsq[3] + wsq[2]) + wsq[1]) + wsq[0]);  // the order istft_overlap_add sums in
-
-  auto fetch = [&](int t0, float (&r)[SPT]) {
-#pragma unroll
-    for (int q = 0; q < SPT; ++q) {
-      const int i = tid + 256 * q;
-      const int p = t0 * HOP + i, n = p - NFFT / 2;
-      float v = 0.f;
-      if (i < SPAN && n >= 0 && n < L) {
-        const float rv = pcm16 ? (float)((const int16_t*)ref)[roff + n] : ((const float*)ref)[roff + n];
-        float m = ep[0][n];
-        if (nm > 1) m += ep[1][n];
-        if (nm > 2) m += ep[2][n];
-        if (nm > 3) m += ep[3][n];
-        const int hp = p >> 7;  // frames hp - 3 .. hp cover p
-        float inv = inv_full;
-        if (hp < 3 || hp >= T) {
-          float wss = 0.f;
-#pragma unroll
-          for (int qq = 3; qq >= 0; --qq)
-            if (hp - qq >= 0 && hp - qq < T) wss += wsq[qq];
-          inv = wss > 1.17549435e-38f ? 1.0f / wss : 1.0f;
-        }
-        v = cD * (m - rv * xs) * inv;
-      }
-      r[q] = v;
-    }
-  };
-  auto stash = [&](const float (&r)[SPT]) {
-#pragma unroll
-    for (int q = 0; q < SPT; ++q) {
-      const int i = tid + 256 * q;
-      if (i < SPAN) smp[i] = r[q];
-    }
-  };
-
-  for (int i = tid; i < NFFT; i += 256) {
-    tw[i] = g_tw512[i];
-    win[i] = g_hann512[i];
-  }
-  t256[tid] = g_tw512[(2 * (tid & 15) * (tid >> 4)) & 511];
-  float pre[SPT];
-  fetch(tile0 * FPB, pre);
-  stash(pre);
-  __syncthreads();
-
-  const int j = lane & 15, g = lane >> 4;
-  const int fr = 4 * wave + g;
-  const int partner = (lane & 48) | ((16 - j) & 15);
-  for (int ti = 0; ti < TPB; ++ti) {
-    const int t0 = (tile0 + ti) * FPB;
-    if (t0 >= T) break;  // block-uniform
-    const int nfr = min(FPB, T - t0);
-    const bool more = ti + 1 < TPB && t0 + FPB < T;
-    if (more) fetch(t0 + FPB, pre);
-    const bool active = fr < nfr;
-    v2f z[16];
-#pragma unroll
-    for (int n1 = 0; n1 < 16; ++n1) {
-      const v2f sm = *reinterpret_cast<const v2f*>(&smp[fr * HOP + 32 * n1 + 2 * j]);
-      const v2f w = *reinterpret_cast<const v2f*>(&win[32 * n1 + 2 * j]);
-      z[n1] = sm * w;
-    }
-    fft256_g16(z, xch[4 * wave + g], t256, j);
-
-    // real-FFT split and contraction as in sisdr_grad_kernel; each value goes to the column block of every member
-    const int64_t row = active ? (int64_t)offs[t0 + fr] + u : 0;
-    const float2* const xlo = mix + row * NBIN + j;
-    const float2* const xhi = mix + row * NBIN + (256 - j);
     float* const dlo = dmask + row * ld + j;
     float* const dhi = dmask + row * ld + (256 - j);
-    auto put = [&](float* at, float v) {
-      at[col[0]] = v;
-      if (nm > 1) at[col[1]] = v;
-      if (nm > 2) at[col[2]] = v;
-      if (nm > 3) at[col[3]] = v;
-    };
     if (active) {
 #pragma unroll
       for (int k2 = 0; k2 < 8; ++k2) {
@@ -811,6 +634,104 @@ __global__ __launch_bounds__(256, 4) void mixit_grad_kernel(const float* __restr
       __syncthreads();
     }
   }
+}
+
+// SI-SDR (include/sepkern.h, sk_sisdr_mask_grad): blockIdx.y = (utterance j, estimate k); i = the best permutation's source,
+//   sample(n) = (A e_k[n] + B r_i[n]) + C   with A, B, C = coef * gscale (B also carries int16 PCM's 2^-15),
+// as two rounded products, their sum, plus C: no fused multiply-add, whatever the file's contraction setting.
+__global__ __launch_bounds__(256, 4) void sisdr_grad_kernel(const float* __restrict__ est, const int64_t* __restrict__ est_offs,
+                                                            const void* __restrict__ ref, int pcm16,
+                                                            const int64_t* __restrict__ ref_offs,
+                                                            const int32_t* __restrict__ nframes,
+                                                            const int32_t* __restrict__ best_perm, const float* __restrict__ coef,
+                                                            const float* __restrict__ gscale, const float2* __restrict__ mix,
+                                                            const int32_t* __restrict__ offs, int S, float* __restrict__ dmask,
+                                                            int ld) {
+  const int us = blockIdx.y;
+  const int u = us / S, ks = us - u * S;
+  const int T = nframes[u];
+  const int tile0 = blockIdx.x * TPB;
+  if (tile0 * FPB >= T) return;
+  int perm[SK_MAXS];
+  sk_nth_perm(best_perm[u], S, perm);
+  int src = perm[0];
+#pragma unroll
+  for (int q = 1; q < SK_MAXS; ++q) src = (q < S && ks == q) ? perm[q] : src;
+  const float gs = gscale[0];
+  const float cA = coef[3 * us] * gs, cB = coef[3 * us + 1] * gs * (pcm16 ? 1.0f / 32768.0f : 1.0f), cC = coef[3 * us + 2] * gs;
+  const float* const ep = est + est_offs[us];
+  const int64_t roff = ref_offs[u * S + src];
+  grad_tiles(
+      u, T, tile0, mix, offs, dmask, ld,
+      [&](int n) {
+#pragma clang fp contract(off)
+        const float a = cA * ep[n], b = cB * ref_raw(ref, pcm16, roff, n);
+        return (a + b) + cC;
+      },
+      [&](float* at, float v) { at[ks * NBIN] = v; });
+}
+
+// MixIT (include/sepkern.h, sk_mixit_mask_grad): blockIdx.y = j * 2 + n, ONE transform per (utterance j, reference n), whose
+// gradient signal and contraction are the same for every estimate of n's group; put stores each bin into every member's
+// column block.  With m = the members' estimates added in ascending order, D = coef * gscale and xs = int16 PCM's 2^-15 (or 1),
+//   sample(t) = D * fma(-x_n[t], xs, m):   the adds, ONE fused multiply-add, one product.
+// The members (bits of best_code[j] equal to n) and their sample streams are wavefront-uniform; an empty group leaves before
+// the first barrier.  The groups partition the estimates, so every column < M * 257 of a row is written once, by one lane.
+__global__ __launch_bounds__(256, 4) void mixit_grad_kernel(const float* __restrict__ est, const int64_t* __restrict__ est_offs,
+                                                            const void* __restrict__ ref, int pcm16,
+                                                            const int64_t* __restrict__ ref_offs,
+                                                            const int32_t* __restrict__ nframes,
+                                                            const int32_t* __restrict__ best_code, const float* __restrict__ coef,
+                                                            const float* __restrict__ gscale, const float2* __restrict__ mix,
+                                                            const int32_t* __restrict__ offs, int M, float* __restrict__ dmask,
+                                                            int ld) {
+  const int un = blockIdx.y;
+  const int u = un >> 1, grp = un & 1;
+  const int T = nframes[u];
+  const int tile0 = blockIdx.x * TPB;
+  if (tile0 * FPB >= T) return;
+  // the group's members, ascending: their sample streams and their column blocks (slots >= nm repeat the first member)
+  const int code = __builtin_amdgcn_readfirstlane(best_code[u]);
+  int nm = 0, col[SK_MAXS];
+  const float* ep[SK_MAXS];
+#pragma unroll
+  for (int q = 0; q < SK_MAXS; ++q) {
+    col[q] = 0;
+    ep[q] = est;
+  }
+#pragma unroll
+  for (int k = SK_MAXS - 1; k >= 0; --k)  // descending, each member pushed to the front: slot 0 ends as the first member
+    if (k < M && ((code >> k) & 1) == grp) {
+#pragma unroll
+      for (int q = SK_MAXS - 1; q > 0; --q) {
+        col[q] = col[q - 1];
+        ep[q] = ep[q - 1];
+      }
+      col[0] = k * NBIN;
+      ep[0] = est + est_offs[u * M + k];
+      ++nm;
+    }
+  if (nm == 0) return;  // block-uniform: nobody waits at a barrier
+  const float cD = coef[un] * gscale[0];
+  const float xs = pcm16 ? 1.0f / 32768.0f : 1.0f;
+  const int64_t roff = ref_offs[un];
+  grad_tiles(
+      u, T, tile0, mix, offs, dmask, ld,
+      [&](int n) {
+#pragma clang fp contract(off)
+        const float rv = ref_raw(ref, pcm16, roff, n);
+        float m = ep[0][n];
+        if (nm > 1) m += ep[1][n];
+        if (nm > 2) m += ep[2][n];
+        if (nm > 3) m += ep[3][n];
+        return cD * __builtin_fmaf(-rv, xs, m);
+      },
+      [&](float* at, float v) {
+        at[col[0]] = v;
+        if (nm > 1) at[col[1]] = v;
+        if (nm > 2) at[col[2]] = v;
+        if (nm > 3) at[col[3]] = v;
+      });
 }
 
 // ---- phase-sensitive targets (include/sepkern.h, sk_stft_psa; the definition is sepkern/psa.py's).

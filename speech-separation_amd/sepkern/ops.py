@@ -871,22 +871,32 @@ def mask_istft_rows(mixc, mask, pk, S, est_offs=None, repeat=1):
     return est, d_offs, offsets
 
 
-def sisdr_descriptors(pk, sig_offs, S):
-    """The small device tables of one batch's SI-SDR loss, uploaded in one go BEFORE the network runs: est_offs (B*S) int64 as
-    mask_istft_rows lays the estimates out, ref_offs (B*S) int64 from sig_offs = {'source<i>': [offset of utterance j]}, nsamp
-    (B) int32 = 128 (T_j - 1)."""
-    offsets, _ = _est_offsets(pk, S)
-    refs = [int(sig_offs["source%d" % (i + 1)][j]) for j in range(pk.B) for i in range(S)]
+# ----------------------------------------------------------------------------- waveform losses: SI-SDR uPIT and MixIT
+MIXIT_NREF = 2
+
+
+def _wave_descriptors(pk, sig_offs, n_est, n_ref):
+    """The small device tables of one batch's waveform loss, uploaded in one go BEFORE the network runs: est_offs (B*n_est)
+    int64 as mask_istft_rows lays the estimates out, ref_offs (B*n_ref) int64 from sig_offs = {'source<i>': [offset of utterance
+    j]}, nsamp (B) int32 = 128 (T_j - 1)."""
+    offsets, _ = _est_offsets(pk, n_est)
+    refs = [int(sig_offs["source%d" % (i + 1)][j]) for j in range(pk.B) for i in range(n_ref)]
     both = _i64(offsets + refs, pk.device)
-    return dict(est_offs=both[:pk.B * S], ref_offs=both[pk.B * S:], nsamp=(pk.lens - 1) * 128)
+    return dict(est_offs=both[:pk.B * n_est], ref_offs=both[pk.B * n_est:], nsamp=(pk.lens - 1) * 128)
 
 
-def sisdr_pit_fwd(est, est_offs, ref, ref_offs, nsamp, S, max_samples, count_dev=None, repeat=1):
-    """PIT on SI-SDR.  est: flat float32 estimates at est_offs (int64 device, B*S: j * S + k); ref: flat references, float32 or
-    int16 PCM (scaled by 1/32768), reference i of utterance j at ref_offs[j * S + i]; nsamp int32 device (B): samples per
-    utterance; count_dev: optional device scalar replacing B (the global utterance count under data parallelism) ->
-    dict(out (3,) = [-mean best score, count, sum of best scores], pair (B,S,S) dB, perm_score (S!,B), best_perm (B),
-    coef (B,S,3))."""
+def sisdr_descriptors(pk, sig_offs, S):
+    """_wave_descriptors of the SI-SDR loss: S estimates against the S references 'source1' .. 'source<S>'."""
+    return _wave_descriptors(pk, sig_offs, S, S)
+
+
+def mixit_descriptors(pk, sig_offs, M):
+    """_wave_descriptors of the mixture-invariant loss: M estimates against the two mixed recordings 'source1' / 'source2'."""
+    return _wave_descriptors(pk, sig_offs, M, MIXIT_NREF)
+
+
+def _chk_flat_waves(who, est, est_offs, ref, ref_offs, nsamp, count_dev, n_est, n_ref, need):
+    """The flat-waveform arguments of a loss forward -> (pcm16, B); `need` words what est_offs / ref_offs must hold."""
     _chk(est)
     pcm16 = ref.dtype == torch.int16
     _chk(ref, torch.int16 if pcm16 else torch.float32)
@@ -895,8 +905,46 @@ def sisdr_pit_fwd(est, est_offs, ref, ref_offs, nsamp, S, max_samples, count_dev
     _chk(nsamp, torch.int32)
     _chk(count_dev)
     B = int(nsamp.numel())
-    if est_offs.numel() != B * S or ref_offs.numel() != B * S:
-        raise _lib.SepkernError("sisdr_pit_fwd: need B*S estimate and reference offsets")
+    if est_offs.numel() != B * n_est or ref_offs.numel() != B * n_ref:
+        raise _lib.SepkernError("%s: need %s" % (who, need))
+    return pcm16, B
+
+
+def _wave_mask_grad(who, entry, label, row_bytes, est, est_offs, ref, ref_offs, best, coef, gscale, mixc, pk, n_est, ld, out, repeat):
+    """sk_sisdr_mask_grad / sk_mixit_mask_grad (one signature): make or check dmask -- the tail rows of a fresh buffer are
+    zeroed (as pit_mse_bwd leaves them), `out` (>= R rows) is written in place and otherwise left alone --, time, call.
+    row_bytes(pcm16): the algorithmic bytes per frame."""
+    pcm16 = ref.dtype == torch.int16
+    _chk(est)
+    _chk(ref, torch.int16 if pcm16 else torch.float32)
+    _chk(mixc, torch.complex64)
+    _chk(gscale)
+    _chk(coef)
+    _chk(best, torch.int32)
+    if out is None:
+        ld = n_est * 257 if ld is None else int(ld)
+        out = torch.empty(pk.Rp, ld, dtype=torch.float32, device=est.device)
+        if pk.Rp > pk.R:
+            out[pk.R:].zero_()
+    _chk(out)
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < pk.R or mixc.shape[0] < pk.R or not mixc.is_contiguous():
+        raise _lib.SepkernError("%s: dmask / mixture rows do not cover the batch" % who)
+    with _timed(label, repeat * float(pk.R) * row_bytes(pcm16)):
+        for _ in range(repeat):
+            _lib.call(entry, _ptr(est), _ptr(est_offs), _ptr(ref), int(pcm16), _ptr(ref_offs), _ptr(pk.lens), _ptr(best),
+                      _ptr(coef), _ptr(gscale), _ptr(mixc), _ptr(pk.offs), pk.B, n_est, 512, 128, pk.T, _ptr(out),
+                      int(out.stride(0)), _stream())
+    return out
+
+
+def sisdr_pit_fwd(est, est_offs, ref, ref_offs, nsamp, S, max_samples, count_dev=None, repeat=1):
+    """PIT on SI-SDR.  est: flat float32 estimates at est_offs (int64 device, B*S: j * S + k); ref: flat references, float32 or
+    int16 PCM (scaled by 1/32768), reference i of utterance j at ref_offs[j * S + i]; nsamp int32 device (B): samples per
+    utterance; count_dev: optional device scalar replacing B (the global utterance count under data parallelism) ->
+    dict(out (3,) = [-mean best score, count, sum of best scores], pair (B,S,S) dB, perm_score (S!,B), best_perm (B),
+    coef (B,S,3))."""
+    pcm16, B = _chk_flat_waves("sisdr_pit_fwd", est, est_offs, ref, ref_offs, nsamp, count_dev, S, S,
+                               "B*S estimate and reference offsets")
     nperm = 1
     for i in range(2, S + 1):
         nperm *= i
@@ -918,44 +966,12 @@ def sisdr_pit_fwd(est, est_offs, ref, ref_offs, nsamp, S, max_samples, count_dev
 
 def sisdr_mask_grad(est, est_offs, ref, ref_offs, best_perm, coef, gscale, mixc, pk, S, ld=None, out=None, repeat=1):
     """dmask (Rp, ld) = gscale * d loss / d mask of the SI-SDR uPIT loss (sk_sisdr_mask_grad): the SI-SDR gradient and the
-    adjoint of mask-apply + iSTFT in one kernel.  Rows of the batch's frames are written, columns < S*257; the tail rows of a
-    fresh buffer are zeroed (as pit_mse_bwd leaves them); `out` (>= R rows) is written in place and otherwise left alone."""
-    pcm16 = ref.dtype == torch.int16
-    _chk(est)
-    _chk(ref, torch.int16 if pcm16 else torch.float32)
-    _chk(mixc, torch.complex64)
-    _chk(gscale)
-    _chk(coef)
-    _chk(best_perm, torch.int32)
-    if out is None:
-        ld = S * 257 if ld is None else int(ld)
-        out = torch.empty(pk.Rp, ld, dtype=torch.float32, device=est.device)
-        if pk.Rp > pk.R:
-            out[pk.R:].zero_()
-    _chk(out)
-    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < pk.R or mixc.shape[0] < pk.R or not mixc.is_contiguous():
-        raise _lib.SepkernError("sisdr_mask_grad: dmask / mixture rows do not cover the batch")
+    adjoint of mask-apply + iSTFT in one kernel.  Rows of the batch's frames are written, columns < S*257; dmask as
+    _wave_mask_grad makes or checks it."""
     # algorithmic bytes per frame and source: 2 x 128 new samples, the mixture's complex row, 257 gradients out
-    with _timed("sisdr_bwd", repeat * float(pk.R) * S * (128 * (4 + (2 if pcm16 else 4)) + 257 * 8 + 257 * 4)):
-        for _ in range(repeat):
-            _lib.call("sk_sisdr_mask_grad", _ptr(est), _ptr(est_offs), _ptr(ref), int(pcm16), _ptr(ref_offs), _ptr(pk.lens),
-                      _ptr(best_perm), _ptr(coef), _ptr(gscale), _ptr(mixc), _ptr(pk.offs), pk.B, S, 512, 128, pk.T, _ptr(out),
-                      int(out.stride(0)), _stream())
-    return out
-
-
-# ----------------------------------------------------------------------------- mixture-invariant loss (waveform domain)
-MIXIT_NREF = 2
-
-
-def mixit_descriptors(pk, sig_offs, M):
-    """The small device tables of one batch's mixture-invariant loss, uploaded in one go BEFORE the network runs: est_offs (B*M)
-    int64 as mask_istft_rows lays the M estimates out, ref_offs (B*2) int64 from sig_offs = {'source1' / 'source2': [offset of
-    utterance j]}, nsamp (B) int32 = 128 (T_j - 1)."""
-    offsets, _ = _est_offsets(pk, M)
-    refs = [int(sig_offs["source%d" % (n + 1)][j]) for j in range(pk.B) for n in range(MIXIT_NREF)]
-    both = _i64(offsets + refs, pk.device)
-    return dict(est_offs=both[:pk.B * M], ref_offs=both[pk.B * M:], nsamp=(pk.lens - 1) * 128)
+    return _wave_mask_grad("sisdr_mask_grad", "sk_sisdr_mask_grad", "sisdr_bwd",
+                           lambda pcm16: S * (128 * (4 + (2 if pcm16 else 4)) + 257 * 8 + 257 * 4),
+                           est, est_offs, ref, ref_offs, best_perm, coef, gscale, mixc, pk, S, ld, out, repeat)
 
 
 def mixit_fwd(est, est_offs, ref, ref_offs, nsamp, M, max_samples, tau, count_dev=None, repeat=1):
@@ -964,16 +980,8 @@ def mixit_fwd(est, est_offs, ref, ref_offs, nsamp, M, max_samples, tau, count_de
     ref_offs[j * 2 + n]; nsamp int32 device (B): samples per utterance; tau = 10^(-snr_max/10); count_dev: optional device
     scalar replacing B (the global utterance count under data parallelism) ->
     dict(out (3,) = [-mean best score, count, sum of best scores], assign_score (2^M,B) dB, best_code (B), coef (B,2))."""
-    _chk(est)
-    pcm16 = ref.dtype == torch.int16
-    _chk(ref, torch.int16 if pcm16 else torch.float32)
-    _chk(est_offs, torch.int64)
-    _chk(ref_offs, torch.int64)
-    _chk(nsamp, torch.int32)
-    _chk(count_dev)
-    B = int(nsamp.numel())
-    if est_offs.numel() != B * M or ref_offs.numel() != B * MIXIT_NREF:
-        raise _lib.SepkernError("mixit_fwd: need B*M estimate offsets and B*2 reference offsets")
+    pcm16, B = _chk_flat_waves("mixit_fwd", est, est_offs, ref, ref_offs, nsamp, count_dev, M, MIXIT_NREF,
+                               "B*M estimate offsets and B*2 reference offsets")
     dev = est.device
     score = torch.empty(1 << M, B, device=dev)
     best = torch.empty(B, dtype=torch.int32, device=dev)
@@ -993,34 +1001,15 @@ def mixit_fwd(est, est_offs, ref, ref_offs, nsamp, M, max_samples, tau, count_de
 def mixit_mask_grad(est, est_offs, ref, ref_offs, best_code, coef, gscale, mixc, pk, M, ld=None, out=None, repeat=1):
     """dmask (Rp, ld) = gscale * d loss / d mask of the mixture-invariant loss (sk_mixit_mask_grad): one transform per
     (utterance, reference) whose result lands in the column block of every estimate of that reference's group.  Rows of the
-    batch's frames are written, columns < M*257; the tail rows of a fresh buffer are zeroed; `out` (>= R rows) is written in
-    place and otherwise left alone."""
-    pcm16 = ref.dtype == torch.int16
-    _chk(est)
-    _chk(ref, torch.int16 if pcm16 else torch.float32)
-    _chk(mixc, torch.complex64)
-    _chk(gscale)
-    _chk(coef)
-    _chk(best_code, torch.int32)
+    batch's frames are written, columns < M*257; dmask as _wave_mask_grad makes or checks it."""
     _chk(est_offs, torch.int64)
     _chk(ref_offs, torch.int64)
     if est_offs.numel() != pk.B * M or ref_offs.numel() != pk.B * MIXIT_NREF or best_code.numel() != pk.B or coef.numel() != pk.B * MIXIT_NREF:
         raise _lib.SepkernError("mixit_mask_grad: need B*M estimate offsets, B*2 reference offsets and coefficients, B codes")
-    if out is None:
-        ld = M * 257 if ld is None else int(ld)
-        out = torch.empty(pk.Rp, ld, dtype=torch.float32, device=est.device)
-        if pk.Rp > pk.R:
-            out[pk.R:].zero_()
-    _chk(out)
-    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < pk.R or mixc.shape[0] < pk.R or not mixc.is_contiguous():
-        raise _lib.SepkernError("mixit_mask_grad: dmask / mixture rows do not cover the batch")
     # algorithmic bytes per frame: M + 1 x 128 new samples and the mixture's complex row per reference at most, M x 257 gradients out
-    with _timed("mixit_bwd", repeat * float(pk.R) * (128 * (4 * M + MIXIT_NREF * (2 if pcm16 else 4)) + MIXIT_NREF * 257 * 8 + M * 257 * 4)):
-        for _ in range(repeat):
-            _lib.call("sk_mixit_mask_grad", _ptr(est), _ptr(est_offs), _ptr(ref), int(pcm16), _ptr(ref_offs), _ptr(pk.lens),
-                      _ptr(best_code), _ptr(coef), _ptr(gscale), _ptr(mixc), _ptr(pk.offs), pk.B, M, 512, 128, pk.T, _ptr(out),
-                      int(out.stride(0)), _stream())
-    return out
+    return _wave_mask_grad("mixit_mask_grad", "sk_mixit_mask_grad", "mixit_bwd",
+                           lambda pcm16: 128 * (4 * M + MIXIT_NREF * (2 if pcm16 else 4)) + MIXIT_NREF * 257 * 8 + M * 257 * 4,
+                           est, est_offs, ref, ref_offs, best_code, coef, gscale, mixc, pk, M, ld, out, repeat)
 
 
 # ----------------------------------------------------------------------------- phase-sensitive targets (loss=psa / tpsa)

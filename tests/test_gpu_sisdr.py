@@ -28,6 +28,9 @@ F = 257
 # samples per utterance, longest first: ~8 s ... ~0.5 s; frames 501, 261, 160 (a whole number of 16-frame tiles), 71, 38, 31
 # (not multiples of 16; the last shorter than two tiles)
 LENGTHS = [64000, 33333, 20352, 9000, 4800, 3900]
+# the gradient kernel's tile loop at its own boundaries: frames 163 (two workgroups of 5 tiles + 3 frames), 81 (5 tiles + 1),
+# 80 (exactly 5 tiles), 17 (a tile + 1), 16 (a tile), 3 (every hop an edge hop)
+EDGE_LENGTHS = [20780, 10284, 10156, 2092, 1964, 300]
 
 
 @pytest.fixture(scope="module")
@@ -44,14 +47,14 @@ def arch(dev):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(S):
-    return SO.ratio_mask_case(LENGTHS, S, seed=40 + S)
+def _case(S, edge=False):
+    return SO.ratio_mask_case(EDGE_LENGTHS if edge else LENGTHS, S, seed=40 + S)
 
 
 @functools.lru_cache(maxsize=None)
-def _oracle(S):
+def _oracle(S, edge=False):
     """fp64 autograd (loss, dmask per utterance, info) and the float32 evaluation's dmask of the same graph."""
-    c = _case(S)
+    c = _case(S, edge)
     refs = [[OS.pcm16_to_float(r).astype(np.float64) for r in rs] for rs in c["refs_pcm"]]
     out = {}
     for name, dt in (("f64", torch.float64), ("f32", torch.float32)):
@@ -238,6 +241,52 @@ def test_sisdr_mask_grad_against_fp64_autograd(dev, S, as_float):
     got = _dmask_rows(dms, solo["pk"], {"masks": [c["masks"][j]], "specs": [c["specs"][j]]})[0]
     want = _dmask_rows(dm, pk, c)[j]
     assert np.linalg.norm(got - want) <= 1.9e-5 * np.linalg.norm(want)
+
+
+@pytest.mark.parametrize("as_float", [False, True], ids=["int16", "float32"])
+@pytest.mark.parametrize("S", [2, 3, 4])
+def test_sisdr_mask_grad_at_the_tile_loop_boundaries(dev, S, as_float):
+    """EDGE_LENGTHS: the branches of the gradient kernels' shared tile loop, through the SI-SDR kernel.  On the CPU, for these
+    inputs: the oracle's best permutation leads by >= 41.0 / 26.6 / 16.7 dB (S = 2 / 3 / 4), and the float32 evaluation of the
+    graph sits 5.7e-7 / 4.7e-7 / 4.4e-7 (relative L2) from the fp64 one; the gate is 4 x that, as above."""
+    from sepkern import ops
+    c, orc = _case(S, True), _oracle(S, True)
+    _assert_margin(orc["f64"]["info"], "S=%d" % S)
+    B = len(EDGE_LENGTHS)
+    assert [X.shape[1] for X in c["specs"]] == [163, 81, 80, 17, 16, 3]
+    f = _forward(c, dev, as_float)
+    pk, res = f["pk"], f["res"]
+    assert [int(b) for b in res["best_perm"]] == list(orc["f64"]["info"]["best"])
+    one = torch.ones(1, device=dev)
+    args = (f["est"], f["est_offs"], f["ref"], f["ref_offs"], res["best_perm"], res["coef"])
+    dm = ops.sisdr_mask_grad(*args, one, f["mixc"], pk, S)
+    assert dm.shape == (pk.Rp, S * F) and torch.isfinite(dm).all()
+    got = _dmask_rows(dm, pk, c)
+    err = _rel(got, orc["f64"]["dmask"])
+    err32 = _rel(orc["f32"]["dmask"], orc["f64"]["dmask"])
+    print("S=%d %s: dmask relative L2 vs fp64 autograd: kernel %.3g, torch float32 on the CPU %.3g (gate: 4 x)"
+          % (S, "float32" if as_float else "int16", err, err32))
+    assert err <= 4.0 * err32
+    # a second run gives the same bits
+    assert torch.equal(ops.sisdr_mask_grad(*args, one, f["mixc"], pk, S), dm)
+    # a caller's buffer: a canary in the rows >= R and the columns >= S F is untouched, every valid element is written
+    buf = torch.full((pk.Rp + 3, S * F + 3), 7.0, device=dev)
+    ops.sisdr_mask_grad(*args, one, f["mixc"], pk, S, out=buf)
+    assert (buf[pk.R:] == 7.0).all() and (buf[:, S * F:] == 7.0).all()
+    assert torch.equal(buf[:pk.R, :S * F], dm[:pk.R])
+    # A = B = C = 0 gives exact zeros (a canary-filled buffer shows they were written)
+    buf.fill_(7.0)
+    ops.sisdr_mask_grad(f["est"], f["est_offs"], f["ref"], f["ref_offs"], res["best_perm"], torch.zeros_like(res["coef"]), one,
+                        f["mixc"], pk, S, out=buf)
+    assert not buf[:pk.R, :S * F].any() and (buf[pk.R:] == 7.0).all() and (buf[:, S * F:] == 7.0).all()
+    # an utterance alone (with the batch's count) gives the bits it has inside the batch
+    for j in (1, B - 1):
+        solo_c = {k: ([v[j]] if k != "shuffle" else v) for k, v in c.items()}
+        s = _forward(solo_c, dev, as_float, count_dev=torch.full((1,), float(B), device=dev))
+        assert torch.equal(s["res"]["coef"][0], res["coef"][j]) and int(s["res"]["best_perm"][0]) == int(res["best_perm"][j])
+        dms = ops.sisdr_mask_grad(s["est"], s["est_offs"], s["ref"], s["ref_offs"], res["best_perm"][j:j + 1].contiguous(),
+                                  res["coef"][j:j + 1].contiguous(), one, s["mixc"], s["pk"], S)
+        assert np.array_equal(_dmask_rows(dms, s["pk"], solo_c)[0], got[j])
 
 
 # ------------------------------------------------------------------------------------------------ 8: through the arch
