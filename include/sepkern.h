@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 143
+#define SK_VERSION 144
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -229,6 +229,46 @@ size_t sk_wpe_workspace_bytes(int T, int C, int taps, int block_frames, int cont
 int sk_wpe(const void* Y_c64, int64_t y_chan_stride, int64_t y_row_stride, int T, int C, int taps, int delay, int iterations,
            int block_frames, int context_frames, int ref, double loading, void* X_c64, int64_t x_chan_stride, int64_t x_row_stride,
            float* mag_out, int ld_mag, void* G_out_c128, void* ws, sk_stream_t stream);
+
+/* ---------------------------------------------------------------- mask-guided cACGMM spatial clustering (multi-channel recordings)
+ * Between the network and the beamformer: the masks of one microphone are re-estimated from all C channels by a complex
+ * angular central Gaussian mixture model on the directions y / |y| (Ito et al. 2016), with the network's masks as the class
+ * prior of every time-frequency point (Nakatani et al. 2017; guided source separation, Boeddeker et al. 2018).  No counterpart
+ * in the reference; sepkern/cacgmm.py states the definition and restates the arithmetic below in numpy fp64.
+ * Y: complex64 spectra, element (c, t, f) at Y[c*y_chan_stride + t*y_row_stride + f] (elements; unit bin stride, F = 257 bins,
+ * y_row_stride >= 257; this may be sk_wpe's X); prior (T, ld_prior >= S*257) float32 with stream k in columns k*257 ..
+ * (sk_stitch's output); mask_out (T, ld_out >= S*257) float32 likewise, not overlapping prior (neighbouring windows read it).
+ * Blocks and windows are sk_wpe's: block j holds frames [j Lb, min(T, (j+1) Lb)), its window is [max(0, j Lb - Lc),
+ * min(T, (j+1) Lb + Lc)), Lb + 2 Lc <= 4096.  Per (block, bin), on the window, every operand widened to fp64 first:
+ *   n(t) = sum_c |y_c(t)|^2, c ascending; a frame with n(t) == 0 is dead, otherwise z(t) = y(t) / sqrt(n(t))
+ *   p_k(t) = max(m_k, 1e-6) / sum_k' max(m_k', 1e-6), k' ascending, m_k = prior[t][k*257 + f]: fixed over the iterations
+ *   state: one Hermitian B_k per class, I at the start or B_in (nblk, S, 257, C, C) complex128, of which the upper triangle and
+ *          the real part of the diagonal are read.  A state is admitted before it is used: B_k = U^H U by an fp64 Cholesky
+ *          factorisation; class k is reset to I where a pivot is not > 0 or not finite or an entry of U is not finite
+ *   pass:  q_k(t) = ||U_k^-H z(t)||^2 by forward substitution;  l_k(t) = (log p_k(t) - 2 sum_a log U_k[a][a]) - C log q_k(t);
+ *          gamma_k(t) = exp(l_k - max l) / sum_k' exp(l_k' - max l), k' ascending.  Dead frames get gamma_k = p_k and take part
+ *          in no sum; while every class of the cell is the identity the pass is q = 1, gamma = p
+ *   update (q of the old B): n_k = sum_t gamma_k(t), S_k = sum_t (gamma_k(t) / q_k(t)) z z^H, t ascending over the window (upper
+ *          triangle, real diagonal);  B_k' = S_k (C / n_k);  B_k' += (loading Re tr B_k' / C) I;  admitted as above, and reset
+ *          where n_k == 0
+ * `iterations` (0..16) passes with update, then one pass without over the block's own frames:
+ *   mask_out[t][k*257 + f] = float32(gamma_k(t));  B_out (nblk, S, 257, C, C) complex128 = the last state, full Hermitian
+ *   matrices (may be NULL).  With iterations == 0 and no B_in mask_out is float32(p).  The model does not see the scale of B
+ *   or a complex scalar on y(t); with loading > 0 every updated B_k has a condition number of at most C / loading + 1.
+ * One launch on `stream`, one workgroup per (block, bin) with the states, their factors and a chunk of 64 frames in LDS, no
+ * host synchronisation, no atomics, no hand-off between workgroups, every sum in one fixed order: bitwise reproducible, and
+ * the bits do not depend on the strides or on the call count (one call of I iterations = I calls of one chained through
+ * B_out -> B_in).  Every element of mask_out (T x S*257) and of B_out is written exactly once, nothing else is written, and
+ * nothing of Y outside its C x T x 257 elements or of prior outside its T x S*257 is read.  All pointers are device pointers.
+ * SK_EINVAL before anything is launched: C outside 2..8, S outside 2..4, T < 1, iterations outside 0..16, block_frames < 1,
+ * context_frames < 0, block_frames + 2 context_frames > 4096, loading negative or NaN, ld_prior or ld_out < S*257,
+ * y_row_stride < 257, a NULL Y, prior or mask_out.  ws: sk_cacgmm keeps nothing in device memory between its passes;
+ * sk_cacgmm_workspace_bytes is 0 and ws may be NULL.  Not in it, on purpose: a noise class, learned mixture weights,
+ * permutation alignment across bins, S = 1. */
+size_t sk_cacgmm_workspace_bytes(int T, int C, int S, int block_frames, int context_frames);
+int sk_cacgmm(const void* Y_c64, int64_t y_chan_stride, int64_t y_row_stride, const float* prior, int ld_prior, int T, int C, int S,
+              int iterations, int block_frames, int context_frames, double loading, const void* B_in_c128, float* mask_out,
+              int ld_out, void* B_out_c128, void* ws, sk_stream_t stream);
 
 /* ---------------------------------------------------------------- fp32 GEMM (matrix cores)
  * C[M,N] (ldc) = act( opA(A) * opB(B) + bias[n] + (accumulate ? C : 0) ).

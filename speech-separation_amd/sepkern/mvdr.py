@@ -32,7 +32,8 @@ With delta > 0 every N_s that is not zero has a condition number of at most C / 
 N is positive semi-definite, so its eigenvalues lie in [delta tr / C, tr (1 + delta / C)].
 
 Out of the definition, on purpose: S = 1 (which needs a noise class), smoothing of the weights across block edges, the GEV and
-rank-1 variants, dereverberation (WPE).
+rank-1 variants, dereverberation (WPE).  Masks re-estimated from all channels before they steer the beamformers are a stage of
+their own in front of this one: sepkern/cacgmm.py (sk_cacgmm).
 """
 import numpy as np
 

@@ -8,6 +8,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from . import cacgmm as _cacgmm
 
 _WS = {}
 
@@ -776,6 +777,53 @@ def wpe(Y, taps, delay, iterations, block_frames, context_frames, loading, ref=0
             _lib.call("sk_wpe", _ptr(Y), int(Y.stride(0)), int(Y.stride(1)), T, C, K, dl, I, Lb, Lc, ref, float(loading), _ptr(X),
                       int(X.stride(0)), int(X.stride(1)), _ptr(mag), 257, _ptr(G), None, _stream())
     return X[:, :, :257], mag, G
+
+
+# ----------------------------------------------------------------------------- mask-guided cACGMM spatial clustering
+def cacgmm(Y, prior, S, iterations, block_frames, context_frames, loading, B_in=None, want_B=False, out=None, repeat=1):
+    """The masks re-estimated from all channels by a cACGMM whose class prior they are, per block of frames and bin (sk_cacgmm;
+    sepkern/cacgmm.py defines the result).  Y: (C, T, >= 257) complex64 spectra with unit bin stride (any channel and row
+    stride: a view is read where it lies; ops.wpe's X will do), 2 <= C <= 8; prior: (>= T, >= S*257) float32 with unit column
+    stride, stream s in columns s*257 .. (ops.stitch's output); B_in: None or the (nblk, S, 257, C, C) contiguous complex128
+    state to start from (a B of an earlier call); out: a float32 (>= T, >= S*257) buffer with unit column stride to write into
+    (not overlapping prior).
+    -> (mask (T, S*257) float32, B (nblk, S, 257, C, C) complex128 or None); nothing synchronises with the host."""
+    _lib.load()
+    _chk(Y, torch.complex64)
+    _chk(prior)
+    if Y.dim() != 3 or Y.shape[2] < 257 or Y.stride(2) != 1:
+        raise _lib.SepkernError("cacgmm: Y must be (C, T, >= 257) complex64 with unit bin stride")
+    C, T = int(Y.shape[0]), int(Y.shape[1])
+    S, I, Lb, Lc = int(S), int(iterations), int(block_frames), int(context_frames)
+    try:                                    # the kernel's own limits, before anything is sized by them
+        _cacgmm.check_arguments(C, S, T, I, Lb, Lc, float(loading), y_row_stride=int(Y.stride(1)))
+    except ValueError as e:
+        raise _lib.SepkernError(str(e))
+    if prior.dim() != 2 or prior.stride(1) != 1 or prior.shape[0] < T or prior.shape[1] < S * 257:
+        raise _lib.SepkernError("cacgmm: prior must be (>= T, >= S*257) float32 with unit column stride")
+    dev = Y.device
+    nblk = -(-T // Lb)
+    shape_B = (nblk, S, 257, C, C)
+    if B_in is not None:
+        _chk(B_in, torch.complex128)
+        if tuple(B_in.shape) != shape_B or not B_in.is_contiguous():
+            raise _lib.SepkernError("cacgmm: B_in must be (nblk, S, 257, C, C) contiguous complex128")
+    if out is None:
+        out = torch.empty(T, S * 257, dtype=torch.float32, device=dev)
+    _chk(out)
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < T or out.shape[1] < S * 257:
+        raise _lib.SepkernError("cacgmm: out must be (>= T, >= S*257) float32 with unit column stride")
+    B = torch.empty(shape_B, dtype=torch.complex128, device=dev) if want_B else None
+    # algorithmic bytes: every iteration reads its window of Y and of the prior once, the block is read once more and the
+    # masks written; the windows overlap by the context
+    win = float(min(T, Lb + 2 * Lc)) * nblk
+    per = 257.0 * (C * 8 + S * 4) * (I * win + T) + 257.0 * S * 4 * T
+    per += 257.0 * nblk * S * C * C * 16 * ((B_in is not None) + bool(want_B))
+    with _timed("cacgmm", repeat * per):
+        for _ in range(repeat):
+            _lib.call("sk_cacgmm", _ptr(Y), int(Y.stride(0)), int(Y.stride(1)), _ptr(prior), int(prior.stride(0)), T, C, S, I, Lb, Lc,
+                      float(loading), _ptr(B_in), _ptr(out), int(out.stride(0)), _ptr(B), None, _stream())
+    return out[:T, :S * 257], B
 
 
 # ----------------------------------------------------------------------------- PIT-MSE

@@ -10,6 +10,7 @@ stitch.memory_bytes(T, W, Hn, S) = K W S 257 4 bytes, about 0.9 GB for an hour a
 import numpy as np
 import torch
 
+from . import cacgmm as cg
 from . import mvdr as mv
 from . import ops
 from . import stitch as st
@@ -51,7 +52,8 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
                        working_rate=WORKING_RATE, want_float=True, want_pcm=False, return_details=False, ref_channel=0,
                        mvdr_block_frames=200, mvdr_context_blocks=1, mvdr_loading=1e-3, mvdr_postmask=False, mvdr=True,
                        wpe=False, wpe_taps=10, wpe_delay=3, wpe_iterations=3, wpe_block_frames=600, wpe_context_frames=0,
-                       wpe_loading=1e-3):
+                       wpe_loading=1e-3, cacgmm=False, cacgmm_iterations=5, cacgmm_block_frames=200, cacgmm_context_frames=200,
+                       cacgmm_loading=1e-3):
     """model: a uPIT SepDNN on the GPU; pcm: 1-D tensor of the recording's samples, int16 PCM or float32, at sample_rate Hz
     (moved to the model's device if it is not there; resampled on the device when sample_rate is not working_rate, the rate the
     model was trained at).  -> (wav (S, L) float32 or None, pcm16 (S, L) int16 or None) at working_rate,
@@ -71,7 +73,13 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
     replaces Y everywhere downstream: the network sees |X[ref_channel]| (sk_wpe's mag_out), the masks are applied to
     X[ref_channel] (mixc), MVDR runs on X.  The details gain X and keep the untouched Y.  The defaults (10 taps, a delay of 3,
     3 iterations, 9.6 s blocks) are the literature's; they are not tuned.  mvdr=False with wpe and a (C, n) pcm dereverberates
-    with all channels and masks the reference channel instead of beamforming.  Without wpe the calls are those of before."""
+    with all channels and masks the reference channel instead of beamforming.  Without wpe the calls are those of before.
+    cacgmm: between the network and the beamformer the stitched masks are re-estimated from all channels (sk_cacgmm,
+    sepkern/cacgmm.py: a cACGMM per block of cacgmm_block_frames frames and bin, fitted in cacgmm_iterations iterations on the
+    block and cacgmm_context_frames on either side with the network's masks as its class prior, loading cacgmm_loading), on X
+    with wpe.  It needs a (C, n) pcm and mvdr: the refined masks steer sk_mvdr and nothing else -- mvdr_postmask, the details'
+    stitched and everything upstream keep the network's masks.  The details gain cacgmm_masks.  The defaults (5 iterations,
+    3.2 s blocks with 3.2 s of context on either side) are untuned.  Without cacgmm the calls and their bits are those of before."""
     if not hasattr(model, "forward_packed"):
         raise SepkernError("separate_recording needs a model with forward_packed (the uPIT arch)")
     st.check_geometry(1, window_frames, hop_frames)
@@ -81,6 +89,11 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
     pcm = torch.as_tensor(pcm)
     if pcm.dim() not in (1, 2) or pcm.dtype not in (torch.int16, torch.float32):
         raise SepkernError("separate_recording: pcm must be a 1-D, or for an array a (C, n), int16 or float32 tensor")
+    if cacgmm:
+        if pcm.dim() != 2 or not mvdr:
+            raise ValueError("separate_recording: cacgmm needs a (C, n) pcm and mvdr")
+        cg.check_arguments(int(pcm.shape[0]), int(model.num_spk), 1, int(cacgmm_iterations), int(cacgmm_block_frames),
+                           int(cacgmm_context_frames), float(cacgmm_loading))
     pcm = pcm.to(dev, non_blocking=True)
     if wpe:
         wp.check_arguments(int(pcm.shape[0]) if pcm.dim() == 2 else 1, 1, int(wpe_taps), int(wpe_delay), int(wpe_iterations),
@@ -138,7 +151,12 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
     if Y is None or not mvdr:
         wav, pcm16 = ops.mask_istft_frames(mixc, stitched, S, want_pcm=want_pcm, want_float=want_float)
     else:
-        weights, Z, _ = ops.mvdr(Y if X is None else X, stitched, S, mvdr_block_frames, mvdr_context_blocks, ref_channel, mvdr_loading)
+        steer = stitched
+        if cacgmm:
+            steer, _ = ops.cacgmm(Y if X is None else X, stitched, S, cacgmm_iterations, cacgmm_block_frames, cacgmm_context_frames,
+                                  cacgmm_loading)
+            details.update(cacgmm_masks=steer)
+        weights, Z, _ = ops.mvdr(Y if X is None else X, steer, S, mvdr_block_frames, mvdr_context_blocks, ref_channel, mvdr_loading)
         wav, pcm16 = ops.mask_istft_streams(Z, stitched if mvdr_postmask else None, S, want_pcm=want_pcm, want_float=want_float)
         details.update(Y=Y, weights=weights, Z=Z)
     if return_details:

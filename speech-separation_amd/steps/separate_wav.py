@@ -18,6 +18,9 @@ beamformed streams are written.  The channels of an ID must share one rate and a
 --wpe dereverberates the spectra first (sk_wpe, sepkern/wpe.py: weighted prediction error over all channels), with or without
 --mvdr and on mono files too; without --mvdr a multi-channel recording is dereverberated with all its channels and the masks
 are applied to --ref-channel.
+
+--cacgmm (with --mvdr, multi-channel recordings only) re-estimates the stitched masks from all channels before they steer the
+beamformers (sk_cacgmm, sepkern/cacgmm.py: a cACGMM spatial mixture model with the network's masks as its class prior).
 """
 import argparse
 import concurrent.futures
@@ -62,6 +65,11 @@ def get_args(argv=None):
   parser.add_argument("--wpe-block-frames", type=int, default=600, help="frames per block of prediction filters")
   parser.add_argument("--wpe-context-frames", type=int, default=0, help="frames on either side of a block its filters are estimated on as well")
   parser.add_argument("--wpe-loading", type=float, default=1e-3, help="diagonal loading of the covariance matrix, relative to its mean diagonal")
+  parser.add_argument("--cacgmm", action="store_true", help="re-estimate the masks from all channels by a mask-guided cACGMM before they steer the beamformers (needs --mvdr)")
+  parser.add_argument("--cacgmm-iterations", type=int, default=5, help="EM iterations of the spatial model (0..16)")
+  parser.add_argument("--cacgmm-block-frames", type=int, default=200, help="frames per block of the spatial model")
+  parser.add_argument("--cacgmm-context-frames", type=int, default=200, help="frames on either side of a block its model is fitted on as well")
+  parser.add_argument("--cacgmm-loading", type=float, default=1e-3, help="diagonal loading of the classes' matrices, relative to their mean diagonal")
   parser.add_argument("--writers", type=int, default=8, help="threads that read the wav inputs and write the wav outputs")
   return parser.parse_args(argv)
 
@@ -70,6 +78,9 @@ def main(argv=None):
   args = get_args(argv)
   if args.mvdr_channel_scps and not (args.mvdr or args.wpe):
     print("separate_wav: --mvdr-channel-scps needs --mvdr", file=sys.stderr)
+    return 1
+  if args.cacgmm and not args.mvdr:
+    print("separate_wav: --cacgmm needs --mvdr", file=sys.stderr)
     return 1
   import eval_qsub
   m = eval_qsub.load_arch(args.arch_file)
@@ -143,7 +154,9 @@ def main(argv=None):
                                     mvdr_loading=args.mvdr_loading, mvdr_postmask=args.mvdr_postmask, mvdr=args.mvdr or not args.wpe,
                                     wpe=args.wpe, wpe_taps=args.wpe_taps, wpe_delay=args.wpe_delay, wpe_iterations=args.wpe_iterations,
                                     wpe_block_frames=args.wpe_block_frames, wpe_context_frames=args.wpe_context_frames,
-                                    wpe_loading=args.wpe_loading)
+                                    wpe_loading=args.wpe_loading, cacgmm=args.cacgmm, cacgmm_iterations=args.cacgmm_iterations,
+                                    cacgmm_block_frames=args.cacgmm_block_frames, cacgmm_context_frames=args.cacgmm_context_frames,
+                                    cacgmm_loading=args.cacgmm_loading)
       out_h = torch.empty(pcm16.shape, dtype=torch.int16).pin_memory()
       out_h.copy_(pcm16, non_blocking=True)
       torch.cuda.synchronize()
