@@ -14,6 +14,9 @@
 // The phase-sensitive loss adds stft_psa_kernel, the STFT kernel over the S + 1 signals of an utterance.  STOI scoring, which
 // shares the FFT alone, is stoi.hip.
 //
+// Shape coverage: tests/test_gpu_stft_family.py runs stft_kernel, istft_kernel, istft_rows_kernel and stft_psa_kernel at the
+// lengths their tile loops branch on, against fp64 (grad_tiles: EDGE_LENGTHS in tests/test_gpu_sisdr.py).
+//
 // Reference semantics restated: librosa.core.stft / istft as used at
 // steps/extract_feats.py:85-89,104-105 and steps/reconstruct_sources.py:39-42 (see oracle/stft.py).
 #include "fft512.h"
