@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 144
+#define SK_VERSION 145
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -701,6 +701,60 @@ int sk_mixit_mask_grad(const float* est, const int64_t* est_offs, const void* re
                        const int32_t* nframes, const int32_t* best_code, const float* coef, const float* gscale,
                        const void* mix_rows_c64, const int32_t* offs, int B, int M, int n_fft, int hop, int max_frames,
                        float* dmask, int ld, sk_stream_t stream);
+
+/* ---------------------------------------------------------------- deep clustering (loss=dpcl; k-means masks)
+ * A second way to separate beside uPIT (Hershey et al. 2016; the low-rank objective of Isik et al. 2016; the sigmoid + unit-norm
+ * embedding and the magnitude-ratio weights of Wang et al. 2018): the network emits a D-dimensional embedding per
+ * time-frequency point, the loss pulls the embeddings of points dominated by the same source together, and k-means on the
+ * embeddings gives the masks.  No counterpart in the reference; sepkern/dpcl.py states the definition and restates the
+ * arithmetic below in numpy fp64.
+ * All three entry points work on PACKED rows ("packed rows" above: row of (t, j) = offs[t] + j, lens sorted descending, lens[0]
+ * = T).  z (R, ld >= F*D) float32: dimension d of bin f in column d*F + f (D planes of F columns); mix and the S sources
+ * src_host[s] (a host array of device pointers) are (R, F) contiguous.  A point i = (row, bin); utterance j has lens[j] * F
+ * points, numbered t*F + f.  v_i = (z[row][d*F + f])_d, u_i = v_i / |v_i| (0 for a zero vector; fp32, d ascending).
+ *
+ * sk_dpcl_fwd:  y_i = the first maximum of src_s[row][f] over s;  weights before normalisation w'_i = mix_i (weight =
+ *   SK_DPCL_MR) or [mix_i > thr_j] (SK_DPCL_VAD), thr_j = vad_ratio * max_{i in j} mix_i, ONE fp32 product;  w_i = w'_i / sum_j w'
+ *   (0 for an utterance whose weights are all zero).  With the rows sqrt(w'_i) [u_i | onehot(y_i)] the Gram matrix holds
+ *     A = U^T W U (D x D),  Bm = U^T W Y (D x S),  C = Y^T W Y (diagonal),   L_j = |A|_F^2 - 2 |Bm|_F^2 + |C|_F^2
+ *   Launch (1) (SK_DPCL_VAD: two launches before it form thr): (utterance, chunk of 8 of ITS frames), tiles of 64 points; the
+ *   exact-fp32 MFMA sums four points per instruction (fp32 products, an fp32 chain of four), every such sum is added in fp64;
+ *   one fp64 partial per chunk in a fixed slot of ws; (2) per utterance the chunks added in ascending order in fp64, the
+ *   normaliser 1 / tr C applied, L_j;  (3) the batch output.
+ *     lj (B) fp64 = L_j;  out[0] = loss = (1/count) sum_j L_j, out[1] = count, out[2] = sum_j L_j (j ascending, fp64);  count = B, or
+ *     count_dev[0] (device scalar, may be NULL: the GLOBAL utterance count of a data-parallel step)
+ *     ab (B, 40*40 + 40*4) float32 = A (pitch 40) and Bm (pitch 4) of every utterance, zero-padded;  stats (B, 2) = 1 / sum w', thr
+ * sk_dpcl_bwd:  dz = gscale[0] / out[1] * dL_j/dz on the rows and columns of the batch -- one point per lane,
+ *     g_i = 4 w_i (A u_i - Bm[:, y_i]),   dL/dv_i = (g_i - u_i (u_i . g_i)) / |v_i|   (0 for a zero vector or a zero weight)
+ *   from ab, stats and out as sk_dpcl_fwd left them; w_i and y_i are recomputed.  Only rows offs[t] + j, t < lens[j], columns
+ *   < F*D of dz (>= R, ld) are written, each exactly once.
+ * sk_dpcl_kmeans:  per utterance, S clusters on u_i.  A point is ACTIVE when mix_i > thr_j (above) and then weighs mix_i.
+ *   Initialisation (skipped with centroids_in (B, S, D) float32): centroid 0 = the active point of largest mix; centroid k = the
+ *   active point whose least squared distance to the centroids before k is largest; ties to the lowest point index; with at
+ *   most k active points centroid k copies centroid 0 (zeros without any active point).  `iterations` >= 0 Lloyd steps: every
+ *   point to the centroid of least squared distance (fp32, d ascending; ties to the lowest k), every centroid to the weighted
+ *   mean of its active members (the loss's sums: four points per MFMA in fp32, added in fp64; a cluster without active member
+ *   keeps its centroid).  Then one final assignment:  labels (R, F) int32;  mask (R, ld_mask >= S*F): mask[row][k*F + f] = 1.0 where the
+ *   label is k, else 0.0 -- the layout of the uPIT masks;  centroids (B, S, D) float32.  Two launches for thr, two per centroid,
+ *   two per iteration, one for the assignment; no host synchronisation, no hand-off between workgroups.
+ * No atomics, every sum in one fixed order, chunk boundaries a function of the utterance's own length: bitwise reproducible,
+ * the bits do not depend on ld, and an utterance's numbers do not depend on the batch around it.  Nothing outside the rows
+ * and columns named above is read or written.  SK_EINVAL before anything is launched: D outside 1..40, S outside 1..4 (2..4 for
+ * k-means), F, T or B < 1, B > 65535, ld < F*D, ld_mask < S*F, iterations < 0, vad_ratio outside [0, 1], a weight other than
+ * the two, a NULL pointer.  ws >= sk_dpcl_workspace_bytes / sk_dpcl_kmeans_workspace_bytes (0 for arguments out of range). */
+#define SK_DPCL_MR 0
+#define SK_DPCL_VAD 1
+size_t sk_dpcl_workspace_bytes(int T, int B, int F, int D, int S);
+int sk_dpcl_fwd(const float* z, int ld, const float* mix, const float* const* src_host, const int32_t* lens,
+                const int32_t* offs, int T, int B, int F, int D, int S, int weight, float vad_ratio, const float* count_dev,
+                double* lj, float* ab, float* stats, float* out, void* ws, sk_stream_t stream);
+int sk_dpcl_bwd(const float* z, int ld, const float* mix, const float* const* src_host, const int32_t* lens,
+                const int32_t* offs, int T, int B, int F, int D, int S, int weight, const float* ab, const float* stats,
+                const float* out, const float* gscale, float* dz, sk_stream_t stream);
+size_t sk_dpcl_kmeans_workspace_bytes(int T, int B, int F, int D, int S);
+int sk_dpcl_kmeans(const float* z, int ld, const float* mix, const int32_t* lens, const int32_t* offs, int T, int B, int F, int D,
+                   int S, int iterations, float vad_ratio, const float* centroids_in, float* mask, int ld_mask, int32_t* labels,
+                   float* centroids, void* ws, sk_stream_t stream);
 
 /* ---------------------------------------------------------------- phase-sensitive uPIT targets (loss=psa / tpsa)
  * The targets of the phase-sensitive approximation loss (sepkern/psa.py states the definition and restates it in numpy fp64),

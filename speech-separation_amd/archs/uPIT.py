@@ -34,6 +34,14 @@ Beyond the reference (all optional, defaults reproduce it):
     the best of the 2^M assignments of the M time-domain estimates to the two recordings is scored (SNR with the soft
     threshold of conf key mixit_snr_max, default 30 dB).  No isolated sources are needed.  It needs waveforms;
     compute_loss returns (mean negative score per utterance in dB, number of utterances).
+    'dpcl': deep clustering (Hershey et al. 2016; sepkern/dpcl.py, include/sepkern.h "deep clustering"): the same network
+    with out_dim = feat_dim * embed_dim (conf key embed_dim, default 20, at most 40) emits an embedding per time-frequency
+    point, the loss (sk_dpcl_fwd / sk_dpcl_bwd) pulls the embeddings of points dominated by the same source together -- weights
+    dpcl_weight = mr (magnitude ratio, default) or vad (points above -dpcl_vad_db dB, default 40) -- and at inference k-means
+    (sk_dpcl_kmeans, dpcl_kmeans_iters Lloyd steps, default 20) turns the embeddings into num_spk binary masks in the uPIT
+    mask layout: compute_masks, steps/reconstruct_sources.py and sepkern.separate run unchanged.  It trains on whatever
+    loss=mse trains on (magnitudes of the mixture and the sources).  compute_loss returns (mean loss per utterance, number
+    of utterances).
   * DynMixTrainSet / DynMixCollator (steps/train_qsub.py --dynamic-mix): training mixtures drawn afresh every epoch from
     single-speaker utterances and mixed on the GPU (sk_dynamic_mix); every loss above trains on them.  With rir_scp / rir_synth
     (--mix-rir-scp / --mix-rir-synth) every source is first convolved with a room impulse response, also on the GPU
@@ -60,6 +68,7 @@ except ImportError:  # the frozen copy exp/<...>/arch.py is imported from anothe
             break
     import sepkern  # noqa: F401
 from sepkern import dist as skdist
+from sepkern import dpcl as _dpcl
 from sepkern import ops
 from sepkern.data import features_from_pcm as _features_from_pcm, wave_features_from_pcm as _wave_features_from_pcm
 from sepkern.data import psa_features_from_pcm as _psa_features_from_pcm
@@ -420,6 +429,25 @@ class DynMixCollator():
     return {'pcm': pcm}
 
 
+class _DpclFn(torch.autograd.Function):
+  """out = [mean_j L_j, count, sum_j L_j] of the deep-clustering loss (sepkern/dpcl.py) from the packed embedding rows."""
+
+  @staticmethod
+  def forward(ctx, z, mix, pk, count_dev, embed_dim, weight, vad_db, *srcs):
+    res = ops.dpcl_fwd(z, mix, list(srcs), pk, embed_dim, weight, vad_db, count_dev)
+    ctx.save_for_backward(z, mix, res["ab"], res["stats"], res["out"], *srcs)
+    ctx.pk, ctx.conf = pk, (embed_dim, weight)
+    return res["out"]
+
+  @staticmethod
+  def backward(ctx, gout):
+    z, mix, ab, stats, out = ctx.saved_tensors[:5]
+    srcs = list(ctx.saved_tensors[5:])
+    # (columns >= F*D and rows >= R of a padded buffer: zero, as _WaveLossFn leaves dmask)
+    dz = ops.dpcl_bwd(z, mix, srcs, ctx.pk, ctx.conf[0], dict(ab=ab, stats=stats, out=out), gout[0:1].contiguous(), ctx.conf[1])
+    return (dz, None, None, None, None, None, None) + (None,) * len(srcs)
+
+
 class _PitFn(torch.autograd.Function):
   """out = [loss/norm, norm, sum_b min_p L/S] (reference archs/uPIT.py:181-197,206)."""
 
@@ -444,13 +472,15 @@ LOSSES = ('mse', 'sisdr', 'psa', 'tpsa')
 PSA_LOSSES = ('psa', 'tpsa')       # PIT-MSE on phase-sensitive targets (sepkern/psa.py); 'tpsa' holds them to [0, |mix|]
 MIXIT_LOSSES = ('mixit',)          # mixture-invariant training (sepkern/mixit.py): num_spk masks against the TWO mixed recordings
 WAVE_LOSSES = ('sisdr',) + MIXIT_LOSSES      # computed from the batch's waveforms (the driver keeps them with the staged batch)
+DPCL_LOSSES = ('dpcl',)            # deep clustering (sepkern/dpcl.py): embeddings instead of masks, on loss=mse's inputs
 
 
 def parse_loss(value):
-  """The conf key `loss`: 'mse' (default), 'sisdr', 'psa', 'tpsa' or 'mixit'."""
+  """The conf key `loss`: 'mse' (default), 'sisdr', 'psa', 'tpsa', 'mixit' or 'dpcl'."""
   value = str(value).strip().lower()
-  if value not in LOSSES + MIXIT_LOSSES:
-    raise ValueError("conf key loss: %r is not one of %s" % (value, " / ".join(repr(v) for v in LOSSES + MIXIT_LOSSES)))
+  known = LOSSES + MIXIT_LOSSES + DPCL_LOSSES
+  if value not in known:
+    raise ValueError("conf key loss: %r is not one of %s" % (value, " / ".join(repr(v) for v in known)))
   return value
 
 
@@ -504,10 +534,23 @@ class SepDNN(SepDNNBase):
     self.mixit_snr_max = float(kwargs.get('mixit_snr_max', 30.0))     # dB, read by loss=mixit only (sepkern/mixit.py: tau)
     if self.loss_kind in MIXIT_LOSSES and not 2 <= self.num_spk <= 4:
       raise ValueError("loss=mixit: num_spk = %d estimates per mixture is outside 2..4" % self.num_spk)
+    # loss=dpcl (sepkern/dpcl.py): the head emits embed_dim planes of feat_dim columns; num_spk counts the label columns in
+    # training and the clusters at inference
+    self.embed_dim = _dpcl.parse_embed_dim(kwargs.get('embed_dim', 20))
+    self.dpcl_weight = _dpcl.parse_weight(kwargs.get('dpcl_weight', 'mr'))
+    self.dpcl_vad_db = float(kwargs.get('dpcl_vad_db', _dpcl.DEFAULT_VAD_DB))
+    self.dpcl_kmeans_iters = int(kwargs.get('dpcl_kmeans_iters', _dpcl.DEFAULT_ITERATIONS))
+    if self.loss_kind in DPCL_LOSSES:
+      _dpcl.vad_ratio(self.dpcl_vad_db)
+      if not 1 <= self.num_spk <= _dpcl.MAX_S:
+        raise ValueError("loss=dpcl: num_spk = %d is outside 1..%d" % (self.num_spk, _dpcl.MAX_S))
+      if self.dpcl_kmeans_iters < 0:
+        raise ValueError("loss=dpcl: dpcl_kmeans_iters = %d is negative" % self.dpcl_kmeans_iters)
+    out_dim = self.feat_dim * (self.embed_dim if self.loss_kind in DPCL_LOSSES else self.num_spk)
     for key in kwargs.keys():
       print('modelparam:', key, kwargs[key])
     # the reference hard-codes 2 x 600 (archs/uPIT.py:115-119); hidden_dim / num_layers widen it
-    self._build(gpuid, self.feat_dim, self.feat_dim * self.num_spk, int(kwargs.get('hidden_dim', 600)),
+    self._build(gpuid, self.feat_dim, out_dim, int(kwargs.get('hidden_dim', 600)),
                 int(kwargs.get('num_layers', 2)), str(kwargs.get('dtype', 'fp32')), kwargs.get('sync_bn', '0'))
 
   def forward_packed(self, x2d, pk):
@@ -516,6 +559,17 @@ class SepDNN(SepDNNBase):
       self.hidden = self.init_hidden(pk.B)
     h0, c0 = self.hidden
     return self.run_net_packed(x2d, pk, h0, c0)
+
+  def masks_packed(self, x2d, pk):
+    """x2d (R,F) packed rows -> the (rows, F*S) masks of the batch: the network's own output for a uPIT model (forward_packed's
+    tensor itself); for a loss=dpcl model the k-means masks of its embeddings (sk_dpcl_kmeans: a fresh contiguous tensor of
+    0.0 / 1.0 in the same layout, num_spk clusters)."""
+    out = self.forward_packed(x2d, pk)
+    if getattr(self, 'loss_kind', 'mse') not in DPCL_LOSSES:
+      return out
+    if not 2 <= self.num_spk <= _dpcl.MAX_S:
+      raise ValueError("loss=dpcl: k-means masks need num_spk in 2..%d clusters (got %d)" % (_dpcl.MAX_S, self.num_spk))
+    return ops.dpcl_kmeans(out.detach(), x2d, pk, self.num_spk, self.dpcl_kmeans_iters, self.dpcl_vad_db, D=self.embed_dim)[0]
 
   def forward_padded(self, x, lens):
     """x (T,B,F) time-major zero-padded CUDA tensor, lens int32 CUDA (B) -> mask (T,B,F*S)."""
@@ -585,6 +639,23 @@ def compute_loss_packed(model, mix, sources, pk, plotdir=""):
                    plotdir + '/Chosen_Permutation.png')
 
   return loss, norm
+
+
+def compute_loss_dpcl(model, mix, sources, pk):
+  """The loss=dpcl route on loss=mse's inputs: mix (R,F) and sources [(R,F)]*S packed magnitude rows and their Packing.
+  Returns (mean deep-clustering loss per utterance, number of utterances)."""
+  if len(sources) < model.num_spk:
+    raise ValueError("loss=dpcl: the batch holds %d sources (num_spk = %d)" % (len(sources), model.num_spk))
+  model.zero_grad()
+  model.hidden = model.init_hidden(pk.B)
+  # data-parallel: divide by the GLOBAL utterance count (None = single process: the kernel uses B), while training only
+  training_step = model.training and torch.is_grad_enabled()
+  count = skdist.global_norm(pk.lens.new_full((1,), pk.B), 1) if training_step else None
+  z = model.forward_packed(mix, pk)                     # (rows, feat_dim * embed_dim): plane d of a row = dimension d of its bins
+  srcs = [s.contiguous() for s in sources[:model.num_spk]]
+  out = _DpclFn.apply(z, mix.contiguous(), pk, count, model.embed_dim, model.dpcl_weight, model.dpcl_vad_db, *srcs)
+  model.step_frames = pk.R                  # (the norm counts utterances: the driver's frames/s line reads this)
+  return out[0], out[1].detach()
 
 
 def _wave_loss(model, mix, pk, wave, loss, descriptors, extra=()):
@@ -677,13 +748,14 @@ def compute_loss(model, epoch, batch_sample, plotdir=""):
     return compute_loss_mixit(model, mix, pk, wave) if kind in MIXIT_LOSSES else compute_loss_wave(model, mix, pk, wave)
   if 'pcm' in batch_sample:        # WavTrainSet batches: features are computed on the GPU
     mix, sources, pk = _features_from_pcm(batch_sample['pcm'], dev)
-    return compute_loss_packed(model, mix, sources[:model.num_spk], pk, plotdir)
-  if 'packed' in batch_sample:     # batches staged on the GPU ahead of the step (sepkern.data.Prefetcher)
+  elif 'packed' in batch_sample:   # batches staged on the GPU ahead of the step (sepkern.data.Prefetcher)
     mix, sources, pk = batch_sample['packed']
-    return compute_loss_packed(model, mix, sources[:model.num_spk], pk, plotdir)
-  mix, pk = _to_packed(batch_sample['mix'], dev)
-  sources = [_to_packed(batch_sample['source' + str(i + 1)], dev)[0] for i in range(model.num_spk)]
-  return compute_loss_packed(model, mix, sources, pk, plotdir)
+  else:
+    mix, pk = _to_packed(batch_sample['mix'], dev)
+    sources = [_to_packed(batch_sample['source' + str(i + 1)], dev)[0] for i in range(model.num_spk)]
+  if kind in DPCL_LOSSES:          # the same front ends: magnitudes of the mixture and the sources
+    return compute_loss_dpcl(model, mix, sources, pk)
+  return compute_loss_packed(model, mix, sources[:model.num_spk], pk, plotdir)
 
 
 def estimate_masks(model, batch_sample):
@@ -698,7 +770,7 @@ def estimate_masks(model, batch_sample):
   model.hidden = model.init_hidden(batch)
 
   with torch.no_grad():
-    mask_np = model.forward_packed(mix, pk).cpu().numpy()            # (sum of lengths, feat_dim*num_spk)
+    mask_np = model.masks_packed(mix, pk).cpu().numpy()              # (sum of lengths, feat_dim*num_spk)
   lens, offs = pk.lens_host, pk.offs_host
   out = []
   for i in range(len(name)):

@@ -21,7 +21,7 @@ BUILD_FLAG_NAMES = {0x1: "TIMING_ONLY (wrong results by construction)", 0x2: "AR
 def build_flag_names(mask):
     return [n for b, n in sorted(BUILD_FLAG_NAMES.items()) if mask & b] + (["unknown 0x%x" % (mask & ~0xf)] if mask & ~0xf else [])
 
-SK_VERSION = 144
+SK_VERSION = 145
 
 _p, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 
@@ -88,6 +88,11 @@ PROTOTYPES = {
     "sk_mixit_workspace_bytes": (_sz, [_i, _i, _i]),
     "sk_mixit_fwd": (_i, [_p, _p, _p, _i, _p, _p, _i, _i, _i, _p, C.c_double, _p, _p, _p, _p, _p, _p]),
     "sk_mixit_mask_grad": (_i, [_p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _p]),
+    "sk_dpcl_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "sk_dpcl_fwd": (_i, [_p, _i, _p, C.POINTER(_p), _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _p]),
+    "sk_dpcl_bwd": (_i, [_p, _i, _p, C.POINTER(_p), _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "sk_dpcl_kmeans_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "sk_dpcl_kmeans": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _i, _p, _p, _p, _p]),
     "sk_stft_psa": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _i64, _p, _i, _i, _p]),
     "sk_rsh_workspace_bytes": (_sz, [_i, _i, _i]),
     "sk_rsh_loss_fwd": (_i, [_p, _p, _i, C.POINTER(_p), _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),

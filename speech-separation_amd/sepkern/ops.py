@@ -9,6 +9,7 @@ import torch
 
 from . import _lib
 from . import cacgmm as _cacgmm
+from . import dpcl as _dpcl
 
 _WS = {}
 
@@ -824,6 +825,137 @@ def cacgmm(Y, prior, S, iterations, block_frames, context_frames, loading, B_in=
             _lib.call("sk_cacgmm", _ptr(Y), int(Y.stride(0)), int(Y.stride(1)), _ptr(prior), int(prior.stride(0)), T, C, S, I, Lb, Lc,
                       float(loading), _ptr(B_in), _ptr(out), int(out.stride(0)), _ptr(B), None, _stream())
     return out[:T, :S * 257], B
+
+
+# ----------------------------------------------------------------------------- deep clustering: loss and k-means masks
+DPCL_AB = 40 * 40 + 40 * 4          # floats of [A | Bm] per utterance (include/sepkern.h)
+
+
+def _dpcl_args(who, z, mix, pk, D, S, smin):
+    """The checks the three deep-clustering wrappers share -> (F, D, S, ld)."""
+    _chk(z)
+    _chk(mix)
+    D, S = int(D), int(S)
+    if pk.perm is not None:
+        raise _lib.SepkernError("%s needs a length-sorted batch (Packing without perm)" % who)
+    if not 1 <= D <= _dpcl.MAX_D or not smin <= S <= _dpcl.MAX_S:
+        raise _lib.SepkernError("%s: D = %d outside 1..%d or S = %d outside %d..%d" % (who, D, _dpcl.MAX_D, S, smin, _dpcl.MAX_S))
+    if mix.dim() != 2 or not mix.is_contiguous() or mix.shape[0] < pk.R or mix.shape[1] < 1:
+        raise _lib.SepkernError("%s: mix must be (>= R, F) contiguous float32 rows of the batch" % who)
+    F = int(mix.shape[1])
+    if z.dim() != 2 or z.stride(1) != 1 or z.shape[0] < pk.R or z.shape[1] < F * D:
+        raise _lib.SepkernError("%s: z must be (>= R, >= F*D = %d) float32 with unit column stride (got %s)" % (who, F * D, tuple(z.shape)))
+    return F, D, S, int(z.stride(0))
+
+
+def _dpcl_srcs(who, srcs, mix):
+    for s in srcs:
+        _chk(s)
+        if s.dim() != 2 or not s.is_contiguous() or s.shape[0] < mix.shape[0] or s.shape[1] != mix.shape[1]:
+            raise _lib.SepkernError("%s: every source must be (>= R, F) contiguous float32 rows like mix" % who)
+    return (C.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs])
+
+
+def _dpcl_weight(who, weight):
+    try:
+        return _dpcl.WEIGHTS.index(weight)
+    except ValueError:
+        raise _lib.SepkernError("%s: weight %r is neither 'mr' nor 'vad'" % (who, weight))
+
+
+def dpcl_fwd(z, mix, srcs, pk, D, weight="mr", vad_db=40.0, count_dev=None, repeat=1):
+    """The deep-clustering loss of a packed batch (sk_dpcl_fwd; sepkern/dpcl.py defines it).  z: (>= R, ld >= F*D) float32
+    embedding rows with unit column stride, dimension d of bin f in column d*F + f; mix and the S = len(srcs) sources: (>= R, F)
+    contiguous float32 magnitude rows of the batch pk; weight 'mr' or 'vad' (active above -vad_db dB of the utterance's maximum);
+    count_dev: optional device scalar replacing B (the global utterance count under data parallelism).
+    -> dict(out (3,) = [loss, count, sum_j L_j], lj (B,) float64, ab (B, 1760) = A and Bm per utterance, stats (B, 2)): what
+    dpcl_bwd takes; nothing synchronises with the host."""
+    lib = _lib.load()
+    F, D, S, ld = _dpcl_args("dpcl_fwd", z, mix, pk, D, len(srcs), 1)
+    sp = _dpcl_srcs("dpcl_fwd", srcs, mix)
+    wk = _dpcl_weight("dpcl_fwd", weight)
+    ratio = float(_dpcl.vad_ratio(vad_db))
+    _chk(count_dev)
+    dev = z.device
+    lj = torch.empty(pk.B, dtype=torch.float64, device=dev)
+    ab = torch.empty(pk.B, DPCL_AB, dtype=torch.float32, device=dev)
+    stats = torch.empty(pk.B, 2, dtype=torch.float32, device=dev)
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    ws = workspace(lib.sk_dpcl_workspace_bytes(pk.T, pk.B, F, D, S), "dpcl")
+    # algorithmic bytes: the embeddings, the mixture (twice with 'vad': the threshold pass) and the S sources, read once
+    with _timed("dpcl_fwd", repeat * float(pk.R) * F * 4 * (D + 1 + wk + S)):
+        for _ in range(repeat):
+            _lib.call("sk_dpcl_fwd", _ptr(z), ld, _ptr(mix), sp, _ptr(pk.lens), _ptr(pk.offs), pk.T, pk.B, F, D, S, wk, ratio,
+                      _ptr(count_dev), _ptr(lj), _ptr(ab), _ptr(stats), _ptr(out), _ptr(ws), _stream())
+    return dict(out=out, lj=lj, ab=ab, stats=stats)
+
+
+def dpcl_bwd(z, mix, srcs, pk, D, res, gscale, weight="mr", out=None, repeat=1):
+    """dz = gscale[0] / count * d(sum_j L_j) / dz (sk_dpcl_bwd) from dpcl_fwd's result `res` on the same operands.  out: a float32
+    buffer of z's shape and strides to write into; only the batch's rows and the columns < F*D are written -- a fresh buffer is
+    allocated with everything else zero.  -> dz."""
+    _lib.load()
+    F, D, S, ld = _dpcl_args("dpcl_bwd", z, mix, pk, D, len(srcs), 1)
+    sp = _dpcl_srcs("dpcl_bwd", srcs, mix)
+    wk = _dpcl_weight("dpcl_bwd", weight)
+    _chk(gscale)
+    for t in (res["ab"], res["stats"], res["out"]):
+        _chk(t)
+    if out is None:
+        out = torch.empty_like(z)
+        if out.shape[0] > pk.R:
+            out[pk.R:].zero_()
+        if out.shape[1] > F * D:
+            out[:, F * D:].zero_()
+    _chk(out)
+    if out.shape != z.shape or out.stride() != z.stride():
+        raise _lib.SepkernError("dpcl_bwd: out must have z's shape and strides")
+    # algorithmic bytes: the forward's operands read once, dz written once
+    with _timed("dpcl_bwd", repeat * float(pk.R) * F * 4 * (2 * D + 1 + S)):
+        for _ in range(repeat):
+            _lib.call("sk_dpcl_bwd", _ptr(z), ld, _ptr(mix), sp, _ptr(pk.lens), _ptr(pk.offs), pk.T, pk.B, F, D, S, wk, _ptr(res["ab"]),
+                      _ptr(res["stats"]), _ptr(res["out"]), _ptr(gscale), _ptr(out), _stream())
+    return out
+
+
+def dpcl_kmeans(z, mix, pk, S, iterations=20, vad_db=40.0, centroids_in=None, out=None, D=None, repeat=1):
+    """k-means masks from the embeddings of a packed batch (sk_dpcl_kmeans; sepkern/dpcl.py defines the result).  z: (>= R, ld >=
+    F*D) float32 embedding rows with unit column stride; mix: (>= R, F) contiguous float32 magnitude rows; D: the embedding
+    dimension, default z.shape[1] // F (to be given when z carries padding columns); 2 <= S <= 4 clusters; iterations >= 0 Lloyd steps; points above -vad_db dB of their
+    utterance's maximum are active; centroids_in: None (farthest-first initialisation) or (B, S, D) contiguous float32;
+    out: a float32 (>= R, >= S*F) buffer with unit column stride to write the masks into (rows of the batch, columns < S*F only).
+    -> (mask (rows of out, S*F) of 0.0 / 1.0 in the uPIT mask layout, labels (R, F) int32, centroids (B, S, D) float32); nothing
+    synchronises with the host."""
+    lib = _lib.load()
+    F = int(mix.shape[1]) if mix.dim() == 2 and mix.shape[1] > 0 else 1
+    F, D, S, ld = _dpcl_args("dpcl_kmeans", z, mix, pk, int(z.shape[1]) // F if D is None and z.dim() == 2 else D, S, 2)
+    iterations = int(iterations)
+    if iterations < 0:
+        raise _lib.SepkernError("dpcl_kmeans: iterations = %d is negative" % iterations)
+    ratio = float(_dpcl.vad_ratio(vad_db))
+    dev = z.device
+    if centroids_in is not None:
+        _chk(centroids_in)
+        if tuple(centroids_in.shape) != (pk.B, S, D) or not centroids_in.is_contiguous():
+            raise _lib.SepkernError("dpcl_kmeans: centroids_in must be (B, S, D) contiguous float32")
+    if out is None:
+        out = torch.empty(z.shape[0], S * F, dtype=torch.float32, device=dev)
+        if out.shape[0] > pk.R:
+            out[pk.R:].zero_()
+    _chk(out)
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < pk.R or out.shape[1] < S * F:
+        raise _lib.SepkernError("dpcl_kmeans: out must be (>= R, >= S*F) float32 with unit column stride")
+    labels = torch.empty(pk.R, F, dtype=torch.int32, device=dev)
+    cent = torch.empty(pk.B, S, D, dtype=torch.float32, device=dev)
+    ws = workspace(lib.sk_dpcl_kmeans_workspace_bytes(pk.T, pk.B, F, D, S), "dpcl")
+    # algorithmic bytes: the embeddings once per initial centroid after the first, per iteration and for the assignment; the
+    # mixture beside each pass and for the threshold; the masks and labels written
+    passes = (0 if centroids_in is not None else S - 1) + iterations + 1
+    with _timed("dpcl_kmeans", repeat * float(pk.R) * F * 4 * (passes * D + passes + 2 + S + 1)):
+        for _ in range(repeat):
+            _lib.call("sk_dpcl_kmeans", _ptr(z), ld, _ptr(mix), _ptr(pk.lens), _ptr(pk.offs), pk.T, pk.B, F, D, S, iterations, ratio,
+                      _ptr(centroids_in), _ptr(out), int(out.stride(0)), _ptr(labels), _ptr(cent), _ptr(ws), _stream())
+    return out[:, :S * F], labels, cent
 
 
 # ----------------------------------------------------------------------------- PIT-MSE

@@ -41,7 +41,9 @@ def window_masks(model, mag, window_frames, hop_frames, batch_windows):
         x = pk.rows(mag.shape[1])
         torch.index_select(mag, 0, idx, out=x[:pk.R])
         model.hidden = model.init_hidden(B)
-        mask = model.forward_packed(x, pk)
+        # (masks_packed: the network's own tensor for a uPIT model; the k-means masks of a deep-clustering model's embeddings,
+        # a fresh contiguous tensor -- its stride makes the descriptors either way)
+        mask = model.masks_packed(x, pk)
         ld = int(mask.stride(0))
         for j, k in enumerate(ks):
             windows[k] = (mask, j * ld, B * ld)
