@@ -111,6 +111,45 @@ def test_parity_with_the_host_function_at_512_taps():
         np.testing.assert_allclose(np.stack(fixed[u][:3]), np.stack(want[:3]), atol=GATE_DB, rtol=0)
 
 
+@pytest.mark.parametrize("S,taps,lens", [(1, 5, [40, 300]), (2, 17, [300, 1000]), (3, 37, [1000, 2048]), (4, 21, [700, 701]),
+                                         (2, 100, [900]), (1, 37, [30])])
+def test_parity_at_orders_whose_last_panel_is_part_gram_part_identity(S, taps, lens):
+    """bss_chol_kernel factors matrices padded with an identity to multiples of 16: S x taps = 5 -> 16, 34 -> 48, 111 -> 112,
+    84 -> 96, 200 -> 208, 37 -> 48 here, and one source's 17 -> 32, 37 -> 48, 21 -> 32, 100 -> 112; n = 30 < taps = 37.
+    Conditions on the inputs, asserted on the host result: more samples than unknowns (n + taps - 1 > S taps; with fewer the
+    projection is exact and SAR is rounding noise, about 290 dB -- S = 4, taps = 37, n = 30 does that) and every SAR below
+    60 dB.  (1, 37, [30]) has 66 samples for 37 unknowns: a margin of two between them, which every other case has, it cannot."""
+    order, one = S * taps, taps
+    assert order % 16 != 0
+    print("S = %d, taps = %d: orders %d -> %d and %d -> %d" % (S, taps, order, -(-order // 16) * 16, one, -(-one // 16) * 16))
+    rng = np.random.default_rng(100 * S + taps)
+    refs = [rng.standard_normal((S, n)) for n in lens]
+    ests = [_estimates(r, rng) for r in refs]
+    want = [bsseval.bss_eval_sources(r, e, taps=taps) for r, e in zip(refs, ests)]
+    for n, w in zip(lens, want):
+        assert n + taps - 1 > S * taps and np.all(w[2] < 60.0), (n, w[2])
+    got = bss_eval_sources_batch(refs, ests, taps=taps)
+    assert got.fallback == []
+    worst = 0.0
+    for u in range(len(lens)):
+        assert got[u][3].tolist() == want[u][3].tolist(), u
+        for m in range(3):
+            g, w = got[u][m], want[u][m]
+            assert g.shape == w.shape == (S,)
+            fin = np.isfinite(w)                                 # S = 1: no interference, SIR is +inf on both sides
+            assert np.array_equal(g[~fin], w[~fin]) and fin.all() == (S > 1 or m != 1) and np.isfinite(g[fin]).all(), (u, m, g, w)
+            if fin.any():
+                worst = max(worst, float(np.max(np.abs(g[fin] - w[fin]))))
+    print("S = %d, taps = %d, lengths %s: max |GPU - host| over SDR/SIR/SAR %.3g dB (gate %.3g)" % (S, taps, lens, worst, GATE_DB))
+    assert worst < GATE_DB
+    # a short and a long utterance in one batch: each has the bits it has alone
+    for u in range(len(lens)):
+        solo = bss_eval_sources_batch(refs[u:u + 1], ests[u:u + 1], taps=taps)
+        assert solo.fallback == []
+        for m in range(4):
+            assert np.array_equal(solo[0][m], got[u][m]), (u, m)
+
+
 def _dense_projection(refs, e, taps):
     n = refs.shape[1]
     cols = []

@@ -20,7 +20,8 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.join(PKG, "archs"))
 STEPS = os.path.join(PKG, "steps")
-PAIRS = [(16000, 8000), (48000, 8000), (44100, 8000), (11025, 8000), (8000, 16000)]
+PAIRS = [(16000, 8000), (48000, 8000), (44100, 8000), (11025, 8000), (8000, 16000),
+         (8000, 10000), (16000, 10000)]      # the ratios scoring uses (stoi_gpu._at_10k): L / M = 5 / 4 and 5 / 8, both on the 1024 tile
 # Ratios steep enough to leave the 1024-output tile, or to fill its LDS (dynamic LDS per workgroup, limit 61 440 B):
 #   96000 -> 8000   L = 1,  M = 12,  1537 taps: tile 1024 with 61 408 B (samples + the tap row)
 #   44100 -> 2000   L = 20, M = 441, 2823 taps: tile 512 with 56 368 B, taps from global memory
