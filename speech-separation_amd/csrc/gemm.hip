@@ -6,7 +6,7 @@
 // Two families of kernels, both fp32 products with fp32 accumulation (results match an fp32 reference to
 // rounding-order differences only):
 //   * fp32 MFMA (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain): gemm_f32_kernel (register-staged, any
-//     alignment), _dma / _dma256 / _streamk (LDS-DMA staging);
+//     alignment), _dma<128 | 256> / _streamk (LDS-DMA staging);
 //   * SPLIT products on the bf16 matrix pipe (r05, the default wherever operands are aligned): both operands cut exactly into
 //     three bf16 pieces, six exact piece products per element pair -- gemm_f32_kernel_split3, gemm_f32_kernel_planes;
 //     the bf16 pipe is 16x the fp32 one, so six products still leave 2.7x its rate.
@@ -211,6 +211,64 @@ __device__ __forceinline__ void finish_splitk(const GemmArgs& g, int z, int row0
     }
 }
 
+// The tile order of every product kernel: position v of nt in the launch order (blockIdx.x of gridDim.x for a tile grid,
+// a stream-K kernel's own count) -> origin (m0, n0) of its TILE_M x TILE_N output tile.
+// XCD-aware: blocks b and b+8 share an XCD (and its L2), so each XCD gets a contiguous run of the tile list (n
+// fastest): neighbours in a run share their A panel, runs share B.  Within a run, groups of GROUP tile rows are walked
+// column by column: the ~128 tiles an XCD has in flight then cover about GROUP x 16 tiles and share 8 A panels and 16 B
+// panels in its 4 MB L2, instead of 2-3 A panels and every B panel of the matrix.  GROUP = GROUP_M for 128-row tiles (and
+// the bf2 kernels), GROUP_M / 2 for the fp32 kernels' 256-row tiles: the same 1024 rows per group.
+template <int TILE_M, int TILE_N, int GROUP>
+__device__ __forceinline__ void tile_origin(int v, int nt, int tilesN, int& m0, int& n0) {
+  const int q = nt >> 3, rem = nt & 7, x = v & 7, j = v >> 3;
+  const int tile = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + j;
+  const int tilesM = nt / tilesN, per = GROUP * tilesN;
+  const int grp = tile / per, rem2 = tile - grp * per, first = grp * GROUP;
+  const int gsz = min(GROUP, tilesM - first);
+  m0 = (first + rem2 % gsz) * TILE_M;
+  n0 = (rem2 / gsz) * TILE_N;
+}
+
+// What block (z = batch entry, ks = K slice) of a tile-grid launch works on (Args: GemmArgs or bf2::Args): its operands,
+// its K range [kbeg, kend) (kchunk is a multiple of the kernel's K step) and where its tile goes -- a split-K slice
+// (partial) writes its slab, dense with row stride N and without the bias, which the reduction adds once.
+template <class Args>
+struct Slice {
+  decltype(Args::A) A, B;
+  float* C;
+  const float* bias;
+  int ldc, kbeg, kend;
+  bool partial;
+  __device__ __forceinline__ Slice(const Args& g, int z, int ks) {
+    A = g.A + z * g.sA;
+    B = g.B + z * g.sB;
+    partial = g.splitk > 1;
+    C = partial ? g.slabs + ((int64_t)z * g.splitk + ks) * g.M * g.N : g.C + z * g.sC;
+    ldc = partial ? g.N : g.ldc;
+    bias = (g.bias && !partial) ? g.bias + z * g.sbias : nullptr;
+    kbeg = ks * g.kchunk;
+    kend = min(g.K, kbeg + g.kchunk);
+  }
+};
+
+// The last act of a block of the 128 x 128-per-four-waves kernels: the wave's 64 x 64 sub-tile at (row0, col0) to C or to
+// the slice's slab, then the in-kernel reduction of the slabs where the launcher set it up.
+__device__ __forceinline__ void finish_tile(const GemmArgs& g, const f32x16 (&acc)[2][2], const Slice<GemmArgs>& sl, int z, int row0,
+                                            int col0, int tid) {
+  store_tile(g, acc, sl.C, sl.ldc, sl.bias, sl.partial, row0, col0, tid & 63);
+  if (sl.partial && g.counters) finish_splitk(g, z, row0, col0, tid);
+}
+
+template <int TM, int TN>
+__device__ __forceinline__ void clear_acc(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
 // VEC == false: the variant for operands with unaligned rows (both operands then use dword loads).
 template <bool TA, bool TB, bool VEC = true>
 __global__ __launch_bounds__(256, 4) void gemm_f32_kernel(GemmArgs g) {
@@ -220,47 +278,20 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_kernel(GemmArgs g) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  // XCD-aware tile order: blocks b and b+8 share an XCD (and its L2), so give each XCD a
-  // contiguous run of tiles (n fastest): neighbours in a run share their A panel, runs share B.
-  int tile = blockIdx.x;
-  {
-    const int nt = gridDim.x, q = nt >> 3, rem = nt & 7, x = tile & 7, j = tile >> 3;
-    tile = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + j;
-  }
-  // within a run, walk groups of GROUP_M tile rows column by column: the ~128 tiles an XCD has in flight
-  // then cover about GROUP_M x 16 tiles and share 8 A panels and 16 B panels in its 4 MB L2, instead of
-  // 2-3 A panels and every B panel of the matrix
   int m0, n0;
-  {
-    const int tilesM = gridDim.x / g.tilesN, per = GROUP_M * g.tilesN;
-    const int grp = tile / per, rem2 = tile - grp * per, first = grp * GROUP_M;
-    const int gsz = min(GROUP_M, tilesM - first);
-    m0 = (first + rem2 % gsz) * BM;
-    n0 = (rem2 / gsz) * BN;
-  }
+  tile_origin<BM, BN, GROUP_M>(blockIdx.x, gridDim.x, g.tilesN, m0, n0);
   const bool fullA = (g.vecA || !VEC) && (m0 + BM <= g.M), fullB = (g.vecB || !VEC) && (n0 + BN <= g.N);
-  const int z = blockIdx.z, ks = blockIdx.y;
-  const float* A = g.A + z * g.sA;
-  const float* B = g.B + z * g.sB;
-  const bool partial = g.splitk > 1;
-  float* C = partial ? g.slabs + ((int64_t)z * g.splitk + ks) * g.M * g.N : g.C + z * g.sC;
-  const int ldc = partial ? g.N : g.ldc;
-  const float* bias = (g.bias && !partial) ? g.bias + z * g.sbias : nullptr;
-  const int kbeg = ks * g.kchunk, kend = min(g.K, kbeg + g.kchunk);  // kchunk is a multiple of BK
+  const int z = blockIdx.z;
+  const Slice<GemmArgs> sl(g, z, blockIdx.y);
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  clear_acc(acc);
 
-  const int nk = (kend - kbeg + BK - 1) / BK;
+  const int nk = (sl.kend - sl.kbeg + BK - 1) / BK;  // any K: the last step may be ragged
   float4 ra[PIECES], rb[PIECES];
   // A is k-major in memory when TA (stored K x M); B is k-major when !TB (stored K x N)
-  fetch<TA, VEC>(A, g.lda, m0, g.M, kbeg, kend, fullA && kbeg + BK <= kend, tid, ra);
-  fetch<!TB, VEC>(B, g.ldb, n0, g.N, kbeg, kend, fullB && kbeg + BK <= kend, tid, rb);
+  fetch<TA, VEC>(sl.A, g.lda, m0, g.M, sl.kbeg, sl.kend, fullA && sl.kbeg + BK <= sl.kend, tid, ra);
+  fetch<!TB, VEC>(sl.B, g.ldb, n0, g.N, sl.kbeg, sl.kend, fullB && sl.kbeg + BK <= sl.kend, tid, rb);
   stash<TA, LDA>(As[0], tid, ra);
   stash<!TB, LDB>(Bs[0], tid, rb);
   __syncthreads();
@@ -270,10 +301,10 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_kernel(GemmArgs g) {
   for (int kt = 0; kt < nk; ++kt) {
     const bool more = kt + 1 < nk;
     if (more) {
-      const int k0 = kbeg + (kt + 1) * BK;
-      const bool kfull = k0 + BK <= kend;  // block-uniform
-      fetch<TA, VEC>(A, g.lda, m0, g.M, k0, kend, fullA && kfull, tid, ra);
-      fetch<!TB, VEC>(B, g.ldb, n0, g.N, k0, kend, fullB && kfull, tid, rb);
+      const int k0 = sl.kbeg + (kt + 1) * BK;
+      const bool kfull = k0 + BK <= sl.kend;  // block-uniform
+      fetch<TA, VEC>(sl.A, g.lda, m0, g.M, k0, sl.kend, fullA && kfull, tid, ra);
+      fetch<!TB, VEC>(sl.B, g.ldb, n0, g.N, k0, sl.kend, fullB && kfull, tid, rb);
     }
 #pragma unroll
     for (int kk = 0; kk < BK; kk += 2) {
@@ -294,8 +325,7 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_kernel(GemmArgs g) {
     cur ^= 1;
   }
 
-  store_tile(g, acc, C, ldc, bias, partial, m0 + wm * 64, n0 + wn * 64, lane);
-  if (partial && g.counters) finish_splitk(g, z, m0 + wm * 64, n0 + wn * 64, tid);
+  finish_tile(g, acc, sl, z, m0 + wm * 64, n0 + wn * 64, tid);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -313,11 +343,14 @@ __global__ __launch_bounds__(256, 4) void gemm_f32_kernel(GemmArgs g) {
 //     k set the two 32-dim halves of every 64 are swapped (lane fetches dim ^ 32), so that the two half-waves of a
 //     fragment read (k and k+4, same dims) fall on opposite halves of the 64 banks: conflict-free ds_read_b32.
 // Rows / dims past the matrix edge are clamped to valid addresses: their products land in rows / columns never stored.
-template <bool KMAJOR, int KBIT = 2>
+// DIM = tile dimension of the image (128 or 256; row bytes of a k-major image = 4 DIM): a 1 KB piece of a k-major image is
+// 256 / DIM k rows -- two rows of 128 dims, or one whole DMA instruction per row of 256 -- and 16 rows of a dim-major one.
+template <bool KMAJOR, int DIM, int KBIT = 2>
 __device__ __forceinline__ const float* dma_src(const float* P, int ld, int dim0, int dimLimit, int k0, int piece, int lane) {
   if (KMAJOR) {
-    const int krow = 2 * piece + (lane >> 5);
-    const int dim = (4 * (lane & 31)) ^ (((krow >> KBIT) & 1) << 5);  // KBIT: the k bit the two half-waves of a read differ in
+    constexpr int LPR = DIM / 4;  // lanes per k row
+    const int krow = piece * (64 / LPR) + lane / LPR;
+    const int dim = (4 * (lane % LPR)) ^ (((krow >> KBIT) & 1) << 5);  // KBIT: the k bit the two half-waves of a read differ in
     return P + (int64_t)(k0 + krow) * ld + min(dim0 + dim, dimLimit - 4);
   } else {
     // slot s of chunk c holds row (s - 8 * bit) & 15, bit = the chunk-index bit in which the two half-waves of a fragment
@@ -328,20 +361,20 @@ __device__ __forceinline__ const float* dma_src(const float* P, int ld, int dim0
   }
 }
 
-// byte offset inside an 8 KB operand image of this lane's fragment data for the 32-row fragment starting at row d0
-// (a multiple of 32), before the per-step immediates (dim-major: + 512 c'; k-major: + 512 (8c' + i))
-template <bool KMAJOR>
+// byte offset inside an operand image of this lane's fragment data for the 32-row fragment starting at row d0 (a multiple
+// of 32), before the per-step immediates (dim-major: + 512 c'; k-major: + 4 DIM (8c' + i))
+template <bool KMAJOR, int DIM>
 __device__ __forceinline__ int frag_base(int d0, int lane) {
   const int l31 = lane & 31, kh = lane >> 5;
-  if (KMAJOR) return 4 * kh * 512 + ((d0 ^ (kh << 5)) + l31) * 4;
+  if (KMAJOR) return 4 * kh * (4 * DIM) + ((d0 ^ (kh << 5)) + l31) * 4;
   return ((d0 + l31) >> 4) * 1024 + kh * 256 + (((l31 & 15) + 8 * kh) & 15) * 16;
 }
 
-template <bool KMAJOR>
+template <bool KMAJOR, int DIM>
 __device__ __forceinline__ void frag_load(const char* img, int base, int cp, float (&v)[4]) {
   if (KMAJOR) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const float*>(img + base + (8 * cp + i) * 512);
+    for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const float*>(img + base + (8 * cp + i) * (4 * DIM));
   } else {
     const float4 q = *reinterpret_cast<const float4*>(img + base + cp * 512);
     v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
@@ -352,218 +385,77 @@ __device__ __forceinline__ void frag_load(const char* img, int base, int cp, flo
 // s_waitcnt vmcnt(0) in front of every LDS read that follows an LDS-DMA BUILTIN it cannot prove disjoint, which
 // serialises the next tile's fetch with this tile's products.  The kernel orders DMA and reads itself (vmcnt(0) +
 // barrier at the top of each K step).  M0 = LDS base of the instruction (wave-uniform).
-__device__ __forceinline__ void dma_1k(const float* src, unsigned lds_addr) {
+template <class T>
+__device__ __forceinline__ void dma_1k(const T* src, unsigned lds_addr) {
   asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_addr) : "memory");
 }
 
-template <bool TA, bool TB>
-__global__ __launch_bounds__(256, 3) void gemm_f32_kernel_dma(GemmArgs g) {
-  constexpr int TILE = BM * BK * 4;  // 8 KB per operand image
-  // LDS stages: the DMA runs NST - 1 K steps ahead of the products.  A third stage (48 KB of LDS) measured +4 % on the
-  // N/N and +1..4 % on the T/N products stand-alone, -4 % on N/T, and nothing on the training step: two are shipped.
-  constexpr int NST = 2;
-  __shared__ __attribute__((aligned(1024))) char lds[NST][2 * TILE];
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  int tile = blockIdx.x;
-  {
-    const int nt = gridDim.x, q = nt >> 3, rem = nt & 7, x = tile & 7, j = tile >> 3;
-    tile = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + j;
-  }
-  int m0, n0;
-  {
-    const int tilesM = gridDim.x / g.tilesN, per = GROUP_M * g.tilesN;
-    const int grp = tile / per, rem2 = tile - grp * per, first = grp * GROUP_M;
-    const int gsz = min(GROUP_M, tilesM - first);
-    m0 = (first + rem2 % gsz) * BM;
-    n0 = (rem2 / gsz) * BN;
-  }
-  const int z = blockIdx.z, ks = blockIdx.y;
-  const float* A = g.A + z * g.sA;
-  const float* B = g.B + z * g.sB;
-  const bool partial = g.splitk > 1;
-  float* C = partial ? g.slabs + ((int64_t)z * g.splitk + ks) * g.M * g.N : g.C + z * g.sC;
-  const int ldc = partial ? g.N : g.ldc;
-  const float* bias = (g.bias && !partial) ? g.bias + z * g.sbias : nullptr;
-  const int kbeg = ks * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
-  const int nk = (kend - kbeg) / BK;  // the host sends only K ranges that are multiples of BK here
-
-  // A is k-major in memory when TA (stored K x M); B is k-major when !TB (stored K x N).  Wave w DMAs pieces 2w, 2w+1.
-  const float* srcA[2];
-  const float* srcB[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    srcA[i] = dma_src<TA>(A, g.lda, m0, g.M, kbeg, 2 * wave + i, lane);
-    srcB[i] = dma_src<!TB>(B, g.ldb, n0, g.N, kbeg, 2 * wave + i, lane);
-  }
-  const int64_t stepA = TA ? (int64_t)BK * g.lda : BK, stepB = !TB ? (int64_t)BK * g.ldb : BK;
-  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)&lds[0][0];
-  const unsigned my_pieces = __builtin_amdgcn_readfirstlane(lds_base + 2 * wave * 1024);
-  auto stage = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      dma_1k(srcA[i], my_pieces + buf * 2 * TILE + i * 1024);
-      dma_1k(srcB[i], my_pieces + buf * 2 * TILE + TILE + i * 1024);
-      srcA[i] += stepA;
-      srcB[i] += stepB;
-    }
-  };
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int fa0 = frag_base<TA>(wm * 64, lane), fa1 = frag_base<TA>(wm * 64 + 32, lane);
-  const int fb0 = frag_base<!TB>(wn * 64, lane), fb1 = frag_base<!TB>(wn * 64 + 32, lane);
-
-  if (nk > 0) stage(0);
-  if (NST == 3 && nk > 1) stage(1);
-  int cur = 0;
-  for (int kt = 0; kt < nk; ++kt) {
-    if (NST == 3 && kt + 1 < nk)
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // step kt has landed; the 4 instructions of step kt + 1 may still fly
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of step kt have landed ...
-    __syncthreads();                                   // ... and everybody's; all reads of the buffer refilled next are done
-    if (kt + NST - 1 < nk) stage(NST == 3 ? (cur + 2) % 3 : cur ^ 1);
-    const char* ai = lds[cur];
-    const char* bi = lds[cur] + TILE;
-#pragma unroll
-    for (int cp = 0; cp < 2; ++cp) {
-      float a0[4], a1[4], b0[4], b1[4];
-      frag_load<TA>(ai, fa0, cp, a0);
-      frag_load<TA>(ai, fa1, cp, a1);
-      frag_load<!TB>(bi, fb0, cp, b0);
-      frag_load<!TB>(bi, fb1, cp, b1);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[i], b0[i], acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[i], b1[i], acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[i], b0[i], acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[i], b1[i], acc[1][1], 0, 0, 0);
-      }
-    }
-    cur = NST == 3 ? (cur + 1) % 3 : cur ^ 1;
-  }
-  store_tile(g, acc, C, ldc, bias, partial, m0 + wm * 64, n0 + wn * 64, lane);
-  if (partial && g.counters) finish_splitk(g, z, m0 + wm * 64, n0 + wn * 64, tid);
-}
-
-// ------------------------------------------------------------------------------------------------------
-// The LDS-DMA kernel with a 256 x 128 block tile and EIGHT waves (4 x 2, each still 64 x 64): the B tile is fetched
-// once per 256 rows instead of once per 128, i.e. 0.75 x the bytes moved global -> LDS per flop (the quantity the
-// ablation in DESIGN.md 4b shows the kernel's loss to be proportional to), at the same waves per SIMD and the same
-// registers per wave as the 128 x 128 kernel.  Same images, K order and epilogue; the A image is 16 pieces (256 rows),
-// a k-major A row is one whole DMA instruction.
-template <bool KMAJOR>
-__device__ __forceinline__ const float* dma_src_w256(const float* P, int ld, int dim0, int dimLimit, int k0, int piece, int lane) {
-  if (KMAJOR) {  // piece = k row; lane fetches 4 dims; the 32-dim halves of every 64 swapped where bit 2 of k is set
-    const int dim = (4 * lane) ^ (((piece >> 2) & 1) << 5);
-    return P + (int64_t)(k0 + piece) * ld + min(dim0 + dim, dimLimit - 4);
-  }
-  return dma_src<false>(P, ld, dim0, dimLimit, k0, piece, lane);  // 16 pieces of 16 rows
-}
-
-template <bool KMAJOR, int DIM>  // DIM = tile dimension of the image (row bytes of a k-major image = 4 DIM)
-__device__ __forceinline__ int frag_base_w(int d0, int lane) {
-  const int l31 = lane & 31, kh = lane >> 5;
-  if (KMAJOR) return 4 * kh * (4 * DIM) + ((d0 ^ (kh << 5)) + l31) * 4;
-  return ((d0 + l31) >> 4) * 1024 + kh * 256 + (((l31 & 15) + 8 * kh) & 15) * 16;
-}
-
-template <bool KMAJOR, int DIM>
-__device__ __forceinline__ void frag_load_w(const char* img, int base, int cp, float (&v)[4]) {
-  if (KMAJOR) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const float*>(img + base + (8 * cp + i) * (4 * DIM));
-  } else {
-    const float4 q = *reinterpret_cast<const float4*>(img + base + cp * 512);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  }
-}
-
-template <bool TA, bool TB>
-__global__ __launch_bounds__(512, 2) void gemm_f32_kernel_dma256(GemmArgs g) {
-  constexpr int BMW = 256;
-  constexpr int TILE_A = BMW * BK * 4, TILE_B = BN * BK * 4, STAGE = TILE_A + TILE_B;  // 16 + 8 KB
+// The LDS-DMA kernel at two block-tile heights.  BMW = 128: four waves as 2 x 2, the tiling of gemm_f32_kernel.  BMW = 256:
+// EIGHT waves (4 x 2, each still 64 x 64): the B tile is fetched once per 256 rows instead of once per 128, i.e. 0.75 x the
+// bytes moved global -> LDS per flop (the quantity the ablation in DESIGN.md 4b shows the kernel's loss to be proportional
+// to), at the same waves per SIMD and the same registers per wave.  Same images, K order and epilogue; the A image of the
+// 256-row form is 16 pieces, a k-major A row one whole DMA instruction.
+// LDS stages: two -- the DMA runs one K step ahead of the products.  A third stage (48 KB of LDS) measured +4 % on the N/N
+// and +1..4 % on the T/N products of the 128-row form stand-alone, -4 % on N/T, and nothing on the training step.
+template <int BMW, bool TA, bool TB>
+__global__ __launch_bounds__(2 * BMW, BMW == 128 ? 3 : 2) void gemm_f32_kernel_dma(GemmArgs g) {
+  static_assert(BMW == 128 || BMW == 256, "block-tile height");
+  constexpr int TILE_A = BMW * BK * 4, TILE_B = BN * BK * 4, STAGE = TILE_A + TILE_B;  // 8 or 16 KB of A, 8 KB of B
+  constexpr int PB = 256 / BMW;  // every wave DMAs A pieces 2w, 2w+1 and B pieces PB w ... (B: 8 pieces over 4 or 8 waves)
   __shared__ __attribute__((aligned(1024))) char lds[2][STAGE];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  int tile = blockIdx.x;
-  {
-    const int nt = gridDim.x, q = nt >> 3, rem = nt & 7, x = tile & 7, j = tile >> 3;
-    tile = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + j;
-  }
   int m0, n0;
-  {
-    constexpr int GM = GROUP_M / 2;  // the same 1024 rows per group
-    const int tilesM = gridDim.x / g.tilesN, per = GM * g.tilesN;
-    const int grp = tile / per, rem2 = tile - grp * per, first = grp * GM;
-    const int gsz = min(GM, tilesM - first);
-    m0 = (first + rem2 % gsz) * BMW;
-    n0 = (rem2 / gsz) * BN;
-  }
-  const int z = blockIdx.z, ks = blockIdx.y;
-  const float* A = g.A + z * g.sA;
-  const float* B = g.B + z * g.sB;
-  const bool partial = g.splitk > 1;
-  float* C = partial ? g.slabs + ((int64_t)z * g.splitk + ks) * g.M * g.N : g.C + z * g.sC;
-  const int ldc = partial ? g.N : g.ldc;
-  const float* bias = (g.bias && !partial) ? g.bias + z * g.sbias : nullptr;
-  const int kbeg = ks * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
-  const int nk = (kend - kbeg) / BK;
+  tile_origin<BMW, BN, GROUP_M * 128 / BMW>(blockIdx.x, gridDim.x, g.tilesN, m0, n0);
+  const int z = blockIdx.z;
+  const Slice<GemmArgs> sl(g, z, blockIdx.y);
+  const int nk = (sl.kend - sl.kbeg) / BK;  // the host sends only K ranges that are multiples of BK here
 
-  // wave w DMAs A pieces 2w, 2w+1 (of 16) and B piece w (of 8)
+  // A is k-major in memory when TA (stored K x M); B is k-major when !TB (stored K x N)
   const float* srcA[2];
+  const float* srcB[PB];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) srcA[i] = dma_src_w256<TA>(A, g.lda, m0, g.M, kbeg, 2 * wave + i, lane);
-  const float* srcB = dma_src<!TB>(B, g.ldb, n0, g.N, kbeg, wave, lane);
+  for (int i = 0; i < 2; ++i) srcA[i] = dma_src<TA, BMW>(sl.A, g.lda, m0, g.M, sl.kbeg, 2 * wave + i, lane);
+#pragma unroll
+  for (int i = 0; i < PB; ++i) srcB[i] = dma_src<!TB, BN>(sl.B, g.ldb, n0, g.N, sl.kbeg, PB * wave + i, lane);
   const int64_t stepA = TA ? (int64_t)BK * g.lda : BK, stepB = !TB ? (int64_t)BK * g.ldb : BK;
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)&lds[0][0];
   const unsigned pa = __builtin_amdgcn_readfirstlane(lds_base + 2 * wave * 1024);
-  const unsigned pb = __builtin_amdgcn_readfirstlane(lds_base + TILE_A + wave * 1024);
-  auto stage = [&](int buf) {
+  const unsigned pb = __builtin_amdgcn_readfirstlane(lds_base + TILE_A + PB * wave * 1024);
+  auto stage = [&](int buf) {  // (instruction order as each form has always had it: A B A B, or A A B)
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       dma_1k(srcA[i], pa + buf * STAGE + i * 1024);
+      if (PB == 2) dma_1k(srcB[i], pb + buf * STAGE + i * 1024);
       srcA[i] += stepA;
     }
-    dma_1k(srcB, pb + buf * STAGE);
-    srcB += stepB;
+    if (PB == 1) dma_1k(srcB[0], pb + buf * STAGE);
+#pragma unroll
+    for (int i = 0; i < PB; ++i) srcB[i] += stepB;
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  clear_acc(acc);
 
-  const int fa0 = frag_base_w<TA, BMW>(wm * 64, lane), fa1 = frag_base_w<TA, BMW>(wm * 64 + 32, lane);
-  const int fb0 = frag_base_w<!TB, BN>(wn * 64, lane), fb1 = frag_base_w<!TB, BN>(wn * 64 + 32, lane);
+  const int fa0 = frag_base<TA, BMW>(wm * 64, lane), fa1 = frag_base<TA, BMW>(wm * 64 + 32, lane);
+  const int fb0 = frag_base<!TB, BN>(wn * 64, lane), fb1 = frag_base<!TB, BN>(wn * 64 + 32, lane);
 
   if (nk > 0) stage(0);
   int cur = 0;
   for (int kt = 0; kt < nk; ++kt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of step kt have landed ...
+    __syncthreads();                                   // ... and everybody's; all reads of the buffer refilled next are done
     if (kt + 1 < nk) stage(cur ^ 1);
     const char* ai = lds[cur];
     const char* bi = lds[cur] + TILE_A;
 #pragma unroll
     for (int cp = 0; cp < 2; ++cp) {
       float a0[4], a1[4], b0[4], b1[4];
-      frag_load_w<TA, BMW>(ai, fa0, cp, a0);
-      frag_load_w<TA, BMW>(ai, fa1, cp, a1);
-      frag_load_w<!TB, BN>(bi, fb0, cp, b0);
-      frag_load_w<!TB, BN>(bi, fb1, cp, b1);
+      frag_load<TA, BMW>(ai, fa0, cp, a0);
+      frag_load<TA, BMW>(ai, fa1, cp, a1);
+      frag_load<!TB, BN>(bi, fb0, cp, b0);
+      frag_load<!TB, BN>(bi, fb1, cp, b1);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[i], b0[i], acc[0][0], 0, 0, 0);
@@ -574,8 +466,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_kernel_dma256(GemmArgs g) {
     }
     cur ^= 1;
   }
-  store_tile(g, acc, C, ldc, bias, partial, m0 + wm * 64, n0 + wn * 64, lane);
-  if (partial && g.counters) finish_splitk(g, z, m0 + wm * 64, n0 + wn * 64, tid);
+  finish_tile(g, acc, sl, z, m0 + wm * 64, n0 + wn * 64, tid);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -673,26 +564,31 @@ struct SignPhase {
 // next segment's first two stages are in flight while a tile is stored.
 // (r05 also carried a split-product form of this kernel, variant 7; since the planes kernel it served no launch of any
 // configuration and was retired in r06.)
-template <bool TA, bool TB>
-__global__ __launch_bounds__(512, 2) void gemm_f32_kernel_streamk(GemmArgs g) {
-  constexpr int BMW = 256, BNW = 256;
-  constexpr int TILE = BMW * BK * 4, STAGE = 2 * TILE;
-  constexpr int NST = 3;
-  constexpr int SLAB = BMW * BNW;  // floats per piece
-  __shared__ __attribute__((aligned(1024))) char lds[NST][STAGE];
-  __shared__ int s_fix[4];  // last ticket?, first and last contributor, which piece of the first
+//
+// The schedule below is shared with bf2::gemm_bf16_streamk_kernel (256 x 256 tiles and 512 threads both: a piece is 128
+// accumulator values per thread); each kernel has its own K step, LDS ring and wait counts.
+constexpr int SK_SLAB = 256 * 256;  // floats per piece
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int P = gridDim.x, b = blockIdx.x;
-  const int nk = g.K / BK, nt = g.sk_tiles, full = g.sk_full;
-  const int64_t R = (int64_t)(nt - full * P) * nk;
-  const int64_t beg = b * R / P, end = (b + 1) * R / P;
-  const int t0 = (int)(beg / nk);                                        // first stream-K tile this workgroup touches
-  const int nseg = full + (end > beg ? (int)((end - 1) / nk) - t0 + 1 : 0);  // + 0, 1 or 2 pieces
-
-  // segment i of this workgroup: position v in the tile order, K steps [kb, ke)
-  auto segment = [&](int i, int& v, int& kb, int& ke) {
+// The partition: this workgroup's range [beg, end) of the cut's R K steps, the first stream-K tile t0 it touches, and its
+// segments -- `full` whole tiles, then 0, 1 or 2 pieces
+struct StreamK {
+  int P, b, nk, nt, full, t0, nseg;
+  int64_t R, beg, end;
+  template <class Args>
+  __device__ __forceinline__ StreamK(const Args& g, int bk) {
+    P = gridDim.x;
+    b = blockIdx.x;
+    nk = g.K / bk;
+    nt = g.sk_tiles;
+    full = g.sk_full;
+    R = (int64_t)(nt - full * P) * nk;
+    beg = b * R / P;
+    end = (b + 1) * R / P;
+    t0 = (int)(beg / nk);
+    nseg = full + (end > beg ? (int)((end - 1) / nk) - t0 + 1 : 0);
+  }
+  // segment i: position v in the tile order (tile_origin), K steps [kb, ke)
+  __device__ __forceinline__ void segment(int i, int& v, int& kb, int& ke) const {
     if (i < full) {
       v = i * P + b; kb = 0; ke = nk;
     } else {
@@ -702,59 +598,117 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_kernel_streamk(GemmArgs g) {
       kb = (int)(max(beg, lo) - lo);
       ke = (int)(min(end, lo + nk) - lo);
     }
-  };
-  // the tile order of the other kernels (each XCD walks its own run of the list; 8-row groups column-wise inside it)
-  auto origin = [&](int v, int& m0, int& n0) {
-    const int q = nt >> 3, rem = nt & 7, x = v & 7, j = v >> 3;
-    const int tile = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + j;
-    constexpr int GM = GROUP_M / 2;
-    const int tilesM = nt / g.tilesN, per = GM * g.tilesN;
-    const int grp = tile / per, rem2 = tile - grp * per, first = grp * GM;
-    const int gsz = min(GM, tilesM - first);
-    m0 = (first + rem2 % gsz) * BMW;
-    n0 = (rem2 / gsz) * BNW;
-  };
+  }
+  __device__ __forceinline__ int64_t steps() const { return (int64_t)full * nk + (end - beg); }  // of all segments
+};
 
-  // DMA cursor: two K steps ahead of the products, across segment boundaries
+// DMA cursor: segment i, K steps [k, ke) of it still to fetch.  It runs ahead of the products across segment boundaries:
+// issue() fetches one K step and advances the sources, open() points them at segment i (and sets k, ke).
+struct SkCursor {
+  int i = 0, k = 0, ke = 0;
+};
+template <class Issue, class Open>
+__device__ __forceinline__ void sk_fetch(const StreamK& sk, SkCursor& d, Issue issue, Open open) {
+  if (d.i >= sk.nseg) return;
+  issue();
+  if (++d.k == d.ke && ++d.i < sk.nseg) open();
+}
+
+// End of a segment that is a PIECE of stream-K tile t.  Element q * 512 + tid of a piece is accumulator value q = acc_at(q) of
+// thread tid; the piece of workgroup w lies in slab 2 w (+ 1 when the tile is the second one of w's range).  The workgroup
+// that draws the tile's last ticket adds the pieces memory -> memory in workgroup order and stores the tile; where(q, row,
+// col) is the kernel's map from accumulator value q to the element of C.
+template <class Args, class AccAt, class Where>
+__device__ __forceinline__ void sk_finish_piece(const Args& g, const StreamK& sk, int t, int tid, AccAt acc_at, Where where) {
+  __shared__ int s_fix[4];  // last ticket?, first and last contributor, which piece of the first
+  const int P = sk.P, nk = sk.nk;
+  const int64_t R = sk.R;
+  float* mine = g.slabs + (size_t)(2 * sk.b + (t - sk.t0)) * SK_SLAB + tid;
+#pragma unroll
+  for (int q = 0; q < 128; ++q) __hip_atomic_store(mine + q * 512, acc_at(q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    // the workgroup whose range holds K step i of the region: the largest w with floor(w R / P) <= i
+    const int w0 = (int)((((int64_t)t * nk + 1) * P - 1) / R), w1 = (int)((((int64_t)(t + 1) * nk) * P - 1) / R);
+    const unsigned old = __hip_atomic_fetch_add(g.counters + t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int last = old == (unsigned)(w1 - w0);
+    if (last) __hip_atomic_store(g.counters + t, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_fix[0] = last; s_fix[1] = w0; s_fix[2] = w1;
+    s_fix[3] = (w0 * R / P < (int64_t)t * nk) ? 1 : 0;  // the first contributor's piece is its second one unless its range starts here
+  }
+  __syncthreads();
+  if (!s_fix[0]) return;
+  const int w0 = s_fix[1], w1 = s_fix[2];
+  const float* sl0 = g.slabs + (size_t)(2 * w0 + s_fix[3]) * SK_SLAB + tid;
+  // 32 values per thread and round trip: the accumulators are dead here, and the tile waits on latency, not bandwidth
+  for (int q0 = 0; q0 < 128; q0 += 32) {
+    float v[32];
+#pragma unroll
+    for (int u = 0; u < 32; ++u) v[u] = __hip_atomic_load(sl0 + (q0 + u) * 512, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int w = w0 + 1; w <= w1; ++w) {
+      const float* sl = g.slabs + (size_t)(2 * w) * SK_SLAB + tid;
+#pragma unroll
+      for (int u = 0; u < 32; ++u) v[u] += __hip_atomic_load(sl + (q0 + u) * 512, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+#pragma unroll
+    for (int u = 0; u < 32; ++u) {
+      int row, col;
+      where(q0 + u, row, col);
+      if (col < g.N && row < g.M) {
+        float* cp = g.C + (int64_t)row * g.ldc + col;
+        float x = v[u];
+        if (g.bias) x += g.bias[col];
+        if (g.accumulate) x += *cp;
+        if (g.act == 1) x = sk_sigmoid(x);
+        *cp = x;
+      }
+    }
+  }
+}
+
+template <bool TA, bool TB>
+__global__ __launch_bounds__(512, 2) void gemm_f32_kernel_streamk(GemmArgs g) {
+  constexpr int BMW = 256, BNW = 256;
+  constexpr int TILE = BMW * BK * 4, STAGE = 2 * TILE;
+  constexpr int NST = 3;
+  __shared__ __attribute__((aligned(1024))) char lds[NST][STAGE];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const StreamK sk(g, BK);
+  auto origin = [&](int v, int& m0, int& n0) { tile_origin<BMW, BNW, GROUP_M / 2>(v, sk.nt, g.tilesN, m0, n0); };
+
+  // DMA cursor: two K steps ahead of the products
   const int64_t stepA = TA ? (int64_t)BK * g.lda : BK, stepB = !TB ? (int64_t)BK * g.ldb : BK;
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)&lds[0][0];
   const unsigned pa = __builtin_amdgcn_readfirstlane(lds_base + 2 * wave * 1024);
   const float* srcA[2];
   const float* srcB[2];
-  int di = 0, dk = 0, dke = 0;
+  SkCursor d;
   auto dma_open = [&]() {
-    int v, kb, ke, m0, n0;
-    segment(di, v, kb, ke);
+    int v, m0, n0;
+    sk.segment(d.i, v, d.k, d.ke);
     origin(v, m0, n0);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      srcA[i] = dma_src_w256<TA>(g.A, g.lda, m0, g.M, kb * BK, 2 * wave + i, lane);
-      srcB[i] = dma_src_w256<!TB>(g.B, g.ldb, n0, g.N, kb * BK, 2 * wave + i, lane);
+      srcA[i] = dma_src<TA, BMW>(g.A, g.lda, m0, g.M, d.k * BK, 2 * wave + i, lane);
+      srcB[i] = dma_src<!TB, BNW>(g.B, g.ldb, n0, g.N, d.k * BK, 2 * wave + i, lane);
     }
-    dk = kb;
-    dke = ke;
   };
   auto fetch = [&](int buf) {
-    if (di >= nseg) return;
+    sk_fetch(sk, d, [&]() {
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      dma_1k(srcA[i], pa + buf * STAGE + i * 1024);
-      dma_1k(srcB[i], pa + buf * STAGE + TILE + i * 1024);
-      srcA[i] += stepA;
-      srcB[i] += stepB;
-    }
-    if (++dk == dke && ++di < nseg) dma_open();
+      for (int i = 0; i < 2; ++i) {
+        dma_1k(srcA[i], pa + buf * STAGE + i * 1024);
+        dma_1k(srcB[i], pa + buf * STAGE + TILE + i * 1024);
+        srcA[i] += stepA;
+        srcB[i] += stepB;
+      }
+    }, dma_open);
   };
 
   f32x16 acc[2][4];
-  auto clear = [&]() {
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  };
   auto store = [&](int m0, int n0) {  // the wave's two 64-column halves through the 64 x 64 epilogue
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -762,20 +716,20 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_kernel_streamk(GemmArgs g) {
       store_tile(g, part, g.C, g.ldc, g.bias, false, m0 + wm * 64, n0 + wn * 128 + 64 * h, lane);
     }
   };
-  clear();
+  clear_acc(acc);
 
   int fa[2], fb[4];
 #pragma unroll
-  for (int i = 0; i < 2; ++i) fa[i] = frag_base_w<TA, BMW>(wm * 64 + 32 * i, lane);
+  for (int i = 0; i < 2; ++i) fa[i] = frag_base<TA, BMW>(wm * 64 + 32 * i, lane);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) fb[j] = frag_base_w<!TB, BNW>(wn * 128 + 32 * j, lane);
+  for (int j = 0; j < 4; ++j) fb[j] = frag_base<!TB, BNW>(wn * 128 + 32 * j, lane);
 
-  const int64_t F = (int64_t)full * nk + (end - beg);  // K steps of this workgroup, all segments
-  if (nseg > 0) dma_open();
+  const int64_t F = sk.steps();
+  if (sk.nseg > 0) dma_open();
   fetch(0);
   fetch(1);
   int ci = 0, cv = 0, ck = 0, cke = 0;
-  if (nseg > 0) segment(0, cv, ck, cke);
+  if (sk.nseg > 0) sk.segment(0, cv, ck, cke);
   int cur = 0;
   for (int64_t f = 0; f < F; ++f) {
     // step f has landed when at most the 4 instructions of step f + 1 are in flight (loads return in order; stores of an
@@ -788,86 +742,40 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_kernel_streamk(GemmArgs g) {
     fetch((cur + 2) % NST);
     const char* ai = lds[cur];
     const char* bi = lds[cur] + TILE;
-    {
 #pragma unroll
-      for (int cp = 0; cp < 2; ++cp) {
-        float a[2][4], bb[4][4];
+    for (int cp = 0; cp < 2; ++cp) {
+      float a[2][4], bb[4][4];
 #pragma unroll
-        for (int i = 0; i < 2; ++i) frag_load_w<TA, BMW>(ai, fa[i], cp, a[i]);
+      for (int i = 0; i < 2; ++i) frag_load<TA, BMW>(ai, fa[i], cp, a[i]);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) frag_load_w<!TB, BNW>(bi, fb[j], cp, bb[j]);
+      for (int j = 0; j < 4; ++j) frag_load<!TB, BNW>(bi, fb[j], cp, bb[j]);
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
+      for (int k = 0; k < 4; ++k)
 #pragma unroll
-          for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][k], bb[j][k], acc[i][j], 0, 0, 0);
-      }
+          for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][k], bb[j][k], acc[i][j], 0, 0, 0);
     }
     cur = (cur + 1) % NST;
     if (++ck < cke) continue;
 
-    // ---- end of a segment
+    // ---- end of a segment: a whole tile is stored, a piece goes through its slab
     int m0, n0;
     origin(cv, m0, n0);
-    if (ci < full) {
+    if (ci < sk.full) {
       store(m0, n0);
     } else {
-      const int t = cv - full * P;
-      float* mine = g.slabs + (size_t)(2 * b + (t - t0)) * SLAB;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r)
-            __hip_atomic_store(mine + ((i * 4 + j) * 16 + r) * 512 + tid, acc[i][j][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) {
-        // the workgroup whose range holds K step i of the region: the largest w with floor(w R / P) <= i
-        const int w0 = (int)((((int64_t)t * nk + 1) * P - 1) / R), w1 = (int)((((int64_t)(t + 1) * nk) * P - 1) / R);
-        const unsigned old = __hip_atomic_fetch_add(g.counters + t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = old == (unsigned)(w1 - w0);
-        if (last) __hip_atomic_store(g.counters + t, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_fix[0] = last; s_fix[1] = w0; s_fix[2] = w1;
-        s_fix[3] = (w0 * R / P < (int64_t)t * nk) ? 1 : 0;  // the first contributor's piece is its second one unless its range starts here
-      }
-      __syncthreads();
-      if (s_fix[0]) {
-        // memory -> memory: element q * 512 + tid of a piece is accumulator register q of thread tid.  Piece of workgroup w:
-        // slab 2 w (+ 1 for the first contributor when the tile is the second one of its range)
-        const int w0 = s_fix[1], w1 = s_fix[2];
-        const float* sl0 = g.slabs + (size_t)(2 * w0 + s_fix[3]) * SLAB + tid;
-        const int kh = lane >> 5, col = n0 + wn * 128 + (lane & 31), row = m0 + wm * 64 + 4 * kh;
-        // 32 values per thread and round trip: the accumulators are dead here, and the tile waits on latency, not bandwidth
-        for (int q0 = 0; q0 < 128; q0 += 32) {
-          float v[32];
-#pragma unroll
-          for (int u = 0; u < 32; ++u) v[u] = __hip_atomic_load(sl0 + (q0 + u) * 512, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          for (int w = w0 + 1; w <= w1; ++w) {
-            const float* sl = g.slabs + (size_t)(2 * w) * SLAB + tid;
-#pragma unroll
-            for (int u = 0; u < 32; ++u) v[u] += __hip_atomic_load(sl + (q0 + u) * 512, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-#pragma unroll
-          for (int u = 0; u < 32; ++u) {
-            const int q = q0 + u, i = q >> 6, j = (q >> 4) & 3, r = q & 15;
-            const int c = col + 32 * j, rw = row + 32 * i + (r & 3) + 8 * (r >> 2);
-            if (c < g.N && rw < g.M) {
-              float* cp = g.C + (int64_t)rw * g.ldc + c;
-              float x = v[u];
-              if (g.bias) x += g.bias[c];
-              if (g.accumulate) x += *cp;
-              if (g.act == 1) x = sk_sigmoid(x);
-              *cp = x;
-            }
-          }
-        }
-      }
+      // accumulator value q = register q & 15 of MFMA tile (q >> 6, (q >> 4) & 3); C/D layout of the 32x32 MFMA as in store_tile
+      const int col = n0 + wn * 128 + (lane & 31), row = m0 + wm * 64 + 4 * (lane >> 5);
+      sk_finish_piece(g, sk, cv - sk.full * sk.P, tid, [&](int q) { return acc[q >> 6][(q >> 4) & 3][q & 15]; },
+                      [&](int q, int& rw, int& c) {
+                        const int i = q >> 6, j = (q >> 4) & 3, r = q & 15;
+                        c = col + 32 * j;
+                        rw = row + 32 * i + (r & 3) + 8 * (r >> 2);
+                      });
     }
-    clear();
-    if (++ci < nseg) segment(ci, cv, ck, cke);
+    clear_acc(acc);
+    if (++ci < sk.nseg) sk.segment(ci, cv, ck, cke);
   }
 }
 
@@ -929,35 +837,18 @@ __global__ __launch_bounds__(256, SK_SPLIT_OCC) void gemm_f32_kernel_split3(Gemm
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  int tile = blockIdx.x;
-  {
-    const int nt = gridDim.x, q = nt >> 3, rem = nt & 7, x = tile & 7, j = tile >> 3;
-    tile = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + j;
-  }
   int m0, n0;
-  {
-    const int tilesM = gridDim.x / g.tilesN, per = GROUP_M * g.tilesN;
-    const int grp = tile / per, rem2 = tile - grp * per, first = grp * GROUP_M;
-    const int gsz = min(GROUP_M, tilesM - first);
-    m0 = (first + rem2 % gsz) * BM;
-    n0 = (rem2 / gsz) * BN;
-  }
-  const int z = blockIdx.z, ks = blockIdx.y;
-  const float* A = g.A + z * g.sA;
-  const float* B = g.B + z * g.sB;
-  const bool partial = g.splitk > 1;
-  float* C = partial ? g.slabs + ((int64_t)z * g.splitk + ks) * g.M * g.N : g.C + z * g.sC;
-  const int ldc = partial ? g.N : g.ldc;
-  const float* bias = (g.bias && !partial) ? g.bias + z * g.sbias : nullptr;
-  const int kbeg = ks * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
-  const int nk = (kend - kbeg) / BK;
+  tile_origin<BM, BN, GROUP_M>(blockIdx.x, gridDim.x, g.tilesN, m0, n0);
+  const int z = blockIdx.z;
+  const Slice<GemmArgs> sl(g, z, blockIdx.y);
+  const int nk = (sl.kend - sl.kbeg) / BK;
 
   const float* srcA[2];
   const float* srcB[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    srcA[i] = dma_src<TA, 3>(A, g.lda, m0, g.M, kbeg, 2 * wave + i, lane);
-    srcB[i] = dma_src<!TB, 3>(B, g.ldb, n0, g.N, kbeg, 2 * wave + i, lane);
+    srcA[i] = dma_src<TA, BM, 3>(sl.A, g.lda, m0, g.M, sl.kbeg, 2 * wave + i, lane);
+    srcB[i] = dma_src<!TB, BN, 3>(sl.B, g.ldb, n0, g.N, sl.kbeg, 2 * wave + i, lane);
   }
   const int64_t stepA = TA ? (int64_t)BK * g.lda : BK, stepB = !TB ? (int64_t)BK * g.ldb : BK;
   const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)&lds[0][0];
@@ -973,12 +864,7 @@ __global__ __launch_bounds__(256, SK_SPLIT_OCC) void gemm_f32_kernel_split3(Gemm
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  clear_acc(acc);
 
 #pragma unroll
   for (int i = 0; i < NST - 1; ++i)
@@ -986,7 +872,7 @@ __global__ __launch_bounds__(256, SK_SPLIT_OCC) void gemm_f32_kernel_split3(Gemm
   int cur = 0;
   // sign phases (SignPhase above): this slice's steps are the global K steps kbeg / BK ...; `held` = the sign the accumulators carry
   SignPhase ph;
-  ph.init(g.flip_q, kbeg / BK);
+  ph.init(g.flip_q, sl.kbeg / BK);
   unsigned held = 0u;
   // One K step; sg = -1 in a negative stretch: the B fragments' values are multiplied by it before they are split (exact; eight
   // v_pk_mul_f32 per wave and step beside the ~150 of the splits.  Two copies of the body, one with the negation folded into the
@@ -1041,8 +927,7 @@ __global__ __launch_bounds__(256, SK_SPLIT_OCC) void gemm_f32_kernel_split3(Gemm
     cur = (cur + 1) % NST;
   }
   if (held) negate_acc();  // the last stretch held -sum
-  store_tile(g, acc, C, ldc, bias, partial, m0 + wm * 64, n0 + wn * 64, lane);
-  if (partial && g.counters) finish_splitk(g, z, m0 + wm * 64, n0 + wn * 64, tid);
+  finish_tile(g, acc, sl, z, m0 + wm * 64, n0 + wn * 64, tid);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1101,20 +986,8 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_kernel_planes(GemmArgs g) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  int tile = blockIdx.x;
-  {
-    const int nt = gridDim.x, q = nt >> 3, rem = nt & 7, x = tile & 7, j = tile >> 3;
-    tile = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + j;
-  }
   int m0, n0;
-  {
-    constexpr int GM = GROUP_M / 2;
-    const int tilesM = gridDim.x / g.tilesN, per = GM * g.tilesN;
-    const int grp = tile / per, rem2 = tile - grp * per, first = grp * GM;
-    const int gsz = min(GM, tilesM - first);
-    m0 = (first + rem2 % gsz) * BMW;
-    n0 = (rem2 / gsz) * BNW;
-  }
+  tile_origin<BMW, BNW, GROUP_M / 2>(blockIdx.x, gridDim.x, g.tilesN, m0, n0);
   // unsplit, unbatched products only (the launcher sees to it)
   const int nk = g.K / BK;
 
@@ -1220,12 +1093,7 @@ __global__ __launch_bounds__(512, 2) void gemm_f32_kernel_planes(GemmArgs g) {
   };
 
   f32x16 acc[2][NJ];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  clear_acc(acc);
 
   // the products of the step in stage `buf`; STORE: the next step's values (in nx) are split and written to the other stage
   // BETWEEN the groups of twelve MFMAs -- no dependence between the two, one basic block
@@ -1341,26 +1209,11 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel_pl3(GemmArgs g) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  int tile = blockIdx.x;
-  {
-    const int nt = gridDim.x, q = nt >> 3, rem = nt & 7, x = tile & 7, j = tile >> 3;
-    tile = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + j;
-  }
   int m0, n0;
-  {
-    const int tilesM = gridDim.x / g.tilesN, per = GROUP_M * g.tilesN;
-    const int grp = tile / per, rem2 = tile - grp * per, first = grp * GROUP_M;
-    const int gsz = min(GROUP_M, tilesM - first);
-    m0 = (first + rem2 % gsz) * BM;
-    n0 = (rem2 / gsz) * BN;
-  }
-  const int z = blockIdx.z, ks = blockIdx.y;
-  const bool partial = g.splitk > 1;
-  float* C = partial ? g.slabs + ((int64_t)z * g.splitk + ks) * g.M * g.N : g.C + z * g.sC;
-  const int ldc = partial ? g.N : g.ldc;
-  const float* bias = (g.bias && !partial) ? g.bias + z * g.sbias : nullptr;
-  const int kbeg = ks * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
-  const int nk = (kend - kbeg) / BK;
+  tile_origin<BM, BN, GROUP_M>(blockIdx.x, gridDim.x, g.tilesN, m0, n0);
+  const int z = blockIdx.z;
+  const Slice<GemmArgs> sl(g, z, blockIdx.y);  // (its A and B are unused here: the operands are the planes)
+  const int kbeg = sl.kbeg, nk = (sl.kend - sl.kbeg) / BK;
 
   // ---- staging.  One DMA instruction = 1 KB = four k rows of one plane tile (16 lanes x 16 B per row).  Lane (kr = lane >> 4,
   // j = lane & 15) fetches, for k row 4 kq + kr, the 16 bytes that belong at position j of the row's LDS image: the image keeps
@@ -1423,12 +1276,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel_pl3(GemmArgs g) {
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  clear_acc(acc);
   auto negate_acc = [&]() {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -1463,8 +1311,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel_pl3(GemmArgs g) {
     cur ^= 1;
   }
   if (held) negate_acc();
-  store_tile(g, acc, C, ldc, bias, partial, m0 + wm * 64, n0 + wn * 64, lane);
-  if (partial && g.counters) finish_splitk(g, z, m0 + wm * 64, n0 + wn * 64, tid);
+  finish_tile(g, acc, sl, z, m0 + wm * 64, n0 + wn * 64, tid);
 }
 
 // The three bf16 planes of an fp32 matrix (sk_split_rows): dst[p][r][c], p = 0 hi, 1 mid, 2 lo, the pieces split3() makes (round
@@ -1588,41 +1435,17 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16_kernel(GemmArgs g) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  int tile = blockIdx.x;
-  {
-    const int nt = gridDim.x, q = nt >> 3, rem = nt & 7, x = tile & 7, j = tile >> 3;
-    tile = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + j;
-  }
-  // within a run, walk groups of GROUP_M tile rows column by column: the ~128 tiles an XCD has in flight
-  // then cover about GROUP_M x 16 tiles and share 8 A panels and 16 B panels in its 4 MB L2, instead of
-  // 2-3 A panels and every B panel of the matrix
   int m0, n0;
-  {
-    const int tilesM = gridDim.x / g.tilesN, per = GROUP_M * g.tilesN;
-    const int grp = tile / per, rem2 = tile - grp * per, first = grp * GROUP_M;
-    const int gsz = min(GROUP_M, tilesM - first);
-    m0 = (first + rem2 % gsz) * BM;
-    n0 = (rem2 / gsz) * BN;
-  }
+  tile_origin<BM, BN, GROUP_M>(blockIdx.x, gridDim.x, g.tilesN, m0, n0);
   const bool fullA = g.vecA && (m0 + BM <= g.M), fullB = g.vecB && (n0 + BN <= g.N);
-  const int z = blockIdx.z, ks = blockIdx.y;
-  const float* A = g.A + z * g.sA;
-  const float* B = g.B + z * g.sB;
-  const bool partial = g.splitk > 1;
-  float* C = partial ? g.slabs + ((int64_t)z * g.splitk + ks) * g.M * g.N : g.C + z * g.sC;
-  const int ldc = partial ? g.N : g.ldc;
-  const float* bias = (g.bias && !partial) ? g.bias + z * g.sbias : nullptr;
-  const int kbeg = ks * g.kchunk, kend = min(g.K, kbeg + g.kchunk);  // kchunk is a multiple of BK
+  const Slice<GemmArgs> sl(g, blockIdx.z, blockIdx.y);
+  const float *A = sl.A, *B = sl.B;
+  const int kbeg = sl.kbeg, kend = sl.kend;
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  clear_acc(acc);
 
-  const int nk = (kend - kbeg + BK - 1) / BK;
+  const int nk = (kend - kbeg + BK - 1) / BK;  // any K: the last step may be ragged
   float4 ra[PIECES], rb[PIECES];
   fetch<TA>(A, g.lda, m0, g.M, kbeg, kend, fullA && kbeg + BK <= kend, tid, ra);
   fetch<!TB>(B, g.ldb, n0, g.N, kbeg, kend, fullB && kbeg + BK <= kend, tid, rb);
@@ -1662,29 +1485,7 @@ __global__ __launch_bounds__(256, 3) void gemm_bf16_kernel(GemmArgs g) {
     cur ^= 1;
   }
 
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = n0 + wn * 64 + j * 32 + l31;
-      if (col >= g.N) continue;
-      const float bv = bias ? bias[col] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = m0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-        if (row < g.M) {
-          float* cp = C + (int64_t)row * ldc + col;
-          float v = acc[i][j][r] + bv;
-          if (!partial) {
-            if (g.accumulate) v += *cp;
-            if (g.act == 1) v = sk_sigmoid(v);
-            *cp = v;
-          } else {
-            __hip_atomic_store(cp, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // write-through: read by another XCD
-          }
-        }
-      }
-    }
+  store_tile(g, acc, sl.C, sl.ldc, sl.bias, sl.partial, m0 + wm * 64, n0 + wn * 64, lane);  // (these slabs go to splitk_reduce_kernel)
 }
 
 }  // namespace bf
@@ -1771,240 +1572,28 @@ __device__ __forceinline__ bf16x8 kmaj_frag(const char* tile, int addr, int rowb
   return __builtin_bit_cast(bf16x8, v);
 }
 
+// One wave's part of a 256 x BN tile (8 waves as 2 x 4): what gemm_bf16_nt_kernel and gemm_bf16_streamk_kernel share.
 // AKM / BKM: the operand is K-major in memory (A stored [K][M], lda = row stride of a k row; B stored [K][N]).
-template <int BN, bool AKM = false, bool BKM = false>
-__global__ __launch_bounds__(NT, 2) void gemm_bf16_nt_kernel(Args g) {
-  constexpr int TM = 8, TN = BN / 64;            // MFMA tiles per wave
-  constexpr int PA = BM / 8 / 8, PB = BN / 8 / 8;  // 1 KB pieces per wave per K step (A: 4, B: 4 or 2)
-  constexpr int ABYTES = BM * BK * 2, BBYTES = BN * BK * 2;
-  __shared__ __attribute__((aligned(1024))) char lds[2 * (ABYTES + BBYTES)];
+template <int BN, bool AKM, bool BKM>
+struct WaveTile {
+  static constexpr int TM = 8, TN = BN / 64;               // MFMA tiles per wave
+  static constexpr int PA = BM / 8 / 8, PB = BN / 8 / 8;   // 1 KB pieces per wave per K step (A: 4, B: 4 or 2)
+  static constexpr int ABYTES = BM * BK * 2, BBYTES = BN * BK * 2, STAGE = ABYTES + BBYTES;
 
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wm = w >> 2, wn = w & 3;
-  int tile = blockIdx.x;
-  {
-    const int nt = gridDim.x, q = nt >> 3, rem = nt & 7, x = tile & 7, j = tile >> 3;
-    tile = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + j;
-  }
-  int m0, n0;
-  {
-    const int tilesM = gridDim.x / g.tilesN, per = GROUP_M * g.tilesN;
-    const int grp = tile / per, rem2 = tile - grp * per, first = grp * GROUP_M;
-    const int gsz = min(GROUP_M, tilesM - first);
-    m0 = (first + rem2 % gsz) * BM;
-    n0 = (rem2 / gsz) * BN;
-  }
-  const int z = blockIdx.z, ks = blockIdx.y;
-  const __bf16* A = g.A + z * g.sA;
-  const __bf16* B = g.B + z * g.sB;
-  const bool partial = g.splitk > 1;
-  float* C = partial ? g.slabs + ((int64_t)z * g.splitk + ks) * g.M * g.N : g.C + z * g.sC;
-  const int ldc = partial ? g.N : g.ldc;
-  const float* bias = (g.bias && !partial) ? g.bias + z * g.sbias : nullptr;
-  const int kbeg = ks * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
-  const int nk = (kend - kbeg) / BK;
-
-  // per-lane DMA sources (rows past the matrix edge are clamped: their products land in rows/cols never stored)
-  const __bf16* srcA[PA];
-  const __bf16* srcB[PB];
-#pragma unroll
-  for (int i = 0; i < PA; ++i) {
-    int r, c;
-    if (AKM) {  // r = k row of the tile, c = first of 8 dims; dims past the padded width are clamped (never stored)
-      kmaj_piece_src<BM>(w * PA + i, lane, r, c);
-      srcA[i] = A + (int64_t)(kbeg + r) * g.lda + min(m0 + c, g.lda - 8);
-    } else {
-      piece_src(w * PA + i, lane, r, c);
-      srcA[i] = A + (int64_t)min(m0 + r, g.M - 1) * g.lda + kbeg + c * 8;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < PB; ++i) {
-    int r, c;
-    if (BKM) {
-      kmaj_piece_src<BN>(w * PB + i, lane, r, c);
-      srcB[i] = B + (int64_t)(kbeg + r) * g.ldb + min(n0 + c, g.ldb - 8);
-    } else {
-      piece_src(w * PB + i, lane, r, c);
-      srcB[i] = B + (int64_t)min(n0 + r, g.N - 1) * g.ldb + kbeg + c * 8;
-    }
-  }
-  const int64_t stepA = AKM ? (int64_t)BK * g.lda : BK, stepB = BKM ? (int64_t)BK * g.ldb : BK;
-  // K-major instantiations issue the DMA as inline assembly: behind the LDS-DMA BUILTIN hipcc puts an s_waitcnt vmcnt(0) in
-  // front of the transposed LDS reads (it cannot prove them disjoint from the DMA's destination), which serialises the next
-  // K step's fetch with this step's products (measured: 20-30 % slower).  The kernel orders DMA and reads itself (vmcnt(0)
-  // + barrier at the top of every K step).  The NT instantiation keeps the builtin (its plain loads are proven disjoint).
-  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
-  const unsigned pieceA = __builtin_amdgcn_readfirstlane(lds_base + w * PA * 1024);
-  const unsigned pieceB = __builtin_amdgcn_readfirstlane(lds_base + ABYTES + w * PB * 1024);
-  auto stage = [&](int buf, int kt) {
-    char* a = lds + buf * (ABYTES + BBYTES);
-    char* b = a + ABYTES;
-#pragma unroll
-    for (int i = 0; i < PA; ++i) {
-      if (AKM || BKM)
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(srcA[i] + kt * stepA),
-                     "s"(pieceA + buf * (ABYTES + BBYTES) + i * 1024)
-                     : "memory");
-      else
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcA[i] + kt * stepA),
-                                         (__attribute__((address_space(3))) void*)(a + (w * PA + i) * 1024), 16, 0, 0);
-    }
-#pragma unroll
-    for (int i = 0; i < PB; ++i) {
-      if (AKM || BKM)
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(srcB[i] + kt * stepB),
-                     "s"(pieceB + buf * (ABYTES + BBYTES) + i * 1024)
-                     : "memory");
-      else
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcB[i] + kt * stepB),
-                                         (__attribute__((address_space(3))) void*)(b + (w * PB + i) * 1024), 16, 0, 0);
-    }
-  };
-
-  f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // fragment addresses: lane holds row (lane & 15) of a 16-row tile, 8 consecutive k at chunk (lane >> 4) + 4 * kstep;
-  // a tile further down adds 16 rows = 2048 B (the rotation repeats every 16 rows), kstep 1 flips slot bit 2 (^ 64 B)
-  const int fa = img(wm * 128 + (lane & 15), lane >> 4);
-  const int fb = img(wn * (BN / 4) + (lane & 15), lane >> 4);
-  // K-major operands: one transposed-read address per 16-dim block of the wave's tile (the chunk rotation is per block)
-  int ka[AKM ? TM : 1], kb[BKM ? TN : 1];
-  if (AKM) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i) ka[i] = kmaj_frag_addr<BM>(wm * TM + i, lane);
-  }
-  if (BKM) {
-#pragma unroll
-    for (int j = 0; j < TN; ++j) kb[j] = kmaj_frag_addr<BN>(wn * TN + j, lane);
-  }
-
-  if (nk > 0) stage(0, 0);
-  int cur = 0;
-  for (int kt = 0; kt < nk; ++kt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of step kt have landed ...
-    __syncthreads();                                   // ... and everybody's; all reads of the other buffer are done
-    if (kt + 1 < nk) stage(cur ^ 1, kt + 1);
-    const char* a = lds + cur * (ABYTES + BBYTES);
-    const char* b = a + ABYTES;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      bf16x8 af[TM], bfr[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        if (AKM)
-          af[i] = kmaj_frag(a, ka[i] + s * 32 * (2 * BM), 2 * BM);
-        else
-          af[i] = *reinterpret_cast<const bf16x8*>(a + ((fa ^ (s << 6)) + i * 2048));
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        if (BKM)
-          bfr[j] = kmaj_frag(b, kb[j] + s * 32 * (2 * BN), 2 * BN);
-        else
-          bfr[j] = *reinterpret_cast<const bf16x8*>(b + ((fb ^ (s << 6)) + j * 2048));
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
-    cur ^= 1;
-  }
-
-  // epilogue: C/D layout of the 16x16 MFMA: col = lane & 15, row = 4 * (lane >> 4) + reg
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int col = n0 + wn * (BN / 4) + j * 16 + (lane & 15);
-    if (col >= g.N) continue;
-    const float bv = bias ? bias[col] : 0.f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = m0 + wm * 128 + i * 16 + 4 * (lane >> 4) + r;
-        if (row < g.M) {
-          float* cp = C + (int64_t)row * ldc + col;
-          float v = acc[i][j][r] + bv;
-          if (!partial) {
-            if (g.accumulate) v += *cp;
-            if (g.act == 1) v = sk_sigmoid(v);
-          }
-          *cp = v;
-        }
-      }
-  }
-}
-
-// The 256 x 256 instantiation as a PERSISTENT stream-K kernel (r03): the schedule, piece / ticket protocol and fix-up of
-// gemm_f32_kernel_streamk above (one workgroup per CU; whole rounds of tiles data-parallel, the K steps of the remaining
-// tiles laid end to end and cut into gridDim.x equal ranges; pieces through slabs, last ticket adds them in workgroup
-// order), on this kernel's images, fragments and two LDS buffers.  It replaces split-K for the unbatched products with
-// few tiles (data gradients: 350 tiles, weight gradients: 196): no K slabs of the whole matrix, no second launch.
-template <bool AKM, bool BKM>
-__global__ __launch_bounds__(NT, 2) void gemm_bf16_streamk_kernel(Args g) {
-  constexpr int BN = 256, TM = 8, TN = 4, PA = 4, PB = 4;
-  constexpr int ABYTES = BM * BK * 2, BBYTES = BN * BK * 2, STAGE = ABYTES + BBYTES;
-  constexpr int SLAB = BM * BN;
-  __shared__ __attribute__((aligned(1024))) char lds[2 * STAGE];
-  __shared__ int s_fix[4];
-
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wm = w >> 2, wn = w & 3;
-  const int P = gridDim.x, b = blockIdx.x;
-  const int nk = g.K / BK, nt = g.sk_tiles, full = g.sk_full;
-  const int64_t R = (int64_t)(nt - full * P) * nk;
-  const int64_t beg = b * R / P, end = (b + 1) * R / P;
-  const int t0 = (int)(beg / nk);
-  const int nseg = full + (end > beg ? (int)((end - 1) / nk) - t0 + 1 : 0);
-
-  auto segment = [&](int i, int& v, int& kb, int& ke) {
-    if (i < full) {
-      v = i * P + b; kb = 0; ke = nk;
-    } else {
-      const int t = t0 + (i - full);
-      const int64_t lo = (int64_t)t * nk;
-      v = full * P + t;
-      kb = (int)(max(beg, lo) - lo);
-      ke = (int)(min(end, lo + nk) - lo);
-    }
-  };
-  auto origin = [&](int v, int& m0, int& n0) {
-    const int q = nt >> 3, rem = nt & 7, x = v & 7, j = v >> 3;
-    const int tile = (x < rem ? x * (q + 1) : rem * (q + 1) + (x - rem) * q) + j;
-    const int tilesM = nt / g.tilesN, per = GROUP_M * g.tilesN;
-    const int grp = tile / per, rem2 = tile - grp * per, first = grp * GROUP_M;
-    const int gsz = min(GROUP_M, tilesM - first);
-    m0 = (first + rem2 % gsz) * BM;
-    n0 = (rem2 / gsz) * BN;
-  };
-
-  // DMA cursor: one K step ahead of the products, across segment boundaries
-  const int64_t stepA = AKM ? (int64_t)BK * g.lda : BK, stepB = BKM ? (int64_t)BK * g.ldb : BK;
-  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
-  const unsigned pieceA = __builtin_amdgcn_readfirstlane(lds_base + w * PA * 1024);
-  const unsigned pieceB = __builtin_amdgcn_readfirstlane(lds_base + ABYTES + w * PB * 1024);
-  const __bf16* srcA[PA];
-  const __bf16* srcB[PB];
-  int di = 0, dk = 0, dke = 0;
-  auto dma_open = [&]() {
-    int v, kb, ke, m0, n0;
-    segment(di, v, kb, ke);
-    origin(v, m0, n0);
-    const int kbeg = kb * BK;
+  // per-lane DMA sources of the K step at kbeg of the tile at (m0, n0).  Rows past the matrix edge are clamped (their
+  // products land in rows / cols never stored); a K-major operand: r = k row of the tile, c = first of 8 dims, dims past the
+  // padded width clamped
+  static __device__ __forceinline__ void sources(const Args& g, const __bf16* A, const __bf16* B, int m0, int n0, int kbeg, int w, int lane,
+                                                 const __bf16* (&srcA)[PA], const __bf16* (&srcB)[PB]) {
 #pragma unroll
     for (int i = 0; i < PA; ++i) {
       int r, c;
       if (AKM) {
         kmaj_piece_src<BM>(w * PA + i, lane, r, c);
-        srcA[i] = g.A + (int64_t)(kbeg + r) * g.lda + min(m0 + c, g.lda - 8);
+        srcA[i] = A + (int64_t)(kbeg + r) * g.lda + min(m0 + c, g.lda - 8);
       } else {
         piece_src(w * PA + i, lane, r, c);
-        srcA[i] = g.A + (int64_t)min(m0 + r, g.M - 1) * g.lda + kbeg + c * 8;
+        srcA[i] = A + (int64_t)min(m0 + r, g.M - 1) * g.lda + kbeg + c * 8;
       }
     }
 #pragma unroll
@@ -2012,165 +1601,236 @@ __global__ __launch_bounds__(NT, 2) void gemm_bf16_streamk_kernel(Args g) {
       int r, c;
       if (BKM) {
         kmaj_piece_src<BN>(w * PB + i, lane, r, c);
-        srcB[i] = g.B + (int64_t)(kbeg + r) * g.ldb + min(n0 + c, g.ldb - 8);
+        srcB[i] = B + (int64_t)(kbeg + r) * g.ldb + min(n0 + c, g.ldb - 8);
       } else {
         piece_src(w * PB + i, lane, r, c);
-        srcB[i] = g.B + (int64_t)min(n0 + r, g.N - 1) * g.ldb + kbeg + c * 8;
+        srcB[i] = B + (int64_t)min(n0 + r, g.N - 1) * g.ldb + kbeg + c * 8;
       }
     }
-    dk = kb;
-    dke = ke;
-  };
-  auto fetch = [&](int buf) {
-    if (di >= nseg) return;
+  }
+
+  // The DMAs of one K step (sources + offA / offB elements) into LDS stage `buf`; pieceA / pieceB = the LDS addresses of this
+  // wave's first pieces in stage 0 (wave-uniform).  BUILTIN == false issues them as inline assembly (dma_1k): behind the
+  // LDS-DMA BUILTIN hipcc puts an s_waitcnt vmcnt(0) in front of the transposed LDS reads (it cannot prove them disjoint from
+  // the DMA's destination), which serialises the next K step's fetch with this step's products (measured: 20-30 % slower).
+  // The kernels order DMA and reads themselves (vmcnt(0) + barrier at the top of every K step).  The tile kernel's NT
+  // instantiation keeps the builtin (its plain loads are proven disjoint).
+  template <bool BUILTIN>
+  static __device__ __forceinline__ void stage(char* lds, unsigned pieceA, unsigned pieceB, int buf, int w, const __bf16* const (&srcA)[PA],
+                                               const __bf16* const (&srcB)[PB], int64_t offA, int64_t offB) {
+    char* a = lds + buf * STAGE;
+    char* b = a + ABYTES;
 #pragma unroll
     for (int i = 0; i < PA; ++i) {
-      asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(srcA[i]), "s"(pieceA + buf * STAGE + i * 1024)
-                   : "memory");
-      srcA[i] += stepA;
+      if (BUILTIN)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcA[i] + offA),
+                                         (__attribute__((address_space(3))) void*)(a + (w * PA + i) * 1024), 16, 0, 0);
+      else
+        dma_1k(srcA[i] + offA, pieceA + buf * STAGE + i * 1024);
     }
 #pragma unroll
     for (int i = 0; i < PB; ++i) {
-      asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(srcB[i]), "s"(pieceB + buf * STAGE + i * 1024)
-                   : "memory");
-      srcB[i] += stepB;
+      if (BUILTIN)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcB[i] + offB),
+                                         (__attribute__((address_space(3))) void*)(b + (w * PB + i) * 1024), 16, 0, 0);
+      else
+        dma_1k(srcB[i] + offB, pieceB + buf * STAGE + i * 1024);
     }
-    if (++dk == dke && ++di < nseg) dma_open();
-  };
-
-  f32x4 acc[TM][TN];
-  auto clear = [&]() {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  };
-  clear();
-
-  const int fa = img(wm * 128 + (lane & 15), lane >> 4);
-  const int fb = img(wn * (BN / 4) + (lane & 15), lane >> 4);
-  int ka[AKM ? TM : 1], kb_[BKM ? TN : 1];
-  if (AKM) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i) ka[i] = kmaj_frag_addr<BM>(wm * TM + i, lane);
-  }
-  if (BKM) {
-#pragma unroll
-    for (int j = 0; j < TN; ++j) kb_[j] = kmaj_frag_addr<BN>(wn * TN + j, lane);
   }
 
-  const int64_t F = (int64_t)full * nk + (end - beg);
-  if (nseg > 0) dma_open();
-  fetch(0);
-  int ci = 0, cv = 0, ck = 0, cke = 0;
-  if (nseg > 0) segment(0, cv, ck, cke);
-  int cur = 0;
-  for (int64_t f = 0; f < F; ++f) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of step f have landed (and an epilogue's stores) ...
-    __syncthreads();                                   // ... and everybody's; all reads of the other buffer are done
-    fetch(cur ^ 1);
-    const char* a = lds + cur * STAGE;
-    const char* bt = a + ABYTES;
+  // fragment addresses: lane holds row (lane & 15) of a 16-row tile, 8 consecutive k at chunk (lane >> 4) + 4 * kstep;
+  // a tile further down adds 16 rows = 2048 B (the rotation repeats every 16 rows), kstep 1 flips slot bit 2 (^ 64 B).
+  // K-major operands: one transposed-read address per 16-dim block of the wave's tile (the chunk rotation is per block)
+  struct Frags {
+    int fa, fb, ka[AKM ? TM : 1], kb[BKM ? TN : 1];
+    __device__ __forceinline__ Frags(int wm, int wn, int lane) {
+      fa = img(wm * 128 + (lane & 15), lane >> 4);
+      fb = img(wn * (BN / 4) + (lane & 15), lane >> 4);
+      if (AKM) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) ka[i] = kmaj_frag_addr<BM>(wm * TM + i, lane);
+      }
+      if (BKM) {
+#pragma unroll
+        for (int j = 0; j < TN; ++j) kb[j] = kmaj_frag_addr<BN>(wn * TN + j, lane);
+      }
+    }
+  };
+
+  // the products of one K step on the operand images in LDS stage `buf`
+  static __device__ __forceinline__ void kstep(const char* lds, int buf, const Frags& f, f32x4 (&acc)[TM][TN]) {
+    const char* a = lds + buf * STAGE;
+    const char* b = a + ABYTES;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       bf16x8 af[TM], bfr[TN];
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         if (AKM)
-          af[i] = kmaj_frag(a, ka[i] + s * 32 * (2 * BM), 2 * BM);
+          af[i] = kmaj_frag(a, f.ka[i] + s * 32 * (2 * BM), 2 * BM);
         else
-          af[i] = *reinterpret_cast<const bf16x8*>(a + ((fa ^ (s << 6)) + i * 2048));
+          af[i] = *reinterpret_cast<const bf16x8*>(a + ((f.fa ^ (s << 6)) + i * 2048));
       }
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         if (BKM)
-          bfr[j] = kmaj_frag(bt, kb_[j] + s * 32 * (2 * BN), 2 * BN);
+          bfr[j] = kmaj_frag(b, f.kb[j] + s * 32 * (2 * BN), 2 * BN);
         else
-          bfr[j] = *reinterpret_cast<const bf16x8*>(bt + ((fb ^ (s << 6)) + j * 2048));
+          bfr[j] = *reinterpret_cast<const bf16x8*>(b + ((f.fb ^ (s << 6)) + j * 2048));
       }
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
     }
-    cur ^= 1;
-    if (++ck < cke) continue;
+  }
 
-    // ---- end of a segment.  C/D layout of the 16x16 MFMA: col = lane & 15, row = 4 * (lane >> 4) + reg
-    int m0, n0;
-    origin(cv, m0, n0);
-    const int col0 = n0 + wn * (BN / 4) + (lane & 15), row0 = m0 + wm * 128 + 4 * (lane >> 4);
-    if (ci < full) {
+  static __device__ __forceinline__ void clear(f32x4 (&acc)[TM][TN]) {
 #pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int col = col0 + j * 16;
-        if (col >= g.N) continue;
-        const float bv = g.bias ? g.bias[col] : 0.f;
+    for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
+      for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+
+  // epilogue of the tile at (m0, n0).  C/D layout of the 16x16 MFMA: col = lane & 15, row = 4 * (lane >> 4) + reg
+  static __device__ __forceinline__ void store(const Args& g, const f32x4 (&acc)[TM][TN], float* C, int ldc, const float* bias, bool partial,
+                                               int m0, int n0, int wm, int wn, int lane) {
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int row = row0 + i * 16 + r;
-            if (row < g.M) {
-              float* cp = g.C + (int64_t)row * g.ldc + col;
-              float v = acc[i][j][r] + bv;
-              if (g.accumulate) v += *cp;
-              if (g.act == 1) v = sk_sigmoid(v);
-              *cp = v;
-            }
-          }
-      }
-    } else {
-      const int t = cv - full * P;
-      float* mine = g.slabs + (size_t)(2 * b + (t - t0)) * SLAB + tid;
+    for (int j = 0; j < TN; ++j) {
+      const int col = n0 + wn * (BN / 4) + j * 16 + (lane & 15);
+      if (col >= g.N) continue;
+      const float bv = bias ? bias[col] : 0.f;
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            __hip_atomic_store(mine + ((i * TN + j) * 4 + r) * 512, acc[i][j][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) {
-        const int w0 = (int)((((int64_t)t * nk + 1) * P - 1) / R), w1 = (int)((((int64_t)(t + 1) * nk) * P - 1) / R);
-        const unsigned old = __hip_atomic_fetch_add(g.counters + t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = old == (unsigned)(w1 - w0);
-        if (last) __hip_atomic_store(g.counters + t, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_fix[0] = last; s_fix[1] = w0; s_fix[2] = w1;
-        s_fix[3] = (w0 * R / P < (int64_t)t * nk) ? 1 : 0;
-      }
-      __syncthreads();
-      if (s_fix[0]) {
-        const int w0 = s_fix[1], w1 = s_fix[2];
-        const float* sl0 = g.slabs + (size_t)(2 * w0 + s_fix[3]) * SLAB + tid;
-        for (int q0 = 0; q0 < 128; q0 += 32) {
-          float v[32];
-#pragma unroll
-          for (int u = 0; u < 32; ++u) v[u] = __hip_atomic_load(sl0 + (q0 + u) * 512, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          for (int ww = w0 + 1; ww <= w1; ++ww) {
-            const float* sl = g.slabs + (size_t)(2 * ww) * SLAB + tid;
-#pragma unroll
-            for (int u = 0; u < 32; ++u) v[u] += __hip_atomic_load(sl + (q0 + u) * 512, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-#pragma unroll
-          for (int u = 0; u < 32; ++u) {
-            const int q = q0 + u, i = q >> 4, j = (q >> 2) & 3, r = q & 3;
-            const int col = col0 + j * 16, row = row0 + i * 16 + r;
-            if (col < g.N && row < g.M) {
-              float* cp = g.C + (int64_t)row * g.ldc + col;
-              float x = v[u];
-              if (g.bias) x += g.bias[col];
-              if (g.accumulate) x += *cp;
-              if (g.act == 1) x = sk_sigmoid(x);
-              *cp = x;
+        for (int r = 0; r < 4; ++r) {
+          const int row = m0 + wm * 128 + i * 16 + 4 * (lane >> 4) + r;
+          if (row < g.M) {
+            float* cp = C + (int64_t)row * ldc + col;
+            float v = acc[i][j][r] + bv;
+            if (!partial) {
+              if (g.accumulate) v += *cp;
+              if (g.act == 1) v = sk_sigmoid(v);
             }
+            *cp = v;
           }
         }
-      }
     }
-    clear();
-    if (++ci < nseg) segment(ci, cv, ck, cke);
+  }
+};
+
+template <int BN, bool AKM = false, bool BKM = false>
+__global__ __launch_bounds__(NT, 2) void gemm_bf16_nt_kernel(Args g) {
+  using W = WaveTile<BN, AKM, BKM>;
+  __shared__ __attribute__((aligned(1024))) char lds[2 * W::STAGE];
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int wm = w >> 2, wn = w & 3;
+  int m0, n0;
+  tile_origin<BM, BN, GROUP_M>(blockIdx.x, gridDim.x, g.tilesN, m0, n0);
+  const Slice<Args> sl(g, blockIdx.z, blockIdx.y);
+  const int nk = (sl.kend - sl.kbeg) / BK;
+
+  const __bf16* srcA[W::PA];
+  const __bf16* srcB[W::PB];
+  W::sources(g, sl.A, sl.B, m0, n0, sl.kbeg, w, lane, srcA, srcB);
+  const int64_t stepA = AKM ? (int64_t)BK * g.lda : BK, stepB = BKM ? (int64_t)BK * g.ldb : BK;
+  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
+  const unsigned pieceA = __builtin_amdgcn_readfirstlane(lds_base + w * W::PA * 1024);
+  const unsigned pieceB = __builtin_amdgcn_readfirstlane(lds_base + W::ABYTES + w * W::PB * 1024);
+  auto stage = [&](int buf, int kt) { W::template stage<!(AKM || BKM)>(lds, pieceA, pieceB, buf, w, srcA, srcB, kt * stepA, kt * stepB); };
+
+  f32x4 acc[W::TM][W::TN];
+  W::clear(acc);
+  const typename W::Frags fr(wm, wn, lane);
+
+  if (nk > 0) stage(0, 0);
+  int cur = 0;
+  for (int kt = 0; kt < nk; ++kt) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of step kt have landed ...
+    __syncthreads();                                   // ... and everybody's; all reads of the other buffer are done
+    if (kt + 1 < nk) stage(cur ^ 1, kt + 1);
+    W::kstep(lds, cur, fr, acc);
+    cur ^= 1;
+  }
+  W::store(g, acc, sl.C, sl.ldc, sl.bias, sl.partial, m0, n0, wm, wn, lane);
+}
+
+// The 256 x 256 instantiation as a PERSISTENT stream-K kernel (r03): the schedule, piece / ticket protocol and fix-up of
+// gemm_f32_kernel_streamk above (StreamK, sk_fetch, sk_finish_piece: one workgroup per CU; whole rounds of tiles
+// data-parallel, the K steps of the remaining tiles laid end to end and cut into gridDim.x equal ranges; pieces through
+// slabs, last ticket adds them in workgroup order), on this kernel's images, fragments and two LDS buffers.  It replaces
+// split-K for the unbatched products with few tiles (data gradients: 350 tiles, weight gradients: 196): no K slabs of the
+// whole matrix, no second launch.
+template <bool AKM, bool BKM>
+__global__ __launch_bounds__(NT, 2) void gemm_bf16_streamk_kernel(Args g) {
+  constexpr int BN = 256;
+  using W = WaveTile<BN, AKM, BKM>;
+  __shared__ __attribute__((aligned(1024))) char lds[2 * W::STAGE];
+
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int wm = w >> 2, wn = w & 3;
+  const StreamK sk(g, BK);
+  auto origin = [&](int v, int& m0, int& n0) { tile_origin<BM, BN, GROUP_M>(v, sk.nt, g.tilesN, m0, n0); };
+
+  // DMA cursor: one K step ahead of the products
+  const int64_t stepA = AKM ? (int64_t)BK * g.lda : BK, stepB = BKM ? (int64_t)BK * g.ldb : BK;
+  const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)lds;
+  const unsigned pieceA = __builtin_amdgcn_readfirstlane(lds_base + w * W::PA * 1024);
+  const unsigned pieceB = __builtin_amdgcn_readfirstlane(lds_base + W::ABYTES + w * W::PB * 1024);
+  const __bf16* srcA[W::PA];
+  const __bf16* srcB[W::PB];
+  SkCursor d;
+  auto dma_open = [&]() {
+    int v, m0, n0;
+    sk.segment(d.i, v, d.k, d.ke);
+    origin(v, m0, n0);
+    W::sources(g, g.A, g.B, m0, n0, d.k * BK, w, lane, srcA, srcB);
+  };
+  auto fetch = [&](int buf) {
+    sk_fetch(sk, d, [&]() {
+      W::template stage<false>(lds, pieceA, pieceB, buf, w, srcA, srcB, 0, 0);
+#pragma unroll
+      for (int i = 0; i < W::PA; ++i) srcA[i] += stepA;
+#pragma unroll
+      for (int i = 0; i < W::PB; ++i) srcB[i] += stepB;
+    }, dma_open);
+  };
+
+  f32x4 acc[W::TM][W::TN];
+  W::clear(acc);
+  const typename W::Frags fr(wm, wn, lane);
+
+  const int64_t F = sk.steps();
+  if (sk.nseg > 0) dma_open();
+  fetch(0);
+  int ci = 0, cv = 0, ck = 0, cke = 0;
+  if (sk.nseg > 0) sk.segment(0, cv, ck, cke);
+  int cur = 0;
+  for (int64_t f = 0; f < F; ++f) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of step f have landed (and an epilogue's stores) ...
+    __syncthreads();                                   // ... and everybody's; all reads of the other buffer are done
+    fetch(cur ^ 1);
+    W::kstep(lds, cur, fr, acc);
+    cur ^= 1;
+    if (++ck < cke) continue;
+
+    // ---- end of a segment: a whole tile is stored, a piece goes through its slab
+    int m0, n0;
+    origin(cv, m0, n0);
+    if (ci < sk.full) {
+      W::store(g, acc, g.C, g.ldc, g.bias, false, m0, n0, wm, wn, lane);
+    } else {
+      // accumulator value q = register q & 3 of MFMA tile (q >> 4, (q >> 2) & 3); C/D layout as in WaveTile::store
+      const int col0 = n0 + wn * (BN / 4) + (lane & 15), row0 = m0 + wm * 128 + 4 * (lane >> 4);
+      sk_finish_piece(g, sk, cv - sk.full * sk.P, tid, [&](int q) { return acc[q >> 4][(q >> 2) & 3][q & 3]; },
+                      [&](int q, int& row, int& col) {
+                        col = col0 + ((q >> 2) & 3) * 16;
+                        row = row0 + (q >> 4) * 16 + (q & 3);
+                      });
+    }
+    W::clear(acc);
+    if (++ci < sk.nseg) sk.segment(ci, cv, ck, cke);
   }
 }
 
@@ -2305,10 +1965,10 @@ GemmFn gemm_fn(int kernel, bool vec, int transA, int transB) {
                                          {gemm_f32_kernel<true, false, false>, gemm_f32_kernel<true, true, false>}};
   static const GemmFn split[2][2] = {{gemm_f32_kernel_split3<false, false>, gemm_f32_kernel_split3<false, true>},
                                      {gemm_f32_kernel_split3<true, false>, nullptr}};
-  static const GemmFn dma[2][2] = {{gemm_f32_kernel_dma<false, false>, gemm_f32_kernel_dma<false, true>},
-                                   {gemm_f32_kernel_dma<true, false>, nullptr}};
-  static const GemmFn wide[2][2] = {{gemm_f32_kernel_dma256<false, false>, gemm_f32_kernel_dma256<false, true>},
-                                    {gemm_f32_kernel_dma256<true, false>, nullptr}};
+  static const GemmFn dma[2][2] = {{gemm_f32_kernel_dma<128, false, false>, gemm_f32_kernel_dma<128, false, true>},
+                                   {gemm_f32_kernel_dma<128, true, false>, nullptr}};
+  static const GemmFn wide[2][2] = {{gemm_f32_kernel_dma<256, false, false>, gemm_f32_kernel_dma<256, false, true>},
+                                    {gemm_f32_kernel_dma<256, true, false>, nullptr}};
   static const GemmFn streamk[2][2] = {{gemm_f32_kernel_streamk<false, false>, gemm_f32_kernel_streamk<false, true>},
                                        {gemm_f32_kernel_streamk<true, false>, nullptr}};
   static const GemmFn bf16[2][2] = {{bf::gemm_bf16_kernel<false, false>, bf::gemm_bf16_kernel<false, true>},

@@ -35,8 +35,8 @@ P_MI355X = 256                   # streamk_wgs() on 256 CUs
 KERNELS = {
     K_F32: dict(name="gemm_f32_kernel", tile=(128, 128), bk=16, ring=2, threads=256, persistent=False, group=GROUP_M, any_k=True),
     K_SPLIT: dict(name="gemm_f32_kernel_split3", tile=(128, 128), bk=16, ring=2, threads=256, persistent=False, group=GROUP_M),
-    K_DMA: dict(name="gemm_f32_kernel_dma", tile=(128, 128), bk=16, ring=2, threads=256, persistent=False, group=GROUP_M),
-    K_WIDE: dict(name="gemm_f32_kernel_dma256", tile=(256, 128), bk=16, ring=2, threads=512, persistent=False, group=GROUP_M // 2),
+    K_DMA: dict(name="gemm_f32_kernel_dma<128>", tile=(128, 128), bk=16, ring=2, threads=256, persistent=False, group=GROUP_M),
+    K_WIDE: dict(name="gemm_f32_kernel_dma<256>", tile=(256, 128), bk=16, ring=2, threads=512, persistent=False, group=GROUP_M // 2),
     K_STREAMK: dict(name="gemm_f32_kernel_streamk", tile=(256, 256), bk=16, ring=3, threads=512, persistent=True, group=GROUP_M // 2),
     K_BF16: dict(name="bf::gemm_bf16_kernel", tile=(128, 128), bk=32, ring=2, threads=256, persistent=False, group=GROUP_M, any_k=True),
     K_PLANES: dict(name="gemm_f32_kernel_planes", tile=(256, 128), bk=16, ring=4, threads=512, persistent=False, group=GROUP_M // 2),
@@ -339,6 +339,16 @@ def _dim(c, g, which, what):
         (what.isdigit() and v == int(what))
 
 
+def xcd_remainder(g):
+    """The XCD runs of the tile list are of two lengths and more than one tile long: nt > 8 and nt % 8 != 0."""
+    return g["tiles"] > 8 and g["tiles"] % 8 != 0
+
+
+def ragged_group(g):
+    """The last group of tile rows is smaller than the others and is walked over more than one tile column."""
+    return g["tilesM"] > g["group"] and g["tilesM"] % g["group"] != 0 and g["tilesN"] > 1
+
+
 def _slice_signs(g, s):
     kb, ke = g["slices"][s]
     return [sign_of_step(g["flip_q"], k) for k in range(kb // 16, cdiv(ke, 16))]
@@ -395,6 +405,10 @@ PREDICATES = {
     "sk_two_tiles": lambda c, g: (lambda nt, full, nk, R, rg: any(n == 2 for _, _, _, n in rg))(*_sk(c, g)),
     "sk_first_piece_second": lambda c, g: (lambda nt, full, nk, R, rg: any(streamk_fixup(t, nk, R)[2] for t in range(nt - full * P_MI355X)))(*_sk(c, g)),
     "sk_refused": lambda c, g, nk: g["cut"] is None and c.ws and c.K // (64 if c.entry == "mm" else 16) == nk,
+    "sk_cut": lambda c, g, nt, full: g["cut"] == (nt, full),      # the accepted partition: tiles, whole rounds in front of the cut
+    "xcd_remainder": lambda c, g: xcd_remainder(g),
+    "ragged_group": lambda c, g: ragged_group(g),
+    "ragged_m": lambda c, g: c.M % g["tile"][0] != 0,
     "thr": lambda c, g, name, side: bool(THRESHOLDS[name](c, g)) == side,
 }
 
@@ -448,7 +462,7 @@ def _mk():
     add(f, "f32", 1, NN, 33, 40, 64, K_F32, [("sigmoid",), ("inkernel_reduce",)], ["sigmoid_before_acc", "acc_per_slice"], kind="sigmoid",
         act=1, acc=True, splitk=2)
 
-    # ---------------- the 128 x 128 LDS-DMA kernels: gemm_f32_kernel_dma (variant 3), _split3 (variant 2), and _pl3
+    # ---------------- the 128 x 128 LDS-DMA kernels: gemm_f32_kernel_dma<128> (variant 3), _split3 (variant 2), and _pl3
     for f, v, kid in (("f32_dma", 3, K_DMA), ("f32_split3", 2, K_SPLIT)):
         for n in (1, 2, 3):
             add(f, "f32", v, (NT, NN, TN)[n - 1], 132, 124, 16 * n, kid, [("nk", n), ("nk_ring+1",)] if n == 3 else [("nk", n)],
@@ -510,7 +524,7 @@ def _mk():
     add("embed", "f32", 4, TN, 260, 132, 80, K_WIDE, [("a_kmajor",)], ["kmajor_clamp"], kind="embed")
     add("embed", "mm", 0, (1, 1), 260, 132, 192, K_BF2, [("a_kmajor",)], ["partial_col_tile"], kind="embed", bias=False)
 
-    # ---------------- the 256-row kernels: gemm_f32_kernel_dma256 (variant 4) and gemm_f32_kernel_planes (variant 9)
+    # ---------------- the 256-row kernels: gemm_f32_kernel_dma<256> (variant 4) and gemm_f32_kernel_planes (variant 9)
     for f, v, kid in (("f32_wide", 4, K_WIDE), ("f32_planes", 9, K_PLANES)):
         is_wide = kid == K_WIDE
         for n in (1, 2, 3, 4, 5):
@@ -637,6 +651,19 @@ def _mk():
             ws=True)
         add(f, entry, v, forms[2], 256, 1028, 64 * bk, kid, [("sk_two_tiles",), ("sk_first_piece_second",), ("a_kmajor",), ("b_kmajor",)],
             ["sk_first_piece", "rows_past_m", "partial_col_tile"], ws=True, acc=True)
+        # the tile-order map under a cut (the cases above are a single row or column of tiles).  A small grid, all of it cut:
+        # 5 x 3 tiles of nk = 20 (fp32), 9 x 2 of nk = 16 (bf16) -- XCD runs of two lengths, a last group of one tile row walked
+        # over several tile columns, a ragged M
+        Mg, Ng, nkg = (1280 - 4, 768 - 4, 20) if kid == K_STREAMK else (2304 - 4, 512, 16)
+        add(f, entry, v, forms[2 if kid == K_STREAMK else 1], Mg, Ng, nkg * bk, kid,
+            [("sk_cut", cdiv(Mg, 256) * cdiv(Ng, 256), 0), ("nk", nkg), ("xcd_remainder",), ("ragged_group",), ("tilesM", 1), ("ragged_m",),
+             ("b_kmajor",)], ["tile_order_xcd", "tile_order_group", "sk_ticket"], ws=True)
+        # ... and one whole data-parallel round in front of the cut: 19 x 15 = 285 tiles of nk = 10, 29 of them cut (290 K steps
+        # over 256 workgroups).  (The GPU test forms the reference of a product this size as a float64 product on the device:
+        # exact for these operand ranges -- expected_image.)
+        add(f, entry, v, forms[0 if kid == K_STREAMK else 2], 4864 - 4, 3840 - 4, 10 * bk, kid,
+            [("sk_cut", 285, 1), ("nk", 10), ("xcd_remainder",), ("ragged_group",), ("ragged_m",), ("sk_two_tiles",)],
+            ["tile_order_xcd", "tile_order_group", "sk_ticket"], ws=True)
     return tuple(cases)
 
 

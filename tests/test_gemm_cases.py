@@ -54,6 +54,18 @@ def test_table_covers_the_boundaries_it_promises():
         assert {(G.K_PLANES, f) for f in ((0, 0), (0, 1), (1, 0))} <= got and {G.K_SPLIT, G.K_PL3} <= {k for k, _ in got}, K
 
 
+def test_every_kernel_walks_an_uneven_tile_list_and_a_ragged_last_group():
+    """The tile-order map is one function for all kernels, the persistent ones included: per kernel id the table holds a case
+    whose XCD runs are of two lengths (nt > 8, nt % 8 != 0) and one whose last group of tile rows is smaller than the others
+    and more than one tile column wide."""
+    for kid, ks in G.KERNELS.items():
+        geoms = [G.geometry(c) for c in G.CASES if c.kid == kid]
+        assert any(G.xcd_remainder(g) for g in geoms), ks["name"]
+        assert any(G.ragged_group(g) for g in geoms), ks["name"]
+    for kid in (G.K_STREAMK, G.K_BF2_STREAMK):      # ... and a cut behind at least one whole round of tiles
+        assert any(G.geometry(c)["cut"][1] >= 1 for c in G.CASES if c.kid == kid), G.KERNELS[kid]["name"]
+
+
 def test_every_defect_model_is_named_by_a_case():
     for defect in G.DEFECTS:
         assert any(defect in c.defects for c in G.CASES), defect
