@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 145
+#define SK_VERSION 146
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -229,6 +229,47 @@ size_t sk_wpe_workspace_bytes(int T, int C, int taps, int block_frames, int cont
 int sk_wpe(const void* Y_c64, int64_t y_chan_stride, int64_t y_row_stride, int T, int C, int taps, int delay, int iterations,
            int block_frames, int context_frames, int ref, double loading, void* X_c64, int64_t x_chan_stride, int64_t x_row_stride,
            float* mag_out, int ld_mag, void* G_out_c128, void* ws, sk_stream_t stream);
+
+/* ---------------------------------------------------------------- mask-based WPD convolutional beamforming (multi-channel recordings)
+ * Weighted power minimisation distortionless response (Nakatani & Kinoshita 2019; Nakatani et al. 2020; the steering-vector-free
+ * form of Zhang et al. 2020): dereverberation, separation and denoising solved jointly -- one filter per stream over the
+ * present frame and the delayed past of all channels, fitted under that stream's own power and constrained to pass the
+ * stream's direct image at the reference microphone.  It takes the place of sk_wpe + sk_mvdr.  No counterpart in the
+ * reference; sepkern/wpd.py states the definition and restates the arithmetic below in numpy fp64.
+ * Y: complex64 spectra, element (c, t, f) at Y[c*y_chan_stride + t*y_row_stride + f] (elements; unit bin stride, F = 257 bins,
+ * y_row_stride >= 257); mask (T, ld_mask >= S*257) float32 with stream s in columns s*257 .. (sk_stitch's or sk_cacgmm's
+ * output).  D = C*(taps + 1) <= 80; taps == 0 is a weighted MPDR beamformer.  Blocks and windows are sk_wpe's: block j holds
+ * frames [j Lb, min(T, (j+1) Lb)), its window is [max(0, j Lb - Lc), min(T, (j+1) Lb + Lc)), Lb + 2 Lc <= 4096.
+ * Per (block, bin, stream s), on the window, every operand widened to fp64 first, with m(t) = mask[t][s*257 + f],
+ * y_(t)[c] = Y[c][t][f], y_(t)[C + k C + c] = Y[c][t - delay - k][f] (0 before frame 0; the recording's frames before the
+ * window) and y(t) the first C entries of y_(t):
+ *   lambda(t) = m(t) ((sum_c |y_c(t)|^2) / C), c ascending, in the first iteration of a call without W_in; otherwise
+ *               |z(t)|^2 of z(t) = w^H y_(t), d ascending, with the previous iteration's w or W_in
+ *   lambda(t) <- max(lambda(t), floor max_t lambda);  omega(t) = 1 / lambda(t)
+ *   R = sum_t (omega y_) y_^H (upper triangle, real diagonal), t ascending;  R += (loading Re tr R / D) I
+ *   PHI = sum_t (m y) y^H, C x C, every entry summed as it stands, t ascending;  PHI~ = [PHI; 0], D x C
+ *   G = R^-1 PHI~: fp64 Cholesky factorisation R = U^H U and two triangular solves per column (sk_wpe's)
+ *   d = sum_{c < C} Re G[c][c], c ascending;  w = G[:, ref] / d
+ * `iterations` times.  The cell falls back to w = e_ref -- Z = Y[ref]'s own bits -- when in any iteration max lambda == 0,
+ * Re tr R == 0 before the loading, Re tr PHI == 0, d is not > 0 or a component of w is not finite.
+ *   Z (S, T, 257) complex64, contiguous: Z[s][t][f] = complex64(w^H y_(t)) for t in the block
+ *   W_out (nblk, S, 257, D) complex128 = the last iteration's w (may be NULL);  W_in likewise, the filter to start from (may be
+ *   NULL): one call of I iterations gives the bits of I calls of one chained through W_out -> W_in in every cell that does not
+ *   fall back.  With loading > 0 cond(R) <= D / loading + 1 however short the window.
+ * One launch on `stream`, grid (nblk, 257, S), one workgroup per (block, bin, stream) with R, PHI~, G, w and the window's
+ * weights in LDS (up to 112 KB), no host synchronisation, no atomics, no hand-off between workgroups, every sum in one fixed
+ * order: bitwise reproducible, and the bits do not depend on the strides.  Every element of Z and of W_out is written exactly
+ * once, nothing else is written, and nothing of Y outside its C x T x 257 elements or of mask outside its T x S*257 is read.
+ * All pointers are device pointers.
+ * SK_EINVAL before anything is launched: C outside 2..8, S outside 2..4, taps < 0, delay < 1, C*(taps + 1) > 80, iterations
+ * outside 1..8, T < 1, block_frames < 1, context_frames < 0, block_frames + 2 context_frames > 4096, ref outside [0, C),
+ * loading negative or NaN, floor outside (0, 1] or NaN, ld_mask < S*257, y_row_stride < 257, a NULL Y, mask or Z.  ws: sk_wpd
+ * keeps nothing in device memory between its passes; sk_wpd_workspace_bytes is 0 and ws may be NULL.  Not in it, on purpose: a
+ * noise class, an eigenvector steering estimate, online estimation. */
+size_t sk_wpd_workspace_bytes(int T, int C, int S, int taps, int block_frames, int context_frames);
+int sk_wpd(const void* Y_c64, int64_t y_chan_stride, int64_t y_row_stride, const float* mask, int ld_mask, int T, int C, int S,
+           int taps, int delay, int iterations, int block_frames, int context_frames, int ref, double loading, double floor,
+           const void* W_in_c128, void* Z_c64, void* W_out_c128, void* ws, sk_stream_t stream);
 
 /* ---------------------------------------------------------------- mask-guided cACGMM spatial clustering (multi-channel recordings)
  * Between the network and the beamformer: the masks of one microphone are re-estimated from all C channels by a complex

@@ -24,6 +24,7 @@
 // price of not keeping x for a window of up to 4096 frames.  With few unknowns most threads have no tile: at C = 1, K = 10
 // nine of a wave's 64 lanes work in pass B (profiles/wpe.txt).
 #include "sk_common.h"
+#include "wpe_solve.h"  // the tiles and the solve, shared with wpd.hip
 
 // sepkern/wpe.py states every operation with a rounding of its own: no product is fused into a sum here
 #pragma clang fp contract(off)
@@ -43,8 +44,6 @@ inline size_t wpe_lds_bytes(int C, int K, int lw) {
   const size_t D = (size_t)C * K, TC = wpe_tc(C);
   return 16 * (D * (D + 1) / 2 + D * C + (TC + K - 1) * C + 2 * TC * C) + 8 * (D + (size_t)lw + 4);
 }
-
-__device__ __forceinline__ int tri_row(int D, int a) { return a * D - a * (a - 1) / 2; }  // packed index of (a, a)
 
 template <int C, int NTHR>
 __global__ __launch_bounds__(NTHR) void wpe_kernel(const float2* __restrict__ Y, int64_t ycs, int64_t yrs, int T, int K, int delay,
@@ -69,24 +68,9 @@ __global__ __launch_bounds__(NTHR) void wpe_kernel(const float2* __restrict__ Y,
   const float2* __restrict__ Yf = Y + f;
 
   // this thread's tile: rows 4 ti .. 4 ti + 3 of y~ against columns 4 tj .. of y~ (R, tj >= ti) or of y (P)
-  int ti = 0, tj = 0;
-  bool is_p = false, has_tile = true;
-  {
-    int r = tid;
-    while (ti < NTR && r >= NTR - ti) {
-      r -= NTR - ti;
-      ++ti;
-    }
-    if (ti < NTR) {
-      tj = ti + r;
-    } else if (r < NTR * NCT) {
-      is_p = true;
-      ti = r / NCT;
-      tj = r - ti * NCT;
-    } else {
-      has_tile = false;
-    }
-  }
+  const SolveTile tile = solve_tile(tid, NTR, NTR, NCT);
+  const int ti = tile.ti, tj = tile.tj;
+  const bool is_p = tile.is_p, has_tile = tile.has;
   // offsets into [past | cur] of the tile's operands at the chunk's first frame; a frame further is C elements further.
   // y~(t)[k C + c] lies at past[(t - c0 + K - 1 - k) C + c].  Rows and columns past D (or C) repeat the last one: their
   // accumulators are never stored.
@@ -190,40 +174,12 @@ __global__ __launch_bounds__(NTHR) void wpe_kernel(const float2* __restrict__ Y,
       if (has_tile) {
         const double2* __restrict__ base = past;
         for (int r = 0; r < nfr; ++r, base += C) {
-          const double w = lam[c0 - w0 + r];
-          double pr[4], pi[4], qr[4], qi[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const double2 a = base[offa[q]], b = base[offb[q]];
-            pr[q] = a.x * w;
-            pi[q] = a.y * w;
-            qr[q] = b.x;
-            qi[q] = b.y;
-          }
-#pragma unroll
-          for (int p = 0; p < 4; ++p)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {  // a conj(b)
-              ar[p][q] += pr[p] * qr[q] + pi[p] * qi[q];
-              ai[p][q] += pi[p] * qr[q] - pr[p] * qi[q];
-            }
+          tile_frame(ar, ai, base, offa, offb, lam[c0 - w0 + r]);
         }
       }
     }
     // PG held the previous G, which pass A has finished with
-    if (has_tile) {
-#pragma unroll
-      for (int p = 0; p < 4; ++p)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int a = 4 * ti + p, b = 4 * tj + q;
-          if (is_p) {
-            if (a < D && b < C) PG[a * C + b] = make_double2(ar[p][q], ai[p][q]);
-          } else if (a <= b && b < D) {
-            Rt[tri_row(D, a) + (b - a)] = make_double2(ar[p][q], a == b ? 0.0 : ai[p][q]);
-          }
-        }
-    }
+    tile_store(tile, ar, ai, Rt, PG, D, D, C);
     __syncthreads();
     double tr = 0.0;
     for (int a = 0; a < D; ++a) tr += Rt[tri_row(D, a)].x;
@@ -235,73 +191,8 @@ __global__ __launch_bounds__(NTHR) void wpe_kernel(const float2* __restrict__ Y,
     const double load = loading * tr / (double)D;
     for (int a = tid; a < D; a += NTHR) Rt[tri_row(D, a)].x += load;
 
-    // ---- R = U^H U, right-looking: step a takes row a's products out of the rows below it.  Row a stays unscaled in LDS while
-    // its step reads it; U[a][b] = R[a][b] / U[a][a] is formed where it is used, with the rounding the stored value will have
-    for (int a = 0; a < D; ++a) {
-      __syncthreads();
-      const double2* __restrict__ rowa = Rt + tri_row(D, a);  // (a, b) at rowa[b - a]
-      const double ri = 1.0 / sqrt(rowa[0].x);
-      if (tid == 0) rinv[a] = ri;
-      const int m = D - 1 - a;
-      for (int idx = tid; idx < m * m; idx += NTHR) {
-        const int ii = idx / m, bb = idx - ii * m;
-        if (bb < ii) continue;
-        const double uar = rowa[1 + ii].x * ri, uai = rowa[1 + ii].y * ri, ubr = rowa[1 + bb].x * ri, ubi = rowa[1 + bb].y * ri;
-        double2* e = Rt + tri_row(D, a + 1 + ii) + (bb - ii);
-        double2 v = *e;
-        v.x -= uar * ubr + uai * ubi;  // conj(ua) ub; on the diagonal |ua|^2, and the imaginary part is never read
-        v.y -= uar * ubi - uai * ubr;
-        *e = v;
-      }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < D * D; idx += NTHR) {
-      const int a = idx / D, b = idx - a * D;
-      if (b > a) {
-        double2* e = Rt + tri_row(D, a) + (b - a);
-        const double ri = rinv[a];
-        *e = make_double2(e->x * ri, e->y * ri);
-      }
-    }
-    // ---- U^H Z = P
-    for (int a = 0; a < D; ++a) {
-      __syncthreads();
-      const double2* __restrict__ rowa = Rt + tri_row(D, a);
-      const double ri = rinv[a];
-      const int m = D - 1 - a;
-      for (int idx = tid; idx < m * C; idx += NTHR) {
-        const int bb = idx / C, c = idx - bb * C;
-        const double2 z0 = PG[a * C + c], u = rowa[1 + bb];
-        const double zr = z0.x * ri, zi = z0.y * ri;
-        double2* e = PG + (a + 1 + bb) * C + c;  // -= conj(u) z
-        *e = make_double2(e->x - (u.x * zr + u.y * zi), e->y - (u.x * zi - u.y * zr));
-      }
-    }
-    __syncthreads();
-    for (int idx = tid; idx < D * C; idx += NTHR) {
-      const double ri = rinv[idx / C];
-      PG[idx] = make_double2(PG[idx].x * ri, PG[idx].y * ri);
-    }
-    // ---- U G = Z, from the last row up
-    for (int a = D - 1; a >= 0; --a) {
-      __syncthreads();
-      const double ri = rinv[a];
-      for (int idx = tid; idx < a * C; idx += NTHR) {
-        const int r = idx / C, c = idx - r * C;
-        const double2 g0 = PG[a * C + c], u = Rt[tri_row(D, r) + (a - r)];
-        const double gr = g0.x * ri, gi = g0.y * ri;
-        double2* e = PG + r * C + c;  // -= u g
-        *e = make_double2(e->x - (u.x * gr - u.y * gi), e->y - (u.x * gi + u.y * gr));
-      }
-    }
-    __syncthreads();
-    int bad = 0;
-    for (int idx = tid; idx < D * C; idx += NTHR) {
-      const double ri = rinv[idx / C];
-      const double2 g = make_double2(PG[idx].x * ri, PG[idx].y * ri);
-      PG[idx] = g;
-      bad |= !(isfinite(g.x) && isfinite(g.y));
-    }
+    // ---- R = U^H U, U^H Z = P, U G = Z
+    const int bad = cholesky_solve_lds<NTHR>(Rt, PG, rinv, D, C, tid);
     if (__syncthreads_or(bad)) pass = true;
   }
 
@@ -352,11 +243,10 @@ int wpe_launch(const float2* Y, int64_t ycs, int64_t yrs, int T, int K, int dela
   const int nblk = (int)sk_cdiv(T, Lb), lw = (int)min((int64_t)T, (int64_t)Lb + 2 * (int64_t)Lc);
   const size_t lds = wpe_lds_bytes(C, K, lw);
   if (lds > (size_t)WPE_LDS_LIMIT) return sk_fail(SK_EINVAL, "sk_wpe: %zu bytes of LDS per workgroup (limit %d)", lds, WPE_LDS_LIMIT);
-  static size_t allowed = 64 * 1024;  // a kernel's dynamic LDS above 64 KB has to be allowed first
-  if (lds > allowed) {
+  // a kernel's dynamic LDS above 64 KB has to be allowed first, on the device the launch goes to: asked for per call, as no
+  // cached answer holds for another device or is safe between host threads
+  if (lds > 64 * 1024)
     SK_CHECK_HIP(hipFuncSetAttribute((const void*)wpe_kernel<C, NTHR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    allowed = lds;
-  }
   hipLaunchKernelGGL((wpe_kernel<C, NTHR>), dim3((unsigned)nblk, NBIN), dim3(NTHR), lds, st, Y, ycs, yrs, T, K, delay, iters, Lb, Lc, ref,
                      loading, lw, X, xcs, xrs, mag, ldm, G);
   SK_CHECK_LAUNCH("wpe_kernel");

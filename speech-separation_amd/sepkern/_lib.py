@@ -21,7 +21,7 @@ BUILD_FLAG_NAMES = {0x1: "TIMING_ONLY (wrong results by construction)", 0x2: "AR
 def build_flag_names(mask):
     return [n for b, n in sorted(BUILD_FLAG_NAMES.items()) if mask & b] + (["unknown 0x%x" % (mask & ~0xf)] if mask & ~0xf else [])
 
-SK_VERSION = 145
+SK_VERSION = 146
 
 _p, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 
@@ -43,6 +43,8 @@ PROTOTYPES = {
     "sk_mvdr": (_i, [_p, _i64, _i64, _p, _i, _i, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _p]),
     "sk_wpe_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "sk_wpe": (_i, [_p, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, C.c_double, _p, _i64, _i64, _p, _i, _p, _p, _p]),
+    "sk_wpd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "sk_wpd": (_i, [_p, _i64, _i64, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, _p, _p, _p, _p, _p]),
     "sk_cacgmm_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "sk_cacgmm": (_i, [_p, _i64, _i64, _p, _i, _i, _i, _i, _i, _i, _i, C.c_double, _p, _p, _i, _p, _p, _p]),
     "sk_gemm_f32": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i64, _i64, _i64, _p]),

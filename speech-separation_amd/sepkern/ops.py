@@ -780,6 +780,50 @@ def wpe(Y, taps, delay, iterations, block_frames, context_frames, loading, ref=0
     return X[:, :, :257], mag, G
 
 
+# ----------------------------------------------------------------------------- mask-based WPD convolutional beamforming
+def wpd(Y, mask, S, taps, delay, iterations, block_frames, context_frames, loading, floor, ref=0, W_in=None, want_W=False, Z=None,
+        repeat=1):
+    """One WPD convolutional beamformer per stream, block of frames and bin, steered by the masks (sk_wpd; sepkern/wpd.py
+    defines the result).  Y: (C, T, >= 257) complex64 spectra with unit bin stride (any channel and row stride: a view is read
+    where it lies), 2 <= C <= 8, C * (taps + 1) <= 80; mask: (>= T, >= S*257) float32 with unit column stride, stream s in
+    columns s*257 .. (ops.stitch's or ops.cacgmm's output); W_in: None or the (nblk, S, 257, C*(taps+1)) contiguous complex128
+    filters to start from (a W of an earlier call); Z: a contiguous complex64 (S, T, 257) buffer to write into.
+    -> (Z (S, T, 257) complex64, W (nblk, S, 257, C*(taps+1)) complex128 or None); nothing synchronises with the host."""
+    _lib.load()
+    _chk(Y, torch.complex64)
+    _chk(mask)
+    if Y.dim() != 3 or Y.shape[2] < 257 or Y.stride(2) != 1:
+        raise _lib.SepkernError("wpd: Y must be (C, T, >= 257) complex64 with unit bin stride")
+    C, T = int(Y.shape[0]), int(Y.shape[1])
+    S, K, dl, I, Lb, Lc, ref = int(S), int(taps), int(delay), int(iterations), int(block_frames), int(context_frames), int(ref)
+    if mask.dim() != 2 or mask.stride(1) != 1 or mask.shape[0] < T or mask.shape[1] < S * 257:
+        raise _lib.SepkernError("wpd: mask must be (>= T, >= S*257) float32 with unit column stride")
+    dev = Y.device
+    nblk = -(-T // Lb) if Lb > 0 else 1
+    D = max(C * (K + 1), 0)
+    shape_W = (nblk, max(S, 0), 257, D)
+    if W_in is not None:
+        _chk(W_in, torch.complex128)
+        if tuple(W_in.shape) != shape_W or not W_in.is_contiguous():
+            raise _lib.SepkernError("wpd: W_in must be (nblk, S, 257, C*(taps+1)) contiguous complex128")
+    if Z is None:
+        Z = torch.empty(max(S, 0), T, 257, dtype=torch.complex64, device=dev)
+    _chk(Z, torch.complex64)
+    if tuple(Z.shape) != (S, T, 257) or not Z.is_contiguous():
+        raise _lib.SepkernError("wpd: Z must be (S, T, 257) contiguous complex64")
+    W = torch.empty(shape_W, dtype=torch.complex128, device=dev) if want_W else None
+    # algorithmic bytes: every stream reads its window of Y twice per iteration (the weights, then the sums) and its masks
+    # once, the block is read once more and Z written; the windows overlap by the context
+    win = float(min(T, Lb + 2 * max(Lc, 0))) * nblk if Lb > 0 else 0.0
+    per = 257.0 * S * ((C * 8 * 2 + 4) * max(I, 0) * win + (C * 8 + 8) * T)
+    per += 257.0 * nblk * S * D * 16 * ((W_in is not None) + bool(want_W))
+    with _timed("wpd", repeat * per):
+        for _ in range(repeat):
+            _lib.call("sk_wpd", _ptr(Y), int(Y.stride(0)), int(Y.stride(1)), _ptr(mask), int(mask.stride(0)), T, C, S, K, dl, I, Lb,
+                      Lc, ref, float(loading), float(floor), _ptr(W_in), _ptr(Z), _ptr(W), None, _stream())
+    return Z, W
+
+
 # ----------------------------------------------------------------------------- mask-guided cACGMM spatial clustering
 def cacgmm(Y, prior, S, iterations, block_frames, context_frames, loading, B_in=None, want_B=False, out=None, repeat=1):
     """The masks re-estimated from all channels by a cACGMM whose class prior they are, per block of frames and bin (sk_cacgmm;

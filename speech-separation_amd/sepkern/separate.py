@@ -14,6 +14,7 @@ from . import cacgmm as cg
 from . import mvdr as mv
 from . import ops
 from . import stitch as st
+from . import wpd as wd
 from . import wpe as wp
 from ._lib import SepkernError
 from .packing import Packing
@@ -55,7 +56,8 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
                        mvdr_block_frames=200, mvdr_context_blocks=1, mvdr_loading=1e-3, mvdr_postmask=False, mvdr=True,
                        wpe=False, wpe_taps=10, wpe_delay=3, wpe_iterations=3, wpe_block_frames=600, wpe_context_frames=0,
                        wpe_loading=1e-3, cacgmm=False, cacgmm_iterations=5, cacgmm_block_frames=200, cacgmm_context_frames=200,
-                       cacgmm_loading=1e-3):
+                       cacgmm_loading=1e-3, wpd=False, wpd_taps=5, wpd_delay=3, wpd_iterations=2, wpd_block_frames=600,
+                       wpd_context_frames=0, wpd_loading=1e-3, wpd_floor=1e-6, wpd_postmask=False):
     """model: a uPIT SepDNN on the GPU; pcm: 1-D tensor of the recording's samples, int16 PCM or float32, at sample_rate Hz
     (moved to the model's device if it is not there; resampled on the device when sample_rate is not working_rate, the rate the
     model was trained at).  -> (wav (S, L) float32 or None, pcm16 (S, L) int16 or None) at working_rate,
@@ -81,7 +83,16 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
     block and cacgmm_context_frames on either side with the network's masks as its class prior, loading cacgmm_loading), on X
     with wpe.  It needs a (C, n) pcm and mvdr: the refined masks steer sk_mvdr and nothing else -- mvdr_postmask, the details'
     stitched and everything upstream keep the network's masks.  The details gain cacgmm_masks.  The defaults (5 iterations,
-    3.2 s blocks with 3.2 s of context on either side) are untuned.  Without cacgmm the calls and their bits are those of before."""
+    3.2 s blocks with 3.2 s of context on either side) are untuned.  Without cacgmm the calls and their bits are those of before.
+    wpd: one WPD convolutional beamformer per stream takes the beamformer's place (sk_wpd, sepkern/wpd.py: the present frame and
+    wpd_taps frames of every channel's past from wpd_delay frames back, wpd_iterations iterations, one filter per block of
+    wpd_block_frames frames estimated on the block and wpd_context_frames on either side, loading wpd_loading, power floor
+    wpd_floor).  It needs a (C, n) pcm and mvdr=False: wpd together with mvdr is refused.  The stitched masks steer it, or
+    sk_cacgmm's with cacgmm, which then needs mvdr or wpd.  With wpe the network and sk_cacgmm see X as above, but sk_wpd runs on
+    the untouched Y: it is the joint solution on the observation.  Its spectra are inverted -- multiplied by the stitched masks
+    once more with wpd_postmask.  The details gain Y, Z and wpd_weights.  The defaults (5 taps, a delay of 3, 2 iterations,
+    9.6 s blocks, a floor of 1e-6) are the literature's; they are not tuned.  Without wpd the calls and their bits are those of
+    before."""
     if not hasattr(model, "forward_packed"):
         raise SepkernError("separate_recording needs a model with forward_packed (the uPIT arch)")
     st.check_geometry(1, window_frames, hop_frames)
@@ -91,9 +102,16 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
     pcm = torch.as_tensor(pcm)
     if pcm.dim() not in (1, 2) or pcm.dtype not in (torch.int16, torch.float32):
         raise SepkernError("separate_recording: pcm must be a 1-D, or for an array a (C, n), int16 or float32 tensor")
+    if wpd:
+        if mvdr:
+            raise ValueError("separate_recording: wpd takes the beamformer's place; pass mvdr=False with it")
+        if pcm.dim() != 2:
+            raise ValueError("separate_recording: wpd needs a (C, n) pcm")
+        wd.check_arguments(int(pcm.shape[0]), int(model.num_spk), 1, int(wpd_taps), int(wpd_delay), int(wpd_iterations),
+                           int(wpd_block_frames), int(wpd_context_frames), int(ref_channel), float(wpd_loading), float(wpd_floor))
     if cacgmm:
-        if pcm.dim() != 2 or not mvdr:
-            raise ValueError("separate_recording: cacgmm needs a (C, n) pcm and mvdr")
+        if pcm.dim() != 2 or not (mvdr or wpd):
+            raise ValueError("separate_recording: cacgmm needs a (C, n) pcm and mvdr or wpd")
         cg.check_arguments(int(pcm.shape[0]), int(model.num_spk), 1, int(cacgmm_iterations), int(cacgmm_block_frames),
                            int(cacgmm_context_frames), float(cacgmm_loading))
     pcm = pcm.to(dev, non_blocking=True)
@@ -105,7 +123,7 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
         C, n = int(pcm.shape[0]), int(pcm.shape[1])
         if mvdr:
             mv.check_arguments(C, int(model.num_spk), 1, int(mvdr_block_frames), int(mvdr_context_blocks), int(ref_channel), float(mvdr_loading))
-        elif not wpe:
+        elif not (wpe or wpd):
             raise ValueError("separate_recording: a (C, n) pcm needs mvdr or wpe")
         flat = pcm.contiguous().view(-1)
         if int(sample_rate) != int(working_rate):           # all channels in one call
@@ -150,7 +168,17 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
     details = dict(masks=windows, stitched=stitched, perms=perms, cost=cost, mag=mag, mixc=mixc)
     if X is not None:
         details.update(X=X, Y=Yw)
-    if Y is None or not mvdr:
+    if wpd:
+        steer = stitched
+        if cacgmm:
+            steer, _ = ops.cacgmm(Y if X is None else X, stitched, S, cacgmm_iterations, cacgmm_block_frames, cacgmm_context_frames,
+                                  cacgmm_loading)
+            details.update(cacgmm_masks=steer)
+        Z, weights = ops.wpd(Y, steer, S, wpd_taps, wpd_delay, wpd_iterations, wpd_block_frames, wpd_context_frames, wpd_loading,
+                             wpd_floor, ref=ref_channel, want_W=True)
+        wav, pcm16 = ops.mask_istft_streams(Z, stitched if wpd_postmask else None, S, want_pcm=want_pcm, want_float=want_float)
+        details.update(Y=Y, Z=Z, wpd_weights=weights)
+    elif Y is None or not mvdr:
         wav, pcm16 = ops.mask_istft_frames(mixc, stitched, S, want_pcm=want_pcm, want_float=want_float)
     else:
         steer = stitched

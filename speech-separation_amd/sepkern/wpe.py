@@ -45,7 +45,8 @@ complex product being its four real products and two sums, and every sum has one
 kernel performs the same operations in the same order.
 
 Out of the definition, on purpose: a power estimate smoothed over neighbouring frames (the "PSD context"), recursive / online
-WPE, joint WPE and beamforming (WPD), and any tuning of taps, delay and iterations: no array data is at hand.
+WPE, joint WPE and beamforming (WPD), and any tuning of taps, delay and iterations: no array data is at hand.  The joint
+solution is a definition of its own, sepkern/wpd.py (sk_wpd), built on this file's windows, sums and solve.
 """
 import numpy as np
 
@@ -103,14 +104,17 @@ def stacked_past(Y, t0, t1, taps, delay):
     return out
 
 
-def covariances(yt, y, w):
+def covariances(yt, y, w, pt=None, pw=None):
     """R (F, D, D), P (F, D, C): the weighted sums over the window, t ascending; yt (L, F, D), y (L, F, C), w (L, F).  Real
-    arithmetic, one rounding per product and per sum: (w y~_a) conj(b) = (pr qr + pi qi) + i (pi qr - pr qi)."""
+    arithmetic, one rounding per product and per sum: (w y~_a) conj(b) = (pr qr + pi qi) + i (pi qr - pr qi).
+    With pt (L, F, Dp) and pw (L, F) the second sum is P = sum_t (pw(t) pt(t)) y(t)^H, (F, Dp, C), instead (sepkern/wpd.py)."""
     L, D, C = yt.shape[0], yt.shape[2], y.shape[2]
     tf = lambda a: np.ascontiguousarray(np.transpose(a, (0, 2, 1)))                # bins innermost: (L, D, F)
     ytr, yti, yr, yi = tf(yt.real), tf(yt.imag), tf(y.real), tf(y.imag)
+    ptr, pti = (ytr, yti) if pt is None else (tf(pt.real), tf(pt.imag))
+    pw = w if pw is None else pw
     Rr, Ri, t1, t2 = (np.zeros((D, D, F)) for _ in range(4))
-    Pr, Pi, u1, u2 = (np.zeros((D, C, F)) for _ in range(4))
+    Pr, Pi, u1, u2 = (np.zeros((ptr.shape[1], C, F)) for _ in range(4))
 
     def add(pr, pi, qr, qi, re, im, a, b):
         np.multiply(pr, qr, out=a)
@@ -125,6 +129,8 @@ def covariances(yt, y, w):
     for t in range(L):
         pr, pi = (ytr[t] * w[t])[:, None, :], (yti[t] * w[t])[:, None, :]
         add(pr, pi, ytr[t][None], yti[t][None], Rr, Ri, t1, t2)
+        if pt is not None:
+            pr, pi = (ptr[t] * pw[t])[:, None, :], (pti[t] * pw[t])[:, None, :]
         add(pr, pi, yr[t][None], yi[t][None], Pr, Pi, u1, u2)
     Rr, Ri, Pr, Pi = (np.transpose(a, (2, 0, 1)) for a in (Rr, Ri, Pr, Pi))
     up = np.triu(np.ones((D, D), dtype=bool), 1)

@@ -21,6 +21,10 @@ are applied to --ref-channel.
 
 --cacgmm (with --mvdr, multi-channel recordings only) re-estimates the stitched masks from all channels before they steer the
 beamformers (sk_cacgmm, sepkern/cacgmm.py: a cACGMM spatial mixture model with the network's masks as its class prior).
+
+--wpd (instead of --mvdr, multi-channel recordings only) beamforms with one WPD convolutional beamformer per stream (sk_wpd,
+sepkern/wpd.py: dereverberation, separation and denoising in one filter over the present frame and the channels' past).  With
+--wpe the network still sees the dereverberated reference channel, and the WPD beamformers the recording as it is.
 """
 import argparse
 import concurrent.futures
@@ -43,7 +47,7 @@ def get_args(argv=None):
   parser.add_argument("arch_file", metavar="arch-file", type=str, help="DNN architecture file (uPIT)")
   parser.add_argument("gpu_id", metavar="gpu-id", type=int, help="GPU ID")
   parser.add_argument("model", type=str, help="Trained model to use")
-  parser.add_argument("wav_scp", metavar="wav-scp", type=str, help="lines of `<ID> <path to a mono 16-bit wav file>` (with --mvdr or --wpe: any number of channels)")
+  parser.add_argument("wav_scp", metavar="wav-scp", type=str, help="lines of `<ID> <path to a mono 16-bit wav file>` (with --mvdr, --wpd or --wpe: any number of channels)")
   parser.add_argument("out_dir", metavar="out-dir", type=str, help="Output directory: <out-dir>/s<k>/<ID>.wav")
   parser.add_argument("--model-config", type=str, help="Config file for DNN", default="")
   parser.add_argument("--window-frames", type=int, default=400, help="window length in frames (the training chunk length)")
@@ -65,22 +69,34 @@ def get_args(argv=None):
   parser.add_argument("--wpe-block-frames", type=int, default=600, help="frames per block of prediction filters")
   parser.add_argument("--wpe-context-frames", type=int, default=0, help="frames on either side of a block its filters are estimated on as well")
   parser.add_argument("--wpe-loading", type=float, default=1e-3, help="diagonal loading of the covariance matrix, relative to its mean diagonal")
-  parser.add_argument("--cacgmm", action="store_true", help="re-estimate the masks from all channels by a mask-guided cACGMM before they steer the beamformers (needs --mvdr)")
+  parser.add_argument("--cacgmm", action="store_true", help="re-estimate the masks from all channels by a mask-guided cACGMM before they steer the beamformers (needs --mvdr or --wpd)")
   parser.add_argument("--cacgmm-iterations", type=int, default=5, help="EM iterations of the spatial model (0..16)")
   parser.add_argument("--cacgmm-block-frames", type=int, default=200, help="frames per block of the spatial model")
   parser.add_argument("--cacgmm-context-frames", type=int, default=200, help="frames on either side of a block its model is fitted on as well")
   parser.add_argument("--cacgmm-loading", type=float, default=1e-3, help="diagonal loading of the classes' matrices, relative to their mean diagonal")
+  parser.add_argument("--wpd", action="store_true", help="beamform multi-channel recordings with one WPD convolutional beamformer per stream instead of --mvdr (2..8 channels)")
+  parser.add_argument("--wpd-taps", type=int, default=5, help="frames of every channel's past the beamformers use besides the present one (channels * (taps + 1) <= 80)")
+  parser.add_argument("--wpd-delay", type=int, default=3, help="frames between the present and the newest past frame the beamformers use")
+  parser.add_argument("--wpd-iterations", type=int, default=2, help="re-estimations of the streams' powers (1..8)")
+  parser.add_argument("--wpd-block-frames", type=int, default=600, help="frames per block of beamformer filters")
+  parser.add_argument("--wpd-context-frames", type=int, default=0, help="frames on either side of a block its filters are estimated on as well")
+  parser.add_argument("--wpd-loading", type=float, default=1e-3, help="diagonal loading of the covariance matrix, relative to its mean diagonal")
+  parser.add_argument("--wpd-floor", type=float, default=1e-6, help="floor of a stream's power, relative to its largest in the window, in (0, 1]")
+  parser.add_argument("--wpd-postmask", action="store_true", help="multiply the beamformed spectra by the masks")
   parser.add_argument("--writers", type=int, default=8, help="threads that read the wav inputs and write the wav outputs")
   return parser.parse_args(argv)
 
 
 def main(argv=None):
   args = get_args(argv)
-  if args.mvdr_channel_scps and not (args.mvdr or args.wpe):
+  if args.wpd and args.mvdr:
+    print("separate_wav: --wpd takes the place of --mvdr; give one of them", file=sys.stderr)
+    return 1
+  if args.mvdr_channel_scps and not (args.mvdr or args.wpe or args.wpd):
     print("separate_wav: --mvdr-channel-scps needs --mvdr", file=sys.stderr)
     return 1
-  if args.cacgmm and not args.mvdr:
-    print("separate_wav: --cacgmm needs --mvdr", file=sys.stderr)
+  if args.cacgmm and not (args.mvdr or args.wpd):
+    print("separate_wav: --cacgmm needs --mvdr or --wpd", file=sys.stderr)
     return 1
   import eval_qsub
   m = eval_qsub.load_arch(args.arch_file)
@@ -126,7 +142,7 @@ def main(argv=None):
     rates, chans = [], []
     for path in paths:
       fs, x = scipy.io.wavfile.read(path)
-      if x.dtype.name != 'int16' or x.ndim > 2 or (x.ndim == 2 and not (args.mvdr or args.wpe)):
+      if x.dtype.name != 'int16' or x.ndim > 2 or (x.ndim == 2 and not (args.mvdr or args.wpe or args.wpd)):
         raise ValueError("%s: only mono 16-bit PCM wav is supported" % path)
       rates.append(int(fs))
       chans += [x] if x.ndim == 1 else [x[:, c] for c in range(x.shape[1])]
@@ -151,12 +167,15 @@ def main(argv=None):
       _, pcm16 = separate_recording(model, pcm, rate, args.window_frames, args.hop_frames, args.batch_windows,
                                     working_rate=args.sample_rate, want_float=False, want_pcm=True, ref_channel=args.ref_channel,
                                     mvdr_block_frames=args.mvdr_block_frames, mvdr_context_blocks=args.mvdr_context_blocks,
-                                    mvdr_loading=args.mvdr_loading, mvdr_postmask=args.mvdr_postmask, mvdr=args.mvdr or not args.wpe,
+                                    mvdr_loading=args.mvdr_loading, mvdr_postmask=args.mvdr_postmask, mvdr=args.mvdr or not (args.wpe or args.wpd),
                                     wpe=args.wpe, wpe_taps=args.wpe_taps, wpe_delay=args.wpe_delay, wpe_iterations=args.wpe_iterations,
                                     wpe_block_frames=args.wpe_block_frames, wpe_context_frames=args.wpe_context_frames,
                                     wpe_loading=args.wpe_loading, cacgmm=args.cacgmm, cacgmm_iterations=args.cacgmm_iterations,
                                     cacgmm_block_frames=args.cacgmm_block_frames, cacgmm_context_frames=args.cacgmm_context_frames,
-                                    cacgmm_loading=args.cacgmm_loading)
+                                    cacgmm_loading=args.cacgmm_loading, wpd=args.wpd, wpd_taps=args.wpd_taps, wpd_delay=args.wpd_delay,
+                                    wpd_iterations=args.wpd_iterations, wpd_block_frames=args.wpd_block_frames,
+                                    wpd_context_frames=args.wpd_context_frames, wpd_loading=args.wpd_loading,
+                                    wpd_floor=args.wpd_floor, wpd_postmask=args.wpd_postmask)
       out_h = torch.empty(pcm16.shape, dtype=torch.int16).pin_memory()
       out_h.copy_(pcm16, non_blocking=True)
       torch.cuda.synchronize()
