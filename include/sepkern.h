@@ -514,7 +514,7 @@ int sk_hprev_rows(const float* y, int ldy, const float* h0, const int32_t* offs,
  * in its two low mantissa bits, producers publish without drain / barrier / flag, consumers hold back, pull, check every word
  * and pull again what was not complete; the next step's product runs on the tagged words (<= 3 ulp = 3.6e-7 relative),
  * everything stored (y, gates, cs, states) is exact.  The r03 default; still the engine's choice for H > 896;
- * SK_LSTM_XL8 (with SK_LSTM_BF16, both directions, persistent launches, 608 < H <= 896, B <= 32, a device of 8 XCDs x 32 CUs; ignored otherwise;
+ * SK_LSTM_XL8 (with SK_LSTM_BF16, both directions, persistent launches, 640 < H <= 896, B <= 32, a device of 8 XCDs x 32 CUs; ignored otherwise;
  * r06): XCD-LOCAL streams of 8 rows -- every (direction, 8-row batch group) stream is 28 workgroups of 32 hidden units on ONE
  * XCD, h_t published with plain stores and a plain flag (within an XCD the L2 is the coherence point; polls and pulls stay sc1),
  * 14 KB instead of 28 KB pulled per workgroup and step.  Same arithmetic bit for bit.  A workgroup joins the stream of the XCD it

@@ -1798,7 +1798,7 @@ Plan plan_launch(const Mode& m, int B, int H) {
   const int g = groups_per_wg(p.L.KS, p.L.NBG, m.gmin);
   p.fits = g > 0;
   p.persistent = m.kind == SK_LSTM_PERSISTENT || (m.kind == SK_LSTM_AUTO && p.fits);
-  // XCD-local streams of 8 rows (SK_LSTM_XL8, bf16) where the shape allows them: the 56-chunk instantiation (608 < H <= 896: 28
+  // XCD-local streams of 8 rows (SK_LSTM_XL8, bf16) where the shape allows them: the 56-chunk instantiation (640 < H <= 896: 28
   // workgroups of 32 units per stream), at most 8 streams (B <= 32), a device of 8 XCDs x 32 CUs, a persistent launch; anything
   // else runs the ordinary form
   p.xl8 = m.xl8 && m.bf && p.L.KS == 56 && B <= 32 && m.gmin <= 1 && sk_num_cus() >= 256 && p.persistent;
@@ -1821,7 +1821,7 @@ FwdKernel fwd_kernel(const Plan& p, const Mode& m, bool packed) {
       {SK_PAIR(20, true, false), SK_PAIR(40, true, false), SK_PAIR(56, true, false), SK_PAIR(64, true, false)}};
   static const FwdKernel split3[3][2] = {SK_PAIR(20, false, true), SK_PAIR(40, false, true), SK_PAIR(56, false, true)};
 #undef SK_PAIR
-  static const FwdKernel xl8[2] = {lstm_fwd_xl8_kernel<56, false>, lstm_fwd_xl8_kernel<56, true>};  // bf16, 608 < H <= 896
+  static const FwdKernel xl8[2] = {lstm_fwd_xl8_kernel<56, false>, lstm_fwd_xl8_kernel<56, true>};  // bf16, 640 < H <= 896
   const int k = ks_index(p.L.KS);
   return p.xl8 ? xl8[packed] : m.s3 ? split3[k][packed] : plain[m.bf][k][packed];
 }

@@ -1512,7 +1512,7 @@ def lstm_variant_bits(half=False, blockmap=0, poll1=False, repflags=False, sprea
     choice, 31 = none); tagged (forward, fp32): the exchanged h carries the step's epoch in its two low mantissa bits and
     nothing else is signalled (mode bit 29); split3 (forward, fp32): the product h W_hh^T by the exact three-way bf16 split
     of both operands on the bf16 matrix pipe (mode bit 28; flags hand-off, the tagged one does not combine with it); xl8 (forward,
-    bf16, 608 < H <= 896, B <= 32, persistent launches; other shapes run the ordinary form): XCD-local streams of 8 rows x 28
+    bf16, 640 < H <= 896, B <= 32, persistent launches; other shapes run the ordinary form): XCD-local streams of 8 rows x 28
     workgroups of 32 units with a plain-store hand-off (mode bit 30) -- the same arithmetic bit for bit."""
     if half:      # (the first field of SEPKERN_LSTM_FWD / _BWD keeps its place so that recorded switch strings stay readable)
         raise _lib.SepkernError("the 8-unit / 256-thread forward recurrence (field `half`, mode bit 17) was retired in r05: "

@@ -961,7 +961,7 @@ def test_lstm_geometry_and_protocol_variants_are_bitwise_identical(ops, layout, 
                                               (9, 20, 704, [9] * 7 + [4] * 13, 31), (33, 8, 896, [33] * 3 + [20] * 5, 0), (7, 32, 600, [7] * 32, 0),
                                               (6, 40, 896, [6] * 40, 0)])
 def test_lstm_forward_bf16_xcd_local_streams_of_eight_rows(ops, layout, T, B, H, lens, delay):
-    """Mode bit 30 (bf16 forward, 608 < H <= 896, B <= 32, r06): every (direction, 8-row batch group) stream is 28 workgroups of
+    """Mode bit 30 (bf16 forward, 640 < H <= 896, B <= 32, r06): every (direction, 8-row batch group) stream is 28 workgroups of
     32 units on ONE XCD, h_t published with plain stores and a plain flag (the XCD's L2 is the coherence point; sc1 polls and
     pulls), 14 KB pulled per step.  Who computes what and how it is signalled changes, the arithmetic does not: every output equals
     the ordinary bf16 form's bit for bit, run after run, with ragged lengths, B not a multiple of 8, hidden sizes that leave part

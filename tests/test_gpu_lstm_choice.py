@@ -51,7 +51,7 @@ def _cases():
     for H in (256, 600, 608, 612, 896, 900, 1024):          # bf16, ordinary form
         c.append(("fwd", H, 32, 0, 0, "bf16", True, False, False))
         c.append(("bwd", H, 32, 0, 0, "bf16", True, False, True))
-    for H in (608, 612, 896, 900):                          # bf16 with the XCD-local form asked for: taken for 608 < H <= 896, B <= 32
+    for H in (608, 612, 896, 900):                          # bf16 with the XCD-local form asked for: taken for 640 < H <= 896, B <= 32
         for B in (8, 32, 33):
             c.append(("fwd", H, B, 0, 0, "bf16+xl8", B != 8, False, False))
             c.append(("bwd", H, B, 0, 0, "bf16+xl8", B != 8, False, True))
