@@ -293,16 +293,6 @@ __global__ __launch_bounds__(CG_NTHR) void cacgmm_kernel(const float2* __restric
     }
 }
 
-template <int C>
-int cacgmm_launch(const float2* Y, int64_t ycs, int64_t yrs, const float* prior, int ldp, int T, int K, int iters, int Lb, int Lc,
-                  double loading, const double2* Bin, float* out, int ldo, double2* Bout, hipStream_t st) {
-  const int nblk = (int)sk_cdiv(T, Lb);
-  hipLaunchKernelGGL((cacgmm_kernel<C>), dim3((unsigned)nblk, NBIN), dim3(CG_NTHR), 0, st, Y, ycs, yrs, prior, ldp, T, K, iters, Lb, Lc,
-                     loading, Bin, out, ldo, Bout);
-  SK_CHECK_LAUNCH("cacgmm_kernel");
-  return SK_OK;
-}
-
 }  // namespace
 
 // sk_cacgmm keeps everything between its passes in LDS
@@ -313,31 +303,24 @@ extern "C" int sk_cacgmm(const void* Y_c64, int64_t y_chan_stride, int64_t y_row
                          float* mask_out, int ld_out, void* B_out_c128, void* ws, sk_stream_t stream) {
   SK_CHECK_ARG(C >= CG_MINC && C <= CG_MAXC, "sk_cacgmm: C = %d channels outside %d..%d", C, CG_MINC, CG_MAXC);
   SK_CHECK_ARG(S >= CG_MINS && S <= CG_MAXS, "sk_cacgmm: S = %d streams outside %d..%d", S, CG_MINS, CG_MAXS);
-  SK_CHECK_ARG(T >= 1, "sk_cacgmm: T = %d frames, at least 1 expected", T);
+  SK_CHECK_FRAMES("sk_cacgmm", T);
   SK_CHECK_ARG(iterations >= 0 && iterations <= CG_MAXIT, "sk_cacgmm: iterations = %d outside 0..%d", iterations, CG_MAXIT);
-  SK_CHECK_ARG(block_frames >= 1, "sk_cacgmm: block_frames = %d, at least 1 expected", block_frames);
-  SK_CHECK_ARG(context_frames >= 0, "sk_cacgmm: context_frames = %d is negative", context_frames);
-  SK_CHECK_ARG((int64_t)block_frames + 2 * (int64_t)context_frames <= CG_MAXWIN,
-               "sk_cacgmm: a window of block_frames + 2 context_frames = %lld frames, at most %d",
-               (long long)block_frames + 2 * (long long)context_frames, CG_MAXWIN);
-  SK_CHECK_ARG(loading >= 0.0, "sk_cacgmm: loading = %g is negative or NaN", loading);
+  SK_CHECK_BLOCK_FRAMES("sk_cacgmm", block_frames);
+  SK_CHECK_WINDOW("sk_cacgmm", block_frames, context_frames, CG_MAXWIN);
+  SK_CHECK_LOADING("sk_cacgmm", loading);
   SK_CHECK_ARG(ld_prior >= S * NBIN, "sk_cacgmm: ld_prior = %d below S*257 = %d", ld_prior, S * NBIN);
   SK_CHECK_ARG(ld_out >= S * NBIN, "sk_cacgmm: ld_out = %d below S*257 = %d", ld_out, S * NBIN);
-  SK_CHECK_ARG(y_row_stride >= NBIN, "sk_cacgmm: y_row_stride = %lld below 257", (long long)y_row_stride);
+  SK_CHECK_Y_ROW_STRIDE("sk_cacgmm", y_row_stride);
   SK_CHECK_ARG(Y_c64 && prior && mask_out, "sk_cacgmm: null pointer (Y, prior or mask_out)");
   const float2* Y = (const float2*)Y_c64;
   const double2* Bi = (const double2*)B_in_c128;
   double2* Bo = (double2*)B_out_c128;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t ycs = y_chan_stride, yrs = y_row_stride;
-  const int I = iterations, Lb = block_frames, Lc = context_frames;
-  switch (C) {
-    case 2: return cacgmm_launch<2>(Y, ycs, yrs, prior, ld_prior, T, S, I, Lb, Lc, loading, Bi, mask_out, ld_out, Bo, st);
-    case 3: return cacgmm_launch<3>(Y, ycs, yrs, prior, ld_prior, T, S, I, Lb, Lc, loading, Bi, mask_out, ld_out, Bo, st);
-    case 4: return cacgmm_launch<4>(Y, ycs, yrs, prior, ld_prior, T, S, I, Lb, Lc, loading, Bi, mask_out, ld_out, Bo, st);
-    case 5: return cacgmm_launch<5>(Y, ycs, yrs, prior, ld_prior, T, S, I, Lb, Lc, loading, Bi, mask_out, ld_out, Bo, st);
-    case 6: return cacgmm_launch<6>(Y, ycs, yrs, prior, ld_prior, T, S, I, Lb, Lc, loading, Bi, mask_out, ld_out, Bo, st);
-    case 7: return cacgmm_launch<7>(Y, ycs, yrs, prior, ld_prior, T, S, I, Lb, Lc, loading, Bi, mask_out, ld_out, Bo, st);
-    default: return cacgmm_launch<8>(Y, ycs, yrs, prior, ld_prior, T, S, I, Lb, Lc, loading, Bi, mask_out, ld_out, Bo, st);
-  }
+  const int nblk = (int)sk_cdiv(T, block_frames);
+  return sk_dispatch_int<CG_MINC, CG_MAXC>(C, [&](auto c) {
+    hipLaunchKernelGGL((cacgmm_kernel<decltype(c)::value>), dim3((unsigned)nblk, NBIN), dim3(CG_NTHR), 0, (hipStream_t)stream, Y,
+                       y_chan_stride, y_row_stride, prior, ld_prior, T, S, iterations, block_frames, context_frames, loading, Bi, mask_out,
+                       ld_out, Bo);
+    SK_CHECK_LAUNCH("cacgmm_kernel");
+    return SK_OK;
+  });
 }

@@ -329,16 +329,6 @@ int mvdr_launch(const float2* Y, int64_t ycs, int64_t yrs, const float* mask, in
   return SK_OK;
 }
 
-template <int C>
-int mvdr_launch_s(int S, const float2* Y, int64_t ycs, int64_t yrs, const float* mask, int ld, int T, int Lb, int R, int ref,
-                  double loading, float2* weights, float2* Z, double2* scm, double* part, hipStream_t st) {
-  switch (S) {
-    case 2: return mvdr_launch<C, 2>(Y, ycs, yrs, mask, ld, T, Lb, R, ref, loading, weights, Z, scm, part, st);
-    case 3: return mvdr_launch<C, 3>(Y, ycs, yrs, mask, ld, T, Lb, R, ref, loading, weights, Z, scm, part, st);
-    default: return mvdr_launch<C, 4>(Y, ycs, yrs, mask, ld, T, Lb, R, ref, loading, weights, Z, scm, part, st);
-  }
-}
-
 }  // namespace
 
 // [block statistics (nblk, S, C (C + 1) / 2, 2, 257) fp64]
@@ -352,30 +342,22 @@ extern "C" int sk_mvdr(const void* Y_c64, int64_t y_chan_stride, int64_t y_row_s
                        void* scm_out_c128, void* ws, sk_stream_t stream) {
   SK_CHECK_ARG(C >= MINC && C <= MAXC, "sk_mvdr: C = %d channels outside %d..%d", C, MINC, MAXC);
   SK_CHECK_ARG(S >= MINS && S <= SK_MAXS, "sk_mvdr: S = %d streams outside %d..%d", S, MINS, SK_MAXS);
-  SK_CHECK_ARG(T >= 1, "sk_mvdr: T = %d frames, at least 1 expected", T);
-  SK_CHECK_ARG(block_frames >= 1, "sk_mvdr: block_frames = %d, at least 1 expected", block_frames);
+  SK_CHECK_FRAMES("sk_mvdr", T);
+  SK_CHECK_BLOCK_FRAMES("sk_mvdr", block_frames);
   SK_CHECK_ARG(context_blocks >= 0, "sk_mvdr: context_blocks = %d is negative", context_blocks);
-  SK_CHECK_ARG(ref >= 0 && ref < C, "sk_mvdr: ref = %d outside [0, %d)", ref, C);
-  SK_CHECK_ARG(loading >= 0.0, "sk_mvdr: loading = %g is negative or NaN", loading);
-  SK_CHECK_ARG(ld_mask >= S * NBIN, "sk_mvdr: ld_mask = %d below S * 257 = %d", ld_mask, S * NBIN);
-  SK_CHECK_ARG(y_row_stride >= NBIN, "sk_mvdr: y_row_stride = %lld below 257", (long long)y_row_stride);
+  SK_CHECK_REF("sk_mvdr", ref, C);
+  SK_CHECK_LOADING("sk_mvdr", loading);
+  SK_CHECK_LD_MASK("sk_mvdr", ld_mask, S);
+  SK_CHECK_Y_ROW_STRIDE("sk_mvdr", y_row_stride);
   SK_CHECK_ARG(mvdr_shape_ok(T, C, S, block_frames), "sk_mvdr: T = %d frames in blocks of %d make too many workgroups", T, block_frames);
   SK_CHECK_ARG(Y_c64 && mask && weights_c64 && Z_c64, "sk_mvdr: null pointer (Y, mask, weights or Z)");
   SK_CHECK_ARG(ws, "sk_mvdr: ws is NULL, %zu bytes of workspace expected", sk_mvdr_workspace_bytes(T, C, S, block_frames));
   const float2* Y = (const float2*)Y_c64;
   float2 *W = (float2*)weights_c64, *Z = (float2*)Z_c64;
-  double2* scm = (double2*)scm_out_c128;
-  double* part = (double*)ws;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t ycs = y_chan_stride, yrs = y_row_stride;
-  const int Lb = block_frames, R = context_blocks;
-  switch (C) {
-    case 2: return mvdr_launch_s<2>(S, Y, ycs, yrs, mask, ld_mask, T, Lb, R, ref, loading, W, Z, scm, part, st);
-    case 3: return mvdr_launch_s<3>(S, Y, ycs, yrs, mask, ld_mask, T, Lb, R, ref, loading, W, Z, scm, part, st);
-    case 4: return mvdr_launch_s<4>(S, Y, ycs, yrs, mask, ld_mask, T, Lb, R, ref, loading, W, Z, scm, part, st);
-    case 5: return mvdr_launch_s<5>(S, Y, ycs, yrs, mask, ld_mask, T, Lb, R, ref, loading, W, Z, scm, part, st);
-    case 6: return mvdr_launch_s<6>(S, Y, ycs, yrs, mask, ld_mask, T, Lb, R, ref, loading, W, Z, scm, part, st);
-    case 7: return mvdr_launch_s<7>(S, Y, ycs, yrs, mask, ld_mask, T, Lb, R, ref, loading, W, Z, scm, part, st);
-    default: return mvdr_launch_s<8>(S, Y, ycs, yrs, mask, ld_mask, T, Lb, R, ref, loading, W, Z, scm, part, st);
-  }
+  return sk_dispatch_int<MINC, MAXC>(C, [&](auto c) {
+    return sk_dispatch_int<MINS, SK_MAXS>(S, [&](auto s) {
+      return mvdr_launch<decltype(c)::value, decltype(s)::value>(Y, y_chan_stride, y_row_stride, mask, ld_mask, T, block_frames, context_blocks,
+                                                                 ref, loading, W, Z, (double2*)scm_out_c128, (double*)ws, (hipStream_t)stream);
+    });
+  });
 }

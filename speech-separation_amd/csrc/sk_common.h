@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <type_traits>
 
 #include "../../include/sepkern.h"
 
@@ -37,6 +38,45 @@ int sk_num_cus();
 
 static inline int64_t sk_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t sk_align(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// ---- what the array kernels (mvdr, wpe, wpd, cacgmm) share on the host ------------------------------------------------------
+// A runtime n in LO..HI as a compile-time constant: f(std::integral_constant<int, n>{}).  The caller has checked the range; a
+// value outside it takes HI.
+template <int LO, int HI, class F>
+inline int sk_dispatch_int(int n, F&& f) {
+  if constexpr (LO == HI) {
+    return f(std::integral_constant<int, HI>{});
+  } else {
+    return n == LO ? f(std::integral_constant<int, LO>{}) : sk_dispatch_int<LO + 1, HI>(n, f);
+  }
+}
+
+// One launch with `lds` bytes of dynamic LDS, refused above `limit`.  A kernel's dynamic LDS above 64 KB has to be allowed
+// first, on the device the launch goes to: asked for per call, as no cached answer holds for another device or is safe between
+// host threads.  `entry` is the C entry point's name, for the message.
+template <class... P, class... A>
+inline int sk_launch_lds(const char* entry, const char* what, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, int limit,
+                         hipStream_t st, A... args) {
+  if (lds > (size_t)limit) return sk_fail(SK_EINVAL, "%s: %zu bytes of LDS per workgroup (limit %d)", entry, lds, limit);
+  if (lds > 64 * 1024) SK_CHECK_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+  SK_CHECK_LAUNCH(what);
+  return SK_OK;
+}
+
+// The checks of the block arguments, one line each so that an entry point keeps its own order; `who` is its name, a literal.
+#define SK_CHECK_FRAMES(who, T) SK_CHECK_ARG((T) >= 1, who ": T = %d frames, at least 1 expected", T)
+#define SK_CHECK_BLOCK_FRAMES(who, Lb) SK_CHECK_ARG((Lb) >= 1, who ": block_frames = %d, at least 1 expected", Lb)
+#define SK_CHECK_WINDOW(who, Lb, Lc, maxwin)                                                                            \
+  do {                                                                                                                  \
+    SK_CHECK_ARG((Lc) >= 0, who ": context_frames = %d is negative", Lc);                                               \
+    SK_CHECK_ARG((int64_t)(Lb) + 2 * (int64_t)(Lc) <= (maxwin),                                                         \
+                 who ": a window of block_frames + 2 context_frames = %lld frames, at most %d", (long long)(Lb) + 2 * (long long)(Lc), maxwin); \
+  } while (0)
+#define SK_CHECK_REF(who, ref, C) SK_CHECK_ARG((ref) >= 0 && (ref) < (C), who ": ref = %d outside [0, %d)", ref, C)
+#define SK_CHECK_LOADING(who, loading) SK_CHECK_ARG((loading) >= 0.0, who ": loading = %g is negative or NaN", loading)
+#define SK_CHECK_Y_ROW_STRIDE(who, yrs) SK_CHECK_ARG((yrs) >= 257, who ": y_row_stride = %lld below 257", (long long)(yrs))
+#define SK_CHECK_LD_MASK(who, ld, S) SK_CHECK_ARG((ld) >= (S) * 257, who ": ld_mask = %d below S * 257 = %d", ld, (S) * 257)
 
 // ---- device helpers ------------------------------------------------------------------------
 __device__ __forceinline__ float sk_wave_sum(float v) {

@@ -250,31 +250,6 @@ inline int wpd_tiles(int C, int K) {
   return ntr * (ntr + 1) / 2 + nct * nct;
 }
 
-template <int C, int NTHR>
-int wpd_launch(const float2* Y, int64_t ycs, int64_t yrs, const float* mask, int ldm, int T, int S, int K, int delay, int iters, int Lb,
-               int Lc, int ref, double loading, double floor, const double2* Win, float2* Z, double2* Wout, hipStream_t st) {
-  const int nblk = (int)sk_cdiv(T, Lb), lw = (int)min((int64_t)T, (int64_t)Lb + 2 * (int64_t)Lc);
-  const size_t lds = wpd_lds_bytes(C, K, lw);
-  if (lds > (size_t)WPD_LDS_LIMIT) return sk_fail(SK_EINVAL, "sk_wpd: %zu bytes of LDS per workgroup (limit %d)", lds, WPD_LDS_LIMIT);
-  // a kernel's dynamic LDS above 64 KB has to be allowed first, on the device the launch goes to: asked for per call, as no
-  // cached answer holds for another device or is safe between host threads
-  if (lds > 64 * 1024)
-    SK_CHECK_HIP(hipFuncSetAttribute((const void*)wpd_kernel<C, NTHR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((wpd_kernel<C, NTHR>), dim3((unsigned)nblk, NBIN, (unsigned)S), dim3(NTHR), lds, st, Y, ycs, yrs, mask, ldm, T, S, K,
-                     delay, iters, Lb, Lc, ref, loading, floor, lw, Win, Z, Wout);
-  SK_CHECK_LAUNCH("wpd_kernel");
-  return SK_OK;
-}
-
-template <int C>
-int wpd_launch_c(const float2* Y, int64_t ycs, int64_t yrs, const float* mask, int ldm, int T, int S, int K, int delay, int iters, int Lb,
-                 int Lc, int ref, double loading, double floor, const double2* Win, float2* Z, double2* Wout, hipStream_t st) {
-  // a wave is enough while every tile has a thread in it
-  if (wpd_tiles(C, K) <= 64)
-    return wpd_launch<C, 64>(Y, ycs, yrs, mask, ldm, T, S, K, delay, iters, Lb, Lc, ref, loading, floor, Win, Z, Wout, st);
-  return wpd_launch<C, 256>(Y, ycs, yrs, mask, ldm, T, S, K, delay, iters, Lb, Lc, ref, loading, floor, Win, Z, Wout, st);
-}
-
 }  // namespace
 
 // sk_wpd keeps everything between its passes in LDS
@@ -290,32 +265,29 @@ extern "C" int sk_wpd(const void* Y_c64, int64_t y_chan_stride, int64_t y_row_st
   SK_CHECK_ARG((int64_t)C * ((int64_t)taps + 1) <= WPD_MAXD, "sk_wpd: C * (taps + 1) = %lld above %d", (long long)C * ((long long)taps + 1),
                WPD_MAXD);
   SK_CHECK_ARG(iterations >= 1 && iterations <= WPD_MAXIT, "sk_wpd: iterations = %d outside 1..%d", iterations, WPD_MAXIT);
-  SK_CHECK_ARG(T >= 1, "sk_wpd: T = %d frames, at least 1 expected", T);
-  SK_CHECK_ARG(block_frames >= 1, "sk_wpd: block_frames = %d, at least 1 expected", block_frames);
-  SK_CHECK_ARG(context_frames >= 0, "sk_wpd: context_frames = %d is negative", context_frames);
-  SK_CHECK_ARG((int64_t)block_frames + 2 * (int64_t)context_frames <= WPD_MAXWIN,
-               "sk_wpd: a window of block_frames + 2 context_frames = %lld frames, at most %d", (long long)block_frames + 2 * (long long)context_frames,
-               WPD_MAXWIN);
-  SK_CHECK_ARG(ref >= 0 && ref < C, "sk_wpd: ref = %d outside [0, %d)", ref, C);
-  SK_CHECK_ARG(loading >= 0.0, "sk_wpd: loading = %g is negative or NaN", loading);
+  SK_CHECK_FRAMES("sk_wpd", T);
+  SK_CHECK_BLOCK_FRAMES("sk_wpd", block_frames);
+  SK_CHECK_WINDOW("sk_wpd", block_frames, context_frames, WPD_MAXWIN);
+  SK_CHECK_REF("sk_wpd", ref, C);
+  SK_CHECK_LOADING("sk_wpd", loading);
   SK_CHECK_ARG(floor > 0.0 && floor <= 1.0, "sk_wpd: floor = %g outside (0, 1] or NaN", floor);
-  SK_CHECK_ARG(ld_mask >= S * NBIN, "sk_wpd: ld_mask = %d below S * 257 = %d", ld_mask, S * NBIN);
-  SK_CHECK_ARG(y_row_stride >= NBIN, "sk_wpd: y_row_stride = %lld below 257", (long long)y_row_stride);
+  SK_CHECK_LD_MASK("sk_wpd", ld_mask, S);
+  SK_CHECK_Y_ROW_STRIDE("sk_wpd", y_row_stride);
   SK_CHECK_ARG(Y_c64 && mask && Z_c64, "sk_wpd: null pointer (Y, mask or Z)");
   const float2* Y = (const float2*)Y_c64;
   const double2* Win = (const double2*)W_in_c128;
   float2* Z = (float2*)Z_c64;
   double2* Wout = (double2*)W_out_c128;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t ycs = y_chan_stride, yrs = y_row_stride;
-  const int K = taps, I = iterations, Lb = block_frames, Lc = context_frames;
-  switch (C) {
-    case 2: return wpd_launch_c<2>(Y, ycs, yrs, mask, ld_mask, T, S, K, delay, I, Lb, Lc, ref, loading, floor, Win, Z, Wout, st);
-    case 3: return wpd_launch_c<3>(Y, ycs, yrs, mask, ld_mask, T, S, K, delay, I, Lb, Lc, ref, loading, floor, Win, Z, Wout, st);
-    case 4: return wpd_launch_c<4>(Y, ycs, yrs, mask, ld_mask, T, S, K, delay, I, Lb, Lc, ref, loading, floor, Win, Z, Wout, st);
-    case 5: return wpd_launch_c<5>(Y, ycs, yrs, mask, ld_mask, T, S, K, delay, I, Lb, Lc, ref, loading, floor, Win, Z, Wout, st);
-    case 6: return wpd_launch_c<6>(Y, ycs, yrs, mask, ld_mask, T, S, K, delay, I, Lb, Lc, ref, loading, floor, Win, Z, Wout, st);
-    case 7: return wpd_launch_c<7>(Y, ycs, yrs, mask, ld_mask, T, S, K, delay, I, Lb, Lc, ref, loading, floor, Win, Z, Wout, st);
-    default: return wpd_launch_c<8>(Y, ycs, yrs, mask, ld_mask, T, S, K, delay, I, Lb, Lc, ref, loading, floor, Win, Z, Wout, st);
-  }
+  const int K = taps, Lb = block_frames, Lc = context_frames;
+  const int nblk = (int)sk_cdiv(T, Lb), lw = (int)min((int64_t)T, (int64_t)Lb + 2 * (int64_t)Lc);
+  return sk_dispatch_int<WPD_MINC, WPD_MAXC>(C, [&](auto c) {
+    constexpr int Cc = decltype(c)::value;
+    auto launch = [&](auto kernel, int nthr) {
+      return sk_launch_lds("sk_wpd", "wpd_kernel", kernel, dim3((unsigned)nblk, NBIN, (unsigned)S), dim3(nthr), wpd_lds_bytes(Cc, K, lw),
+                           WPD_LDS_LIMIT, (hipStream_t)stream, Y, y_chan_stride, y_row_stride, mask, ld_mask, T, S, K, delay, iterations, Lb,
+                           Lc, ref, loading, floor, lw, Win, Z, Wout);
+    };
+    // a wave is enough while every tile has a thread in it
+    return wpd_tiles(Cc, K) <= 64 ? launch(wpd_kernel<Cc, 64>, 64) : launch(wpd_kernel<Cc, 256>, 256);
+  });
 }

@@ -232,35 +232,6 @@ inline int wpe_tiles(int C, int K) {
   return ntr * (ntr + 1) / 2 + ntr * ((C + 3) / 4);
 }
 
-inline bool wpe_shape_ok(int T, int C, int K, int Lb, int Lc) {
-  return C >= 1 && C <= WPE_MAXC && K >= 1 && (int64_t)C * K <= WPE_MAXD && T >= 1 && Lb >= 1 && Lc >= 0 &&
-         (int64_t)Lb + 2 * (int64_t)Lc <= WPE_MAXWIN;
-}
-
-template <int C, int NTHR>
-int wpe_launch(const float2* Y, int64_t ycs, int64_t yrs, int T, int K, int delay, int iters, int Lb, int Lc, int ref, double loading,
-               float2* X, int64_t xcs, int64_t xrs, float* mag, int ldm, double2* G, hipStream_t st) {
-  const int nblk = (int)sk_cdiv(T, Lb), lw = (int)min((int64_t)T, (int64_t)Lb + 2 * (int64_t)Lc);
-  const size_t lds = wpe_lds_bytes(C, K, lw);
-  if (lds > (size_t)WPE_LDS_LIMIT) return sk_fail(SK_EINVAL, "sk_wpe: %zu bytes of LDS per workgroup (limit %d)", lds, WPE_LDS_LIMIT);
-  // a kernel's dynamic LDS above 64 KB has to be allowed first, on the device the launch goes to: asked for per call, as no
-  // cached answer holds for another device or is safe between host threads
-  if (lds > 64 * 1024)
-    SK_CHECK_HIP(hipFuncSetAttribute((const void*)wpe_kernel<C, NTHR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL((wpe_kernel<C, NTHR>), dim3((unsigned)nblk, NBIN), dim3(NTHR), lds, st, Y, ycs, yrs, T, K, delay, iters, Lb, Lc, ref,
-                     loading, lw, X, xcs, xrs, mag, ldm, G);
-  SK_CHECK_LAUNCH("wpe_kernel");
-  return SK_OK;
-}
-
-template <int C>
-int wpe_launch_c(const float2* Y, int64_t ycs, int64_t yrs, int T, int K, int delay, int iters, int Lb, int Lc, int ref, double loading,
-                 float2* X, int64_t xcs, int64_t xrs, float* mag, int ldm, double2* G, hipStream_t st) {
-  // a wave is enough while every tile has a thread in it
-  if (wpe_tiles(C, K) <= 64) return wpe_launch<C, 64>(Y, ycs, yrs, T, K, delay, iters, Lb, Lc, ref, loading, X, xcs, xrs, mag, ldm, G, st);
-  return wpe_launch<C, 256>(Y, ycs, yrs, T, K, delay, iters, Lb, Lc, ref, loading, X, xcs, xrs, mag, ldm, G, st);
-}
-
 }  // namespace
 
 // sk_wpe keeps everything between its passes in LDS
@@ -274,32 +245,28 @@ extern "C" int sk_wpe(const void* Y_c64, int64_t y_chan_stride, int64_t y_row_st
   SK_CHECK_ARG(delay >= 1, "sk_wpe: delay = %d, at least 1 expected", delay);
   SK_CHECK_ARG((int64_t)C * taps <= WPE_MAXD, "sk_wpe: C * taps = %lld above %d", (long long)C * taps, WPE_MAXD);
   SK_CHECK_ARG(iterations >= 1 && iterations <= WPE_MAXIT, "sk_wpe: iterations = %d outside 1..%d", iterations, WPE_MAXIT);
-  SK_CHECK_ARG(T >= 1, "sk_wpe: T = %d frames, at least 1 expected", T);
-  SK_CHECK_ARG(block_frames >= 1, "sk_wpe: block_frames = %d, at least 1 expected", block_frames);
-  SK_CHECK_ARG(context_frames >= 0, "sk_wpe: context_frames = %d is negative", context_frames);
-  SK_CHECK_ARG((int64_t)block_frames + 2 * (int64_t)context_frames <= WPE_MAXWIN,
-               "sk_wpe: a window of block_frames + 2 context_frames = %lld frames, at most %d", (long long)block_frames + 2 * (long long)context_frames,
-               WPE_MAXWIN);
-  SK_CHECK_ARG(ref >= 0 && ref < C, "sk_wpe: ref = %d outside [0, %d)", ref, C);
-  SK_CHECK_ARG(loading >= 0.0, "sk_wpe: loading = %g is negative or NaN", loading);
-  SK_CHECK_ARG(y_row_stride >= NBIN, "sk_wpe: y_row_stride = %lld below 257", (long long)y_row_stride);
+  SK_CHECK_FRAMES("sk_wpe", T);
+  SK_CHECK_BLOCK_FRAMES("sk_wpe", block_frames);
+  SK_CHECK_WINDOW("sk_wpe", block_frames, context_frames, WPE_MAXWIN);
+  SK_CHECK_REF("sk_wpe", ref, C);
+  SK_CHECK_LOADING("sk_wpe", loading);
+  SK_CHECK_Y_ROW_STRIDE("sk_wpe", y_row_stride);
   SK_CHECK_ARG(x_row_stride >= NBIN, "sk_wpe: x_row_stride = %lld below 257", (long long)x_row_stride);
   SK_CHECK_ARG(!mag_out || ld_mag >= NBIN, "sk_wpe: ld_mag = %d below 257", ld_mag);
   SK_CHECK_ARG(Y_c64 && X_c64, "sk_wpe: null pointer (Y or X)");
   const float2* Y = (const float2*)Y_c64;
   float2* X = (float2*)X_c64;
   double2* G = (double2*)G_out_c128;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t ycs = y_chan_stride, yrs = y_row_stride, xcs = x_chan_stride, xrs = x_row_stride;
-  const int K = taps, I = iterations, Lb = block_frames, Lc = context_frames;
-  switch (C) {
-    case 1: return wpe_launch_c<1>(Y, ycs, yrs, T, K, delay, I, Lb, Lc, ref, loading, X, xcs, xrs, mag_out, ld_mag, G, st);
-    case 2: return wpe_launch_c<2>(Y, ycs, yrs, T, K, delay, I, Lb, Lc, ref, loading, X, xcs, xrs, mag_out, ld_mag, G, st);
-    case 3: return wpe_launch_c<3>(Y, ycs, yrs, T, K, delay, I, Lb, Lc, ref, loading, X, xcs, xrs, mag_out, ld_mag, G, st);
-    case 4: return wpe_launch_c<4>(Y, ycs, yrs, T, K, delay, I, Lb, Lc, ref, loading, X, xcs, xrs, mag_out, ld_mag, G, st);
-    case 5: return wpe_launch_c<5>(Y, ycs, yrs, T, K, delay, I, Lb, Lc, ref, loading, X, xcs, xrs, mag_out, ld_mag, G, st);
-    case 6: return wpe_launch_c<6>(Y, ycs, yrs, T, K, delay, I, Lb, Lc, ref, loading, X, xcs, xrs, mag_out, ld_mag, G, st);
-    case 7: return wpe_launch_c<7>(Y, ycs, yrs, T, K, delay, I, Lb, Lc, ref, loading, X, xcs, xrs, mag_out, ld_mag, G, st);
-    default: return wpe_launch_c<8>(Y, ycs, yrs, T, K, delay, I, Lb, Lc, ref, loading, X, xcs, xrs, mag_out, ld_mag, G, st);
-  }
+  const int K = taps, Lb = block_frames, Lc = context_frames;
+  const int nblk = (int)sk_cdiv(T, Lb), lw = (int)min((int64_t)T, (int64_t)Lb + 2 * (int64_t)Lc);
+  return sk_dispatch_int<1, WPE_MAXC>(C, [&](auto c) {
+    constexpr int Cc = decltype(c)::value;
+    auto launch = [&](auto kernel, int nthr) {
+      return sk_launch_lds("sk_wpe", "wpe_kernel", kernel, dim3((unsigned)nblk, NBIN), dim3(nthr), wpe_lds_bytes(Cc, K, lw), WPE_LDS_LIMIT,
+                           (hipStream_t)stream, Y, y_chan_stride, y_row_stride, T, K, delay, iterations, Lb, Lc, ref, loading, lw, X,
+                           x_chan_stride, x_row_stride, mag_out, ld_mag, G);
+    };
+    // a wave is enough while every tile has a thread in it
+    return wpe_tiles(Cc, K) <= 64 ? launch(wpe_kernel<Cc, 64>, 64) : launch(wpe_kernel<Cc, 256>, 256);
+  });
 }

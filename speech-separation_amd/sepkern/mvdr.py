@@ -37,14 +37,12 @@ their own in front of this one: sepkern/cacgmm.py (sk_cacgmm).
 """
 import numpy as np
 
+from .wpe import num_blocks  # noqa: F401  (one rule for the blocks of all four array kernels)
+
 F = 257
 MIN_C, MAX_C = 2, 8
 MIN_S, MAX_S = 2, 4
 D_MIN = 1e-12
-
-
-def num_blocks(T, block_frames):
-    return -(-int(T) // int(block_frames))
 
 
 def check_arguments(C, S, T, block_frames, context_blocks, ref, loading):

@@ -10,6 +10,7 @@ import torch
 from . import _lib
 from . import cacgmm as _cacgmm
 from . import dpcl as _dpcl
+from . import wpe as _wpe
 
 _WS = {}
 
@@ -669,6 +670,27 @@ def stitch(mag, windows, T, W, Hn, S, ramp, out=None, ws=None, repeat=1):
     return out[:T], perms, cost
 
 
+# ----------------------------------------------------------------------------- the array kernels' shared argument checks
+def _array_spectra(who, Y):
+    """Y of mvdr, wpe, wpd and cacgmm: (C, T, >= 257) complex64, read where it lies -> (C, T)."""
+    _chk(Y, torch.complex64)
+    if Y.dim() != 3 or Y.shape[2] < 257 or Y.stride(2) != 1:
+        raise _lib.SepkernError("%s: Y must be (C, T, >= 257) complex64 with unit bin stride" % who)
+    return int(Y.shape[0]), int(Y.shape[1])
+
+
+def _stream_columns(who, name, m, T, S):
+    """A mask, prior or output of T frames with stream s in columns s*257 .. of a row."""
+    _chk(m)
+    if m.dim() != 2 or m.stride(1) != 1 or m.shape[0] < T or m.shape[1] < S * 257:
+        raise _lib.SepkernError("%s: %s must be (>= T, >= S*257) float32 with unit column stride" % (who, name))
+
+
+def _num_blocks(T, Lb):
+    """Blocks of Lb frames; 1 where Lb is one the call itself will refuse, so that the buffers can still be sized."""
+    return _wpe.num_blocks(T, Lb) if Lb > 0 else 1
+
+
 # ----------------------------------------------------------------------------- mask-based MVDR beamforming
 def mvdr(Y, mask, S, block_frames, context_blocks, ref, loading, want_scm=False, weights=None, Z=None, ws=None, repeat=1):
     """One MVDR beamformer per stream and block of frames, steered by the masks (sk_mvdr; sepkern/mvdr.py defines the result).
@@ -679,16 +701,11 @@ def mvdr(Y, mask, S, block_frames, context_blocks, ref, loading, want_scm=False,
     -> (weights (nblk, S, 257, C) complex64, Z (S, T, 257) complex64, scm (nblk, S, 257, C, C) complex128 or None); nothing
     synchronises with the host."""
     lib = _lib.load()
-    _chk(Y, torch.complex64)
-    _chk(mask)
-    if Y.dim() != 3 or Y.shape[2] < 257 or Y.stride(2) != 1:
-        raise _lib.SepkernError("mvdr: Y must be (C, T, >= 257) complex64 with unit bin stride")
-    C, T = int(Y.shape[0]), int(Y.shape[1])
+    C, T = _array_spectra("mvdr", Y)
     S, Lb, R, ref = int(S), int(block_frames), int(context_blocks), int(ref)
-    if mask.dim() != 2 or mask.stride(1) != 1 or mask.shape[0] < T or mask.shape[1] < S * 257:
-        raise _lib.SepkernError("mvdr: mask must be (>= T, >= S*257) float32 with unit column stride")
+    _stream_columns("mvdr", "mask", mask, T, S)
     nbytes = lib.sk_mvdr_workspace_bytes(T, C, S, Lb)
-    nblk = -(-T // Lb) if Lb > 0 else 1
+    nblk = _num_blocks(T, Lb)
     dev = Y.device
     if weights is None:
         weights = torch.empty(nblk, S, 257, C, dtype=torch.complex64, device=dev)
@@ -754,10 +771,7 @@ def wpe(Y, taps, delay, iterations, block_frames, context_frames, loading, ref=0
     -> (X (C, T, 257) complex64, mag (T, 257) float32 = |X[ref]| or None, G (nblk, 257, C*taps, C) complex128 or None); nothing
     synchronises with the host."""
     _lib.load()
-    _chk(Y, torch.complex64)
-    if Y.dim() != 3 or Y.shape[2] < 257 or Y.stride(2) != 1:
-        raise _lib.SepkernError("wpe: Y must be (C, T, >= 257) complex64 with unit bin stride")
-    C, T = int(Y.shape[0]), int(Y.shape[1])
+    C, T = _array_spectra("wpe", Y)
     K, dl, I, Lb, Lc, ref = int(taps), int(delay), int(iterations), int(block_frames), int(context_frames), int(ref)
     dev = Y.device
     if X is None:
@@ -765,7 +779,7 @@ def wpe(Y, taps, delay, iterations, block_frames, context_frames, loading, ref=0
     _chk(X, torch.complex64)
     if X.dim() != 3 or tuple(X.shape[:2]) != (C, T) or X.shape[2] < 257 or X.stride(2) != 1:
         raise _lib.SepkernError("wpe: X must be (C, T, >= 257) complex64 with unit bin stride")
-    nblk = -(-T // Lb) if Lb > 0 else 1
+    nblk = _num_blocks(T, Lb)
     D = C * K
     mag = torch.empty(T, 257, dtype=torch.float32, device=dev) if want_mag else None
     G = torch.empty(nblk, 257, max(D, 0), C, dtype=torch.complex128, device=dev) if want_G else None
@@ -790,16 +804,11 @@ def wpd(Y, mask, S, taps, delay, iterations, block_frames, context_frames, loadi
     filters to start from (a W of an earlier call); Z: a contiguous complex64 (S, T, 257) buffer to write into.
     -> (Z (S, T, 257) complex64, W (nblk, S, 257, C*(taps+1)) complex128 or None); nothing synchronises with the host."""
     _lib.load()
-    _chk(Y, torch.complex64)
-    _chk(mask)
-    if Y.dim() != 3 or Y.shape[2] < 257 or Y.stride(2) != 1:
-        raise _lib.SepkernError("wpd: Y must be (C, T, >= 257) complex64 with unit bin stride")
-    C, T = int(Y.shape[0]), int(Y.shape[1])
+    C, T = _array_spectra("wpd", Y)
     S, K, dl, I, Lb, Lc, ref = int(S), int(taps), int(delay), int(iterations), int(block_frames), int(context_frames), int(ref)
-    if mask.dim() != 2 or mask.stride(1) != 1 or mask.shape[0] < T or mask.shape[1] < S * 257:
-        raise _lib.SepkernError("wpd: mask must be (>= T, >= S*257) float32 with unit column stride")
+    _stream_columns("wpd", "mask", mask, T, S)
     dev = Y.device
-    nblk = -(-T // Lb) if Lb > 0 else 1
+    nblk = _num_blocks(T, Lb)
     D = max(C * (K + 1), 0)
     shape_W = (nblk, max(S, 0), 257, D)
     if W_in is not None:
@@ -834,20 +843,16 @@ def cacgmm(Y, prior, S, iterations, block_frames, context_frames, loading, B_in=
     (not overlapping prior).
     -> (mask (T, S*257) float32, B (nblk, S, 257, C, C) complex128 or None); nothing synchronises with the host."""
     _lib.load()
-    _chk(Y, torch.complex64)
     _chk(prior)
-    if Y.dim() != 3 or Y.shape[2] < 257 or Y.stride(2) != 1:
-        raise _lib.SepkernError("cacgmm: Y must be (C, T, >= 257) complex64 with unit bin stride")
-    C, T = int(Y.shape[0]), int(Y.shape[1])
+    C, T = _array_spectra("cacgmm", Y)
     S, I, Lb, Lc = int(S), int(iterations), int(block_frames), int(context_frames)
     try:                                    # the kernel's own limits, before anything is sized by them
         _cacgmm.check_arguments(C, S, T, I, Lb, Lc, float(loading), y_row_stride=int(Y.stride(1)))
     except ValueError as e:
         raise _lib.SepkernError(str(e))
-    if prior.dim() != 2 or prior.stride(1) != 1 or prior.shape[0] < T or prior.shape[1] < S * 257:
-        raise _lib.SepkernError("cacgmm: prior must be (>= T, >= S*257) float32 with unit column stride")
+    _stream_columns("cacgmm", "prior", prior, T, S)
     dev = Y.device
-    nblk = -(-T // Lb)
+    nblk = _num_blocks(T, Lb)
     shape_B = (nblk, S, 257, C, C)
     if B_in is not None:
         _chk(B_in, torch.complex128)
@@ -855,9 +860,7 @@ def cacgmm(Y, prior, S, iterations, block_frames, context_frames, loading, B_in=
             raise _lib.SepkernError("cacgmm: B_in must be (nblk, S, 257, C, C) contiguous complex128")
     if out is None:
         out = torch.empty(T, S * 257, dtype=torch.float32, device=dev)
-    _chk(out)
-    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < T or out.shape[1] < S * 257:
-        raise _lib.SepkernError("cacgmm: out must be (>= T, >= S*257) float32 with unit column stride")
+    _stream_columns("cacgmm", "out", out, T, S)
     B = torch.empty(shape_B, dtype=torch.complex128, device=dev) if want_B else None
     # algorithmic bytes: every iteration reads its window of Y and of the prior once, the block is read once more and the
     # masks written; the windows overlap by the context

@@ -35,6 +35,9 @@ LARGE = [(7, 9), (8, 9)]
 GEOMETRIES = [(9, 16, 0), (16, 16, 0), (33, 16, 0), (33, 16, 5), (40, 7, 100), (5, 1, 2), (150, 64, 40)]
 LARGE_GEOMETRIES = [0, 1, 3]                                       # the D >= 70 cases: the numpy definition takes seconds there
 SWITCH = (6, 6)                                                    # D = 42: 70 tiles, the smallest D with four waves
+# (C, K, T, Lb, Lc) for the chunk lengths the geometries above stay inside: a second chunk at 256 frames (C <= 2), and 128
+# frames plus one (C <= 4) with a last block of one frame
+PINS = [(2, 1, 300, 300, 0), (4, 1, 130, 129, 0)]
 DELAYS = [1, 3]
 RATIOS = {}                                                        # label -> largest |W - W_ref| / gate, for the report at the end
 
@@ -137,7 +140,10 @@ def check(Y, mask, got, S, K, delay, Lb, Lc, ref, floor, W_in, label):
 
 def both_layouts(C, K, gi, delay, S, floor, dev):
     T, Lb, Lc = GEOMETRIES[gi]
-    ref = (gi + K) % C
+    layouts_at(C, K, T, Lb, Lc, (gi + K) % C, delay, S, floor, dev)
+
+
+def layouts_at(C, K, T, Lb, Lc, ref, delay, S, floor, dev):
     Y, mask = inputs(C, T, S, ref)
     label = "C=%d K=%d S=%d T=%d Lb=%d Lc=%d delay=%d ref=%d floor=%g" % (C, K, S, T, Lb, Lc, delay, ref, floor)
     W_in = None
@@ -172,6 +178,12 @@ def test_wpd_matches_the_definition_with_four_waves(dev, gi, delay):
 @pytest.mark.parametrize("C,K", LARGE)
 def test_wpd_matches_the_definition_at_seventy_and_eighty_unknowns(dev, C, K, gi, delay):
     both_layouts(C, K, gi, delay, 2, FLOOR, dev)
+
+
+@pytest.mark.parametrize("delay", DELAYS)
+@pytest.mark.parametrize("C,K,T,Lb,Lc", PINS)
+def test_wpd_matches_the_definition_at_its_longer_chunks(dev, C, K, T, Lb, Lc, delay):
+    layouts_at(C, K, T, Lb, Lc, (T + K) % C, delay, 2, FLOOR, dev)
 
 
 @pytest.mark.parametrize("C,K,gi,S,floor", [(2, 1, 3, 4, FLOOR), (4, 1, 2, 4, FLOOR), (3, 0, 3, 3, 1.0), (5, 1, 4, 2, 1.0)])

@@ -36,6 +36,13 @@ GEOMETRIES = [(9, 16, 0), (16, 16, 0), (33, 16, 0), (33, 16, 5), (40, 7, 100), (
 LARGE_GEOMETRIES = [0, 1, 3]                                       # the D >= 70 cases: the numpy definition takes seconds there
 DELAYS = [1, 3]
 ITERATIONS = [1, 3]
+# (C, K, T, Lb, Lc) where the kernel's loops branch.  The chunk is 256 frames at C <= 2, 128 at C <= 4, else 64: a second chunk
+# of 44 frames at 256, in the window walk and the output walk; a second chunk of one frame and a last block of one frame;
+# windows of 390 and 520 frames whose delayed past reaches across chunk boundaries; 128 frames plus one; exactly one chunk of
+# 64; one chunk of 64 plus 6 frames; windows of 97 and 130 frames in chunks of 64 with a context; 54 tiles, the most one wave
+# takes at C = 1, and 65 tiles, the fewest on four waves
+PINS = [(1, 2, 300, 300, 0), (2, 2, 258, 257, 0), (2, 1, 520, 260, 130), (3, 2, 129, 129, 0), (6, 1, 64, 64, 0), (5, 1, 70, 70, 0),
+        (5, 2, 130, 65, 32), (1, 36, 100, 80, 10), (1, 37, 100, 80, 10)]
 
 
 @pytest.fixture(scope="module")
@@ -149,7 +156,10 @@ def check(Y, r, got, Cn, K, delay, I, Lb, ref, label):
 
 def both_layouts(C, K, gi, delay, I, dev):
     T, Lb, Lc = GEOMETRIES[gi]
-    ref = (gi + K) % C
+    layouts_at(C, K, T, Lb, Lc, (gi + K) % C, delay, I, dev)
+
+
+def layouts_at(C, K, T, Lb, Lc, ref, delay, I, dev):
     Y = inputs(C, T)
     r = reference(C, K, T, Lb, Lc, delay, I, ref)
     label = "C=%d K=%d T=%d Lb=%d Lc=%d delay=%d I=%d ref=%d" % (C, K, T, Lb, Lc, delay, I, ref)
@@ -177,6 +187,12 @@ def test_wpe_matches_the_definition_in_both_layouts(dev, C, K, gi, delay, I):
 @pytest.mark.parametrize("C,K", LARGE)
 def test_wpe_matches_the_definition_at_seventy_and_eighty_unknowns(dev, C, K, gi, delay, I):
     both_layouts(C, K, gi, delay, I, dev)
+
+
+@pytest.mark.parametrize("delay,I", [(1, 1), (3, 3)])
+@pytest.mark.parametrize("C,K,T,Lb,Lc", PINS)
+def test_wpe_matches_the_definition_at_its_chunk_and_thread_count_edges(dev, C, K, T, Lb, Lc, delay, I):
+    layouts_at(C, K, T, Lb, Lc, (T + K) % C, delay, I, dev)
 
 
 def test_silent_windows_and_a_delay_beyond_the_recording_pass_y_through(dev):
