@@ -7,6 +7,9 @@ Cases and gates: tests/_dpcl_cases.py (tests/test_dpcl.py shows on any machine t
 Every figure is printed before it is asserted (pytest -s shows them; profiles/dpcl.txt records them).
 Shapes: the batches around a chunk boundary (CH = 8 frames), F in {5, 64, 65, 257} (the tail of a row against the 64-point
 tile), (D, S) up to (40, 4) = the largest padded tile, ld = F D and F D + 8, both weightings.
+The kernels' own edges -- the Gram-tile and backward-block edges of (D, S), multi-chunk ragged batches, the wave trips of a chunk,
+the pick ties, ab and stats against the definition -- are pinned in tests/test_gpu_dpcl_cases.py (claims and defect models:
+tests/test_dpcl_cases.py).
 """
 import ctypes as C
 
