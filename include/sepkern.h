@@ -818,6 +818,41 @@ int sk_stft_psa(const void* wav, int pcm16, const int64_t* sig_offs, const int32
                 int clamp, const int32_t* offs, const int64_t* row_base, float* mix_rows, float* targets, int ld, int64_t plane,
                 void* ws, int min_samples, int max_frames, sk_stream_t stream);
 
+/* ---------------------------------------------------------------- inter-channel phase features (conf key ipd_channels)
+ * The input rows of a network that sees an array (sepkern/ipd.py states the definition and restates it in numpy fp64): with Y_r
+ * the reference channel's STFT and Y_c listed channel c's, both as sk_stft defines them, P = number of listed channels (1..7),
+ *   rows[row*ld + f]                  = |Y_r[t][f]|                                  (the bits sk_stft's magnitude output has)
+ *   rows[row*ld + 257 (1 + 2p) + f]   = Re(Y_c conj Y_r) / (|Y_c| |Y_r|) = cos(theta_c - theta_r),   c = listed channel p
+ *   rows[row*ld + 257 (2 + 2p) + f]   = Im(Y_c conj Y_r) / (|Y_c| |Y_r|) = sin(theta_c - theta_r)
+ * cos and sin both 0 where the fp32 |Y_c|^2 or |Y_r|^2 is below 2^-100.  In fp32, with (a, b) = (Re, Im): the numerators are
+ * fma(a_c, a_r, b_c b_r) and fma(b_c, a_r, -(a_c b_r)), a squared magnitude is fma(a, a, b b), and the feature is
+ * (numerator * rsq(|Y_c|^2)) * rsq(|Y_r|^2): every rounding is fixed, and both entry points give the same bits on the same spectra.
+ * Rows are ld >= 257 (1 + 2P) floats; the columns behind the features up to the next multiple of 16 (or to ld, if that is
+ * nearer) are stored as zeros and nothing behind those is touched: with ld = the width rounded up to 16 a row is what the
+ * engine's first layer reads.  Each element is written by one lane; vector stores only; bitwise reproducible.
+ *
+ * sk_stft_ipd (training): one launch from the batch's waveforms to the rows.  Signal q (0 = the reference channel, 1 + p =
+ * listed channel p) of utterance u: nsamp[u] samples at wav + sig_offs[q*B + u] (elements; float32, or int16 PCM scaled by
+ * 1/32768 when pcm16 != 0), T_u = 1 + nsamp[u]/hop frames; C = 1 + P signals per utterance, 2..8.  Row of frame t of
+ * utterance u: offs[t] + u (packed rows of a length-sorted batch, row_base NULL) or row_base[u] + t (per-utterance blocks,
+ * offs NULL).  Only the rows of existing frames are written; an utterance's numbers depend on neither the batch around it nor
+ * the sample format.  mix_rows (may be NULL): a contiguous (rows, 257) copy of the magnitude columns, for the loss kernels,
+ * which take the mixture without a row stride.  ws: work rows, 257 * 8 bytes for every row the launch addresses, contents
+ * undefined afterwards (the reference's bins on their way from the lane that formed them to the same lane's P contractions).
+ * min_samples <= min_u nsamp[u] must exceed n_fft/2, max_frames >= max_u T_u sizes the grid; n_fft = 512, hop = 128; B <= 65535.
+ *
+ * sk_ipd_rows (inference): the same features from spectra in memory.  Y: complex64, element (c, t, f) at
+ * Y[c*y_chan_stride + t*y_row_stride + f] (elements, y_row_stride >= 257), C channels (2..8), T frames; chans_host: host array
+ * of the P listed channels, each in [0, C), distinct and not ref.  mag (T, ld_mag >= 257): the magnitude rows of the reference
+ * channel as the caller already holds them (sk_stft's magnitude output, sk_wpe's mag_out); they are COPIED into columns
+ * 0..256, so an IPD model's first 257 inputs are the bits a single-channel model gets.  Row t of rows is frame t.
+ * Both return SK_EINVAL (with a text for sk_last_error) for arguments outside the above. */
+int sk_stft_ipd(const void* wav, int pcm16, const int64_t* sig_offs, const int32_t* nsamp, int B, int C, int n_fft, int hop,
+                const int32_t* offs, const int64_t* row_base, float* rows, int ld, float* mix_rows, void* ws, int min_samples,
+                int max_frames, sk_stream_t stream);
+int sk_ipd_rows(const void* Y_c64, int64_t y_chan_stride, int64_t y_row_stride, int T, int C, int ref, const int32_t* chans_host,
+                int P, const float* mag, int ld_mag, float* rows, int ld, sk_stream_t stream);
+
 /* ---------------------------------------------------------------- RSH arch (reference archs/RSH.py)
  * One pass of the greedy source-assignment loss (archs/RSH.py:225-244): mask (T,B,F); x (T,B,ldx) whose
  * first F columns are the mixture; src_host[r] -> (T,B,F), r < S (host array of device pointers).

@@ -46,6 +46,12 @@ Beyond the reference (all optional, defaults reproduce it):
     single-speaker utterances and mixed on the GPU (sk_dynamic_mix); every loss above trains on them.  With rir_scp / rir_synth
     (--mix-rir-scp / --mix-rir-synth) every source is first convolved with a room impulse response, also on the GPU
     (sk_fir_convolve; sepkern/reverb.py): reverberant mixtures, reverberant sources as targets.
+  * conf keys ipd_channels (e.g. 1,2,3) and ipd_ref (0): an IPD model (sepkern/ipd.py).  The network's input is the magnitude
+    of channel ipd_ref of an array recording followed by cos and sin of the phase difference of every listed channel against
+    it, in_dim = 257 (1 + 2P); feat_dim, out_dim and the losses mse / psa / tpsa / dpcl / sisdr are what they are without.
+    It trains on WavTrainSet(ipd_ref=, ipd_channels=) batches of multi-channel wav files (steps/train_qsub.py --wav-input hands
+    the conf keys on): the mixture's listed channels travel as 'chan<c>' behind 'mix' and 'source<N>', and one sk_stft_ipd
+    launch makes the wide rows.  Not with loss=mixit, --dynamic-mix or npz features; steps/separate_wav.py separates with it.
 """
 import collections
 import itertools
@@ -69,9 +75,10 @@ except ImportError:  # the frozen copy exp/<...>/arch.py is imported from anothe
     import sepkern  # noqa: F401
 from sepkern import dist as skdist
 from sepkern import dpcl as _dpcl
+from sepkern import ipd as _ipd
 from sepkern import ops
 from sepkern.data import features_from_pcm as _features_from_pcm, wave_features_from_pcm as _wave_features_from_pcm
-from sepkern.data import psa_features_from_pcm as _psa_features_from_pcm
+from sepkern.data import psa_features_from_pcm as _psa_features_from_pcm, ipd_rows_from_pcm as _ipd_rows_from_pcm
 from sepkern.collate import collate_sorted, eval_magnitudes, read_scp, stage_copies, train_sample
 from sepkern.model import SepDNNBase, UnpackFn, to_packed as _to_packed
 from sepkern.packing import Packing
@@ -137,12 +144,19 @@ class WavTrainSet(Dataset):
   of the recipe would have stored as npz is computed on the GPU inside compute_loss (sk_stft straight into the
   padded (T,B,F) batch).  12x less host I/O than float32 spectrograms and no zlib in the loader."""
 
-  def __init__(self, datadir, location="", sample_rate=None):
+  def __init__(self, datadir, location="", sample_rate=None, ipd_ref=0, ipd_channels=()):
     import glob
     self.items = []
     for line in open(datadir + "/wav.scp"):
       reco_id, filename = line.rstrip('\n').split(' ')
       self.items.append(sorted(glob.glob(filename.replace("/mix/", "/*/"))))
+    # ipd_channels (the model's conf keys, sepkern/ipd.py): the mixtures are array recordings.  'mix' is then channel ipd_ref
+    # of the mixture file, its listed channels follow as 'chan<c>', and a source file with several channels gives its channel
+    # ipd_ref.  Without them every file is mono, as before.
+    self.ipd_ref = _ipd.parse_ref(ipd_ref)
+    self.ipd_channels = _ipd.parse_channels(ipd_channels, self.ipd_ref)
+    if self.items and self.items[0]:
+      self._check_channels(self.items[0][0])
     # sample_rate (steps/train_qsub.py --sample-rate): the rate the network works at.  None: the files' own rate is never
     # looked at (the recipe's data is wav8k).  With a rate, the loader still ships the int16 PCM as it is on disk -- at the
     # file's rate, which it records -- and the batch is resampled on the GPU in front of the STFT (sk_resample), as the
@@ -157,8 +171,54 @@ class WavTrainSet(Dataset):
     from sepkern.data import wav_frames
     return [wav_frames(files[0], sample_rate=self.sample_rate) for files in self.items]
 
+  def _check_channels(self, mix_file):
+    """The mixture file against the model, from its header: raised when the set is built, not at the first batch."""
+    import wave
+    try:
+      with wave.open(mix_file, "rb") as w:
+        have = w.getnchannels()
+    except wave.Error:          # (not 16-bit PCM: __getitem__ says so)
+      return
+    if not self.ipd_channels:
+      if have != 1:
+        raise ValueError("%s has %d channels and the model sees one: list the channels whose phase differences it is to see "
+                         "in the conf key ipd_channels (only mono 16-bit PCM wav is supported without)" % (mix_file, have))
+      return
+    need = max(self.ipd_channels + (self.ipd_ref,)) + 1
+    if have < need:
+      raise ValueError("%s has %d channel(s): ipd_ref = %d with ipd_channels = %s needs %d -- a mono batch cannot feed an IPD model"
+                       % (mix_file, have, self.ipd_ref, ",".join(str(c) for c in self.ipd_channels), need))
+
+  def _read_array(self, idx):
+    """__getitem__ with ipd_channels: {'mix': channel ipd_ref, 'source<N>': channel ipd_ref of each source file (a mono file as
+    it is), 'chan<c>': the mixture's listed channels, in their listed order}."""
+    import scipy.io.wavfile
+    out, rate, extra = {}, None, {}
+    for i, f in enumerate(self.items[idx]):
+      fs, x = scipy.io.wavfile.read(f)
+      if x.dtype != np.int16 or x.ndim not in (1, 2):
+        raise ValueError("%s: only 16-bit PCM wav is supported" % f)
+      if self.sample_rate is not None and rate is not None and fs != rate:
+        raise ValueError("%s is sampled at %d Hz, its mixture at %d: the sources of a mixture must share its rate" % (f, fs, rate))
+      rate = fs
+      if i == 0:
+        self._check_channels(f)
+        for c in self.ipd_channels:
+          extra[_ipd.chan_key(c)] = np.ascontiguousarray(x[:, c])
+      elif x.ndim == 2 and x.shape[1] <= self.ipd_ref:
+        raise ValueError("%s has %d channels, ipd_ref = %d" % (f, x.shape[1], self.ipd_ref))
+      out['mix' if i == 0 else 'source' + str(i)] = np.ascontiguousarray(x[:, self.ipd_ref]) if x.ndim == 2 else x
+    if len(out) == 1:
+      out['source1'] = out['mix']
+    out.update(extra)
+    if self.sample_rate is not None:
+      out['rate'] = int(rate)
+    return out
+
   def __getitem__(self, idx):
     import scipy.io.wavfile
+    if self.ipd_channels:
+      return self._read_array(idx)
     out, rate = {}, None
     for i, f in enumerate(self.items[idx]):
       fs, x = scipy.io.wavfile.read(f)
@@ -181,7 +241,9 @@ class WavCollator():
   sample_rate (WavTrainSet(sample_rate=...)) the samples say at which 'rate' they were recorded, the frame counts are those at
   sample_rate, and the batch also carries {'rate': [per utterance], 'target_rate': sample_rate}.  One tensor
   crosses from the loader's worker process to the trainer instead of 32 x (S + 1) (each of which costs a shared-memory
-  hand-over: measured 15-18 ms per batch whatever the worker count, more than a 14 ms bf16 step)."""
+  hand-over: measured 15-18 ms per batch whatever the worker count, more than a 14 ms bf16 step).
+  An array item (WavTrainSet with ipd_channels) carries the mixture's listed channels as 'chan<c>': they follow the sources in
+  'keys' and in the flat tensor, in the item's order; a batch without them is the batch it was."""
 
   def __init__(self, sample_rate=None):
     self.sample_rate = None if sample_rate is None else int(sample_rate)
@@ -198,11 +260,12 @@ class WavCollator():
       batch = [{k: v for k, v in d.items() if k != 'rate'} for d in batch]
       frames = [1 + out_len(len(d['mix']), r, self.sample_rate) // 128 for d, r in zip(batch, rates)]
     order = np.argsort(np.array(frames))[::-1]
-    others = [k for k in batch[0] if k != 'mix']
+    chans = _ipd.chan_keys(batch[0])       # an array item's listed channels ('chan<c>', WavTrainSet with ipd_channels), in its order
+    others = [k for k in batch[0] if k != 'mix' and k not in chans]
     bad = [k for k in others if not (k.startswith('source') and k[6:].isdigit())]
     if bad:
       raise ValueError("WavCollator: signals besides 'mix' must be named 'source<N>' (got %r)" % bad)
-    keys = ['mix'] + sorted(others, key=lambda k: int(k[6:]))
+    keys = ['mix'] + sorted(others, key=lambda k: int(k[6:])) + chans
     # ONE list of sample counts ('lens', the mixture's) describes every key of the flat tensor: a source whose length differs
     # from its mixture's by a single sample would shift every later signal -- wrong targets, no error -- so it is one here
     for d in batch:
@@ -484,6 +547,23 @@ def parse_loss(value):
   return value
 
 
+IPD_NEEDS_WAVEFORMS = "`ipd_channels` needs waveforms: an IPD model trains on array recordings with `--wav-input`"
+IPD_NO_MIXIT = "`ipd_channels` does not train with `loss=mixit`: its mixtures are sums of two recordings made on one channel"
+IPD_NO_DYNAMIC_MIX = "`ipd_channels` does not train with `--dynamic-mix`: the mixtures made on the GPU have one channel"
+IPD_NO_NPZ = ("`ipd_channels`: npz features hold one channel's magnitudes; an IPD model separates array recordings with "
+              "steps/separate_wav.py")
+
+
+def ipd_conf(conf, loss_kind=None):
+  """(ipd_ref, ipd_channels) of a model conf (a dict of strings): (0, ()) for a model without ipd_channels.  With the
+  conf's loss (parsed) an unsupported pairing is refused here, when the model -- or the driver -- reads its conf."""
+  ref = _ipd.parse_ref(conf.get('ipd_ref', 0))
+  chans = _ipd.parse_channels(conf.get('ipd_channels'), ref)
+  if chans and loss_kind in MIXIT_LOSSES:
+    raise ValueError(IPD_NO_MIXIT)
+  return ref, chans
+
+
 NEEDS_WAVEFORMS = "`loss=sisdr` needs waveforms: train with `--wav-input`"
 
 
@@ -547,10 +627,16 @@ class SepDNN(SepDNNBase):
       if self.dpcl_kmeans_iters < 0:
         raise ValueError("loss=dpcl: dpcl_kmeans_iters = %d is negative" % self.dpcl_kmeans_iters)
     out_dim = self.feat_dim * (self.embed_dim if self.loss_kind in DPCL_LOSSES else self.num_spk)
+    # ipd_channels (sepkern/ipd.py): the network also sees the phase differences of the listed channels against ipd_ref --
+    # in_dim = 257 (1 + 2P); feat_dim, out_dim and every loss stay as they are
+    self.ipd_ref, self.ipd_channels = ipd_conf(kwargs, self.loss_kind)
+    if self.ipd_channels and self.feat_dim != _ipd.F:
+      raise ValueError("ipd_channels: the phase features are made for feat_dim = %d (got %d)" % (_ipd.F, self.feat_dim))
+    in_dim = _ipd.in_dim(len(self.ipd_channels)) if self.ipd_channels else self.feat_dim
     for key in kwargs.keys():
       print('modelparam:', key, kwargs[key])
     # the reference hard-codes 2 x 600 (archs/uPIT.py:115-119); hidden_dim / num_layers widen it
-    self._build(gpuid, self.feat_dim, out_dim, int(kwargs.get('hidden_dim', 600)),
+    self._build(gpuid, in_dim, out_dim, int(kwargs.get('hidden_dim', 600)),
                 int(kwargs.get('num_layers', 2)), str(kwargs.get('dtype', 'fp32')), kwargs.get('sync_bn', '0'))
 
   def forward_packed(self, x2d, pk):
@@ -569,7 +655,8 @@ class SepDNN(SepDNNBase):
       return out
     if not 2 <= self.num_spk <= _dpcl.MAX_S:
       raise ValueError("loss=dpcl: k-means masks need num_spk in 2..%d clusters (got %d)" % (_dpcl.MAX_S, self.num_spk))
-    return ops.dpcl_kmeans(out.detach(), x2d, pk, self.num_spk, self.dpcl_kmeans_iters, self.dpcl_vad_db, D=self.embed_dim)[0]
+    mags = x2d[:, :self.feat_dim].contiguous() if getattr(self, 'ipd_channels', ()) else x2d    # (an IPD model's rows start with them)
+    return ops.dpcl_kmeans(out.detach(), mags, pk, self.num_spk, self.dpcl_kmeans_iters, self.dpcl_vad_db, D=self.embed_dim)[0]
 
   def forward_padded(self, x, lens):
     """x (T,B,F) time-major zero-padded CUDA tensor, lens int32 CUDA (B) -> mask (T,B,F*S)."""
@@ -605,9 +692,11 @@ def compute_cv_loss(model, epoch, batch_sample, plotdir=""):
   return loss, norm
 
 
-def compute_loss_packed(model, mix, sources, pk, plotdir=""):
+def compute_loss_packed(model, mix, sources, pk, plotdir="", net_in=None):
   """compute_loss on inputs that are already resident on the GPU as PACKED rows: mix (R,F) and sources [(R,F)]*S
-  float32 -- PackedSequence.data of the collator's batch -- and their Packing pk.  Same return as compute_loss."""
+  float32 -- PackedSequence.data of the collator's batch -- and their Packing pk.  Same return as compute_loss.
+  net_in (here and in the routes below): the network's input rows where they are not mix -- an IPD model's wide rows
+  (sepkern.data.ipd_rows_from_pcm); the loss kernels read mix either way."""
   batch = pk.B
   model.zero_grad()
   model.hidden = model.init_hidden(batch)
@@ -618,7 +707,7 @@ def compute_loss_packed(model, mix, sources, pk, plotdir=""):
   training_step = model.training and torch.is_grad_enabled()
   norm_override = skdist.global_norm(pk.lens, model.feat_dim) if training_step else None
 
-  mask_out = model.forward_packed(mix, pk)
+  mask_out = model.forward_packed(mix if net_in is None else net_in, pk)
   # mask_out: tensor of shape (sum of lengths, feat_dim*num_spk)
   out, best = _PitFn.apply(mask_out, mix, pk, norm_override, *sources)
   loss, norm = out[0], out[1].detach()
@@ -641,7 +730,7 @@ def compute_loss_packed(model, mix, sources, pk, plotdir=""):
   return loss, norm
 
 
-def compute_loss_dpcl(model, mix, sources, pk):
+def compute_loss_dpcl(model, mix, sources, pk, net_in=None):
   """The loss=dpcl route on loss=mse's inputs: mix (R,F) and sources [(R,F)]*S packed magnitude rows and their Packing.
   Returns (mean deep-clustering loss per utterance, number of utterances)."""
   if len(sources) < model.num_spk:
@@ -651,14 +740,14 @@ def compute_loss_dpcl(model, mix, sources, pk):
   # data-parallel: divide by the GLOBAL utterance count (None = single process: the kernel uses B), while training only
   training_step = model.training and torch.is_grad_enabled()
   count = skdist.global_norm(pk.lens.new_full((1,), pk.B), 1) if training_step else None
-  z = model.forward_packed(mix, pk)                     # (rows, feat_dim * embed_dim): plane d of a row = dimension d of its bins
+  z = model.forward_packed(mix if net_in is None else net_in, pk)      # (rows, feat_dim * embed_dim): plane d of a row = dimension d of its bins
   srcs = [s.contiguous() for s in sources[:model.num_spk]]
   out = _DpclFn.apply(z, mix.contiguous(), pk, count, model.embed_dim, model.dpcl_weight, model.dpcl_vad_db, *srcs)
   model.step_frames = pk.R                  # (the norm counts utterances: the driver's frames/s line reads this)
   return out[0], out[1].detach()
 
 
-def _wave_loss(model, mix, pk, wave, loss, descriptors, extra=()):
+def _wave_loss(model, mix, pk, wave, loss, descriptors, extra=(), net_in=None):
   """The head the waveform losses share: a fresh state, the global count, the descriptors, the network, the loss ->
   (out = [loss, count, sum], the per-utterance choice)."""
   n_est = model.num_spk
@@ -668,20 +757,20 @@ def _wave_loss(model, mix, pk, wave, loss, descriptors, extra=()):
   training_step = model.training and torch.is_grad_enabled()
   count = skdist.global_norm(pk.lens.new_full((1,), pk.B), 1) if training_step else None
   desc = descriptors(pk, wave['sig_offs'], n_est)       # (uploaded before the network is enqueued, not behind it)
-  mask_out = model.forward_packed(mix, pk)
+  mask_out = model.forward_packed(mix if net_in is None else net_in, pk)
   out, best = _WaveLossFn.apply(mask_out, pk, wave, desc, count, n_est, loss, extra)
   model.step_frames = pk.R                  # (the norm counts utterances: the driver's frames/s line reads this)
   return out, best.detach()
 
 
-def compute_loss_wave(model, mix, pk, wave):
+def compute_loss_wave(model, mix, pk, wave, net_in=None):
   """The loss=sisdr route: mix (R,F) packed magnitude rows (the network's input), wave as wave_features_from_pcm made it.
   Returns (mean negative SI-SDR per utterance in dB, number of utterances)."""
   S = model.num_spk
   missing = [k for k in ('source' + str(i + 1) for i in range(S)) if k not in wave['sig_offs']]
   if missing:
     raise ValueError("loss=sisdr: the batch holds no waveform %s (num_spk = %d)" % (", ".join(missing), S))
-  out, model.last_best_perm = _wave_loss(model, mix, pk, wave, _SISDR, ops.sisdr_descriptors)
+  out, model.last_best_perm = _wave_loss(model, mix, pk, wave, _SISDR, ops.sisdr_descriptors, net_in=net_in)
   # (last_best_perm: arg-max permutation per utterance, index into itertools.permutations)
   return out[0], out[1].detach()
 
@@ -723,44 +812,81 @@ def compute_loss_padded(model, mix, sources, lens, plotdir=""):
   return out
 
 
+def _pcm_front(model, pcm, dev, front, **front_args):
+  """A PCM batch through `front` (one of sepkern.data's front ends) -> (its result, net_in): for an IPD model net_in is the
+  wide input rows, made with the front end's rows from one copy of the samples (sepkern.data.ipd_rows_from_pcm); for any other
+  model None -- the call is the one it was."""
+  _match_channels(model, _ipd.chan_keys(pcm['keys']))
+  if getattr(model, 'ipd_channels', ()):
+    return _ipd_rows_from_pcm(pcm, dev, front, **front_args)
+  return front(pcm, dev, **front_args), None
+
+
+def _match_channels(model, have):
+  """The 'chan<c>' signals of a batch against the model's ipd_channels: the same channels in the same order, or an error."""
+  want = [_ipd.chan_key(c) for c in getattr(model, 'ipd_channels', ())]
+  if list(have) == want:
+    return
+  if not want:
+    raise ValueError("the batch carries the array channels %s and the model sees one channel: give it the conf key ipd_channels, "
+                     "or build the WavTrainSet without" % ", ".join(have))
+  if not have:
+    raise ValueError("the model has ipd_channels = %s and the batch holds one channel: an IPD model trains on WavTrainSet(ipd_ref, "
+                     "ipd_channels) batches (steps/train_qsub.py --wav-input)" % ",".join(str(c) for c in model.ipd_channels))
+  raise ValueError("the batch carries the channels %s, the model's ipd_channels ask for %s in that order" % (", ".join(have), ", ".join(want)))
+
+
+def _staged_net_in(model, batch_sample):
+  """The wide rows a Prefetcher staged with the batch (None for a model without ipd_channels)."""
+  _match_channels(model, batch_sample.get('ipd_keys', []) if 'ipd' in batch_sample else [])
+  return batch_sample.get('ipd')
+
+
 def compute_loss(model, epoch, batch_sample, plotdir=""):
   dev = model.lin.weight.device
   kind = getattr(model, 'loss_kind', 'mse')
   if kind in PSA_LOSSES:
     if 'pcm' in batch_sample:
-      mix, targets, pk = _psa_features_from_pcm(batch_sample['pcm'], dev, clamp=kind == 'tpsa')
+      (mix, targets, pk), net_in = _pcm_front(model, batch_sample['pcm'], dev, _psa_features_from_pcm, clamp=kind == 'tpsa')
     elif 'packed' in batch_sample and 'targets' in batch_sample:  # staged by Prefetcher(targets=kind): the targets are in place
       if batch_sample['targets'] != kind:
         raise ValueError("loss=%s: the batch was staged with %r targets" % (kind, batch_sample['targets']))
-      mix, targets, pk = batch_sample['packed']
+      (mix, targets, pk), net_in = batch_sample['packed'], _staged_net_in(model, batch_sample)
     else:                                                         # npz feature batches hold magnitudes only
       raise ValueError(needs_waveforms(kind))
     if len(targets) < model.num_spk:
       raise ValueError("loss=%s: the batch holds %d source waveforms (num_spk = %d)" % (kind, len(targets), model.num_spk))
-    return compute_loss_packed(model, mix, targets[:model.num_spk], pk, plotdir)
+    return compute_loss_packed(model, mix, targets[:model.num_spk], pk, plotdir, net_in=net_in)
   if kind in WAVE_LOSSES:
     if 'pcm' in batch_sample:
-      mix, _, pk, wave = _wave_features_from_pcm(batch_sample['pcm'], dev, source_mags=False)
+      (mix, _, pk, wave), net_in = _pcm_front(model, batch_sample['pcm'], dev, _wave_features_from_pcm, source_mags=False)
     elif 'packed' in batch_sample and 'wave' in batch_sample:     # staged by Prefetcher(keep_wave=True)
-      (mix, _, pk), wave = batch_sample['packed'], batch_sample['wave']
+      (mix, _, pk), wave, net_in = batch_sample['packed'], batch_sample['wave'], _staged_net_in(model, batch_sample)
     else:                                                         # npz feature batches hold magnitudes only
       raise ValueError(needs_waveforms(kind))
-    return compute_loss_mixit(model, mix, pk, wave) if kind in MIXIT_LOSSES else compute_loss_wave(model, mix, pk, wave)
+    if kind in MIXIT_LOSSES:       # (never an IPD model: SepDNN refuses the pairing)
+      return compute_loss_mixit(model, mix, pk, wave)
+    return compute_loss_wave(model, mix, pk, wave, net_in=net_in)
   if 'pcm' in batch_sample:        # WavTrainSet batches: features are computed on the GPU
-    mix, sources, pk = _features_from_pcm(batch_sample['pcm'], dev)
+    (mix, sources, pk), net_in = _pcm_front(model, batch_sample['pcm'], dev, _features_from_pcm)
   elif 'packed' in batch_sample:   # batches staged on the GPU ahead of the step (sepkern.data.Prefetcher)
-    mix, sources, pk = batch_sample['packed']
+    (mix, sources, pk), net_in = batch_sample['packed'], _staged_net_in(model, batch_sample)
   else:
+    if getattr(model, 'ipd_channels', ()):
+      raise ValueError(IPD_NO_NPZ)
     mix, pk = _to_packed(batch_sample['mix'], dev)
     sources = [_to_packed(batch_sample['source' + str(i + 1)], dev)[0] for i in range(model.num_spk)]
+    net_in = None
   if kind in DPCL_LOSSES:          # the same front ends: magnitudes of the mixture and the sources
-    return compute_loss_dpcl(model, mix, sources, pk)
-  return compute_loss_packed(model, mix, sources[:model.num_spk], pk, plotdir)
+    return compute_loss_dpcl(model, mix, sources, pk, net_in=net_in)
+  return compute_loss_packed(model, mix, sources[:model.num_spk], pk, plotdir, net_in=net_in)
 
 
 def estimate_masks(model, batch_sample):
   """The arithmetic half of compute_masks: [(file name, {'s1': (257,T_i) float32, ...}), ...] for one batch, without
   touching the disk (steps/eval_qsub.py overlaps the zlib compression of one batch with the next batch's GPU work)."""
+  if getattr(model, 'ipd_channels', ()):
+    raise ValueError(IPD_NO_NPZ)
   dev = model.lin.weight.device
   mix, pk = _to_packed(batch_sample['mix'], dev)
   name = batch_sample['name']

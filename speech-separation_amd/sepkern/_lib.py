@@ -96,6 +96,8 @@ PROTOTYPES = {
     "sk_dpcl_kmeans_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "sk_dpcl_kmeans": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _p, _i, _p, _p, _p, _p]),
     "sk_stft_psa": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _i64, _p, _i, _i, _p]),
+    "sk_stft_ipd": (_i, [_p, _i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _i, _i, _p]),
+    "sk_ipd_rows": (_i, [_p, _i64, _i64, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p]),
     "sk_rsh_workspace_bytes": (_sz, [_i, _i, _i]),
     "sk_rsh_loss_fwd": (_i, [_p, _p, _i, C.POINTER(_p), _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "sk_rsh_loss_bwd": (_i, [_p, _p, _i, C.POINTER(_p), _p, _p, _i, _i, _i, _i, _p, _p]),

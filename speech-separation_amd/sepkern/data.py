@@ -61,6 +61,14 @@ def _at_target_rate(pcm, flat):
   return out, outs[:len(ns)]
 
 
+def signal_keys(keys):
+  """'mix' and 'source<N>' of a batch's keys: what the front ends below transform.  An array batch (WavTrainSet with
+  ipd_channels) carries the mixture's other channels behind them as 'chan<c>'; the front ends' results for it are bit for bit
+  those of the mono batch of the reference channel, and ipd_rows_from_pcm makes the network's wide input rows."""
+  from .ipd import signal_keys as pick
+  return pick(keys)
+
+
 def mixed_pcm(pcm, dev):
   """A DynMixCollator batch -- pcm carries 'mixing' = {'amp': [S][B], 'peak': [B], 'quantize'} and the int16 samples of the
   SOURCES only, keys 'source1' .. 'source<S>', no 'mix' -- mixed on the device (ops.dynamic_mix: one sk_dynamic_mix launch;
@@ -128,7 +136,7 @@ def features_from_pcm(pcm, dev):
   B, F = len(ns), 257
   pk = Packing.from_lens([1 + n // 128 for n in ns], dev)
   feats, at, total = [], 0, sum(ns)
-  for _ in pcm['keys']:
+  for _ in signal_keys(pcm['keys']):                   # ('chan<c>' keys of an array batch are the IPD front end's, below)
     out = torch.zeros(pk.T, B, F, device=dev)
     ops.stft_batch(flat[at:at + total], lengths=ns, out=out, out_offs=[b * F for b in range(B)],
                    stride_t=[B * F] * B, stride_f=[1] * B)
@@ -165,7 +173,7 @@ def wave_features_from_pcm(pcm, dev, source_mags=True):
   starts = [sum(ns[:j]) for j in range(B)]
   grid = dict(lengths=ns, out_offs=[b * F for b in range(B)], stride_t=[B * F] * B, stride_f=[1] * B)
   feats = []
-  for q, _ in enumerate(pcm['keys'] if source_mags else pcm['keys'][:1]):
+  for q, _ in enumerate(signal_keys(pcm['keys']) if source_mags else pcm['keys'][:1]):
     out = torch.zeros(pk.T, B, F, device=dev)
     ops.stft_batch(flat[q * total:(q + 1) * total], out=out, **grid)
     feats.append(pk.pack(out))
@@ -199,7 +207,7 @@ def psa_features_from_pcm(pcm, dev, clamp=False):
     flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
   src = flat
   flat, ns = _at_target_rate(pcm, flat)                # (another tensor only when a signal had to be resampled)
-  nk, total = len(pcm['keys']), sum(ns)
+  nk, total = len(signal_keys(pcm['keys'])), sum(ns)
   if nk < 2:
     raise ValueError("psa_features_from_pcm: the batch holds no source waveform")
   pk = Packing.from_lens([1 + n // 128 for n in ns], dev)
@@ -210,6 +218,37 @@ def psa_features_from_pcm(pcm, dev, clamp=False):
   src.record_stream(torch.cuda.current_stream(dev))
   flat.record_stream(torch.cuda.current_stream(dev))
   return mix, targets, pk
+
+
+def ipd_rows_from_pcm(pcm, dev, front=features_from_pcm, **front_args):
+  """An array batch (WavTrainSet with ipd_channels: pcm['keys'] ends in 'chan<c>' keys, the mixture's listed channels) ->
+  (what `front` -- one of the front ends above -- returns for it, wide): wide (Rp, ld) = the input rows of an IPD model,
+  [ |Y_ref| | cos_1 | sin_1 | ... ] (sepkern/ipd.py) with the listed channels in the order of the batch's keys, made from
+  the PCM by ONE sk_stft_ipd launch; ld = the width rounded up to 16, zero columns behind the features, rows R.. zero: the
+  engine takes them as they are.  The samples cross to the device and are resampled (a batch with 'rate' / 'target_rate') once,
+  for both.  `front` sees what it sees for the mono batch of the reference channel, so its mixture rows -- which the loss
+  kernels read -- are bit for bit the magnitude columns of wide.  Everything is enqueued on the CURRENT stream."""
+  import torch
+  from . import ops
+  from .ipd import chan_keys
+  if 'mixing' in pcm:
+    raise ValueError("ipd_rows_from_pcm: a batch mixed on the device (--dynamic-mix) has one channel")
+  keys = list(pcm['keys'])
+  chans = chan_keys(keys)
+  if not chans or keys[0] != 'mix':
+    raise ValueError("ipd_rows_from_pcm: the batch holds no 'chan<c>' signals behind 'mix' (got %r)" % keys)
+  flat = pcm['flat']
+  if flat.device != torch.device(dev):
+    flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
+  src = flat
+  flat, ns = _at_target_rate(pcm, flat)
+  res = front({'flat': flat, 'keys': keys, 'lens': ns}, dev, **front_args)
+  pk, total = res[2], sum(ns)
+  starts = [sum(ns[:j]) for j in range(len(ns))]
+  wide, _ = ops.stft_ipd(flat, [[keys.index(k) * total + st for st in starts] for k in ['mix'] + chans], ns, pk=pk, want_mix=False)
+  src.record_stream(torch.cuda.current_stream(dev))
+  flat.record_stream(torch.cuda.current_stream(dev))
+  return res, wide
 
 
 # ----------------------------------------------------------------------------------------------- staging ahead of the step
@@ -337,6 +376,9 @@ class Prefetcher:
     if w is not None:
       yield w['mixc']
       yield w['flat']
+    x = staged.get('ipd') if isinstance(staged, dict) else None
+    if x is not None:
+      yield x
 
   @staticmethod
   def _targets_kind(targets):
@@ -349,7 +391,9 @@ class Prefetcher:
     """One batch -> {'packed': (mix (R,F), [source (R,F)...], Packing), <other keys unchanged>} on `dev`, enqueued on the
     CURRENT stream.  keep_wave: a PCM batch also gets 'wave' (wave_features_from_pcm; no source magnitudes); a batch that
     holds no PCM cannot, which is an error here rather than at the loss.  targets ('psa' / 'tpsa'): a PCM batch's 'packed' holds
-    phase-sensitive targets in place of the source magnitudes (psa_features_from_pcm); a batch without PCM is again an error."""
+    phase-sensitive targets in place of the source magnitudes (psa_features_from_pcm); a batch without PCM is again an error.
+    An array batch (its PCM carries 'chan<c>' signals: WavTrainSet with ipd_channels) also gets 'ipd' -- the wide input rows of
+    an IPD model (ipd_rows_from_pcm) -- and 'ipd_keys', the channels they were made of, in order."""
     import torch
     from torch.nn.utils.rnn import PackedSequence
     from .packing import Packing
@@ -361,12 +405,21 @@ class Prefetcher:
       host = pcm['flat'] if pcm['flat'].is_pinned() else pcm['flat'].pin_memory()
       out = {k: v for k, v in batch.items() if k != 'pcm'}
       if keep_wave:
-        mix, sources, pk, out['wave'] = wave_features_from_pcm(dict(pcm, flat=host), dev, source_mags=False)
+        front, front_args = wave_features_from_pcm, dict(source_mags=False)
       elif targets:
-        mix, sources, pk = psa_features_from_pcm(dict(pcm, flat=host), dev, clamp=targets == 'tpsa')
+        front, front_args = psa_features_from_pcm, dict(clamp=targets == 'tpsa')
         out['targets'] = targets         # (says what 'packed' holds in place of the source magnitudes)
       else:
-        mix, sources, pk = features_from_pcm(dict(pcm, flat=host), dev)
+        front, front_args = features_from_pcm, {}
+      from .ipd import chan_keys
+      if chan_keys(pcm['keys']):         # an array batch: the IPD model's wide input rows are made here too
+        res, out['ipd'] = ipd_rows_from_pcm(dict(pcm, flat=host), dev, front, **front_args)
+        out['ipd_keys'] = chan_keys(pcm['keys'])
+      else:
+        res = front(dict(pcm, flat=host), dev, **front_args)
+      mix, sources, pk = res[:3]
+      if keep_wave:
+        out['wave'] = res[3]
       out['packed'] = (mix, sources, pk)
       out['_keepalive'] = host
       return out

@@ -473,7 +473,9 @@ class Engine:
         """x2d (>= R, in_dim) packed rows of the batch `pk` (sepkern.packing.Packing), h0/c0 (2L,B,H) in sorted order ->
         (mask (R, out_dim) packed, hn, cn (2L,B,H) or None, ctx or None).  ctx feeds backward(); several may be alive
         (the RSH arch runs the network num_spk times per batch)."""
-        if x2d.dim() != 2 or x2d.shape[1] != self.I or x2d.shape[0] < pk.R:
+        # (also taken: rows already as wide as layer 0 reads them, in_dim rounded up to 16 with ZERO columns behind in_dim --
+        # sk_stft_ipd / sk_ipd_rows write them so; with R == Rp layer 0 then skips its sk_pad_rows pass)
+        if x2d.dim() != 2 or x2d.shape[1] not in (self.I, ops.pad_to(self.I, 16)) or x2d.shape[0] < pk.R:
             raise SepkernError("forward: input is %s, expected (>= %d, %d) packed rows" % (tuple(x2d.shape), pk.R, self.I))
         L, dev = self.L, x2d.device
         main = torch.cuda.current_stream(dev)

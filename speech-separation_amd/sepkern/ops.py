@@ -1300,6 +1300,110 @@ def stft_psa(flat, sig_offs, nsamp, S, pk=None, clamp=False, out=None, repeat=1)
     return mix, [tgt[s] for s in range(S)]
 
 
+# ----------------------------------------------------------------------------- inter-channel phase features (ipd_channels)
+def stft_ipd(flat, sig_offs, nsamp, pk=None, out=None, want_mix=True, ws=None, repeat=1):
+    """The input rows of an IPD model from a batch of array waveforms in one launch (sk_stft_ipd; sepkern/ipd.py defines the
+    arithmetic).  flat: ONE 1-D CUDA tensor holding every signal, float32 or int16 PCM (scaled by 1/32768 in-kernel); sig_offs:
+    1 + P lists (the reference channel's, then listed channel 1 .. P) of B offsets into flat; nsamp: samples per utterance.
+    -> (rows (>= R, ld), mix (>= R, 257) or None): rows = [ |Y_r| | cos_1 | sin_1 | ... ] of width 257 (1 + 2P) in a buffer whose
+    row stride ld is that width rounded up to 16, the columns in between zero -- the engine takes it as it is; mix = a contiguous
+    copy of the magnitude columns (want_mix), which the loss kernels read.
+    With pk (the batch's Packing, length-sorted: no perm) both are packed rows (Rp, .), rows R.. zero; without it, utterance u is
+    the block of T_u = 1 + nsamp[u] // 128 rows that starts at row sum_{v<u} T_v.
+    out = (rows (>= R, ld >= width) float32 with unit column stride, mix (>= R, 257) contiguous or None) is written in place.
+    ws: the work rows, a float32 tensor of at least R * 257 * 2 elements (default: allocated here)."""
+    from . import ipd as _ipd
+    pcm16 = flat.dtype == torch.int16
+    _chk(flat, torch.int16 if pcm16 else torch.float32)
+    ns = [int(n) for n in nsamp]
+    B, F, dev = len(ns), 257, flat.device
+    sig_offs = [[int(o) for o in offs] for offs in sig_offs]
+    P = len(sig_offs) - 1
+    if flat.dim() != 1 or not flat.is_contiguous() or B == 0:
+        raise _lib.SepkernError("stft_ipd needs one contiguous 1-D tensor of samples and at least one utterance")
+    if not 1 <= P <= _ipd.MAX_PAIRS or any(len(o) != B for o in sig_offs):
+        raise _lib.SepkernError("stft_ipd needs 1 + P lists (P in 1..%d) of %d signal offsets, the reference channel first" % (_ipd.MAX_PAIRS, B))
+    if any(o < 0 or o + n > flat.numel() for offs in sig_offs for o, n in zip(offs, ns)):
+        raise _lib.SepkernError("stft_ipd: a signal runs past the sample buffer")
+    Ts = [1 + n // 128 for n in ns]
+    width = _ipd.in_dim(P)
+    if pk is not None:
+        if pk.perm is not None:
+            raise _lib.SepkernError("stft_ipd needs a length-sorted batch (Packing without perm)")
+        if pk.B != B or [int(t) for t in pk.lens_host] != Ts:
+            raise _lib.SepkernError("stft_ipd: the Packing's frame counts are not those of the signals")
+        nrows, rows_p, bases = pk.R, pk.Rp, None
+    else:
+        bases, nrows = [], 0
+        for T in Ts:
+            bases.append(nrows)
+            nrows += T
+        rows_p = nrows
+    if out is None:
+        rows = torch.empty(rows_p, _ipd.padded_dim(P), dtype=torch.float32, device=dev)
+        mix = torch.empty(rows_p, F, dtype=torch.float32, device=dev) if want_mix else None
+        if rows_p > nrows:
+            rows[nrows:].zero_()
+            if mix is not None:
+                mix[nrows:].zero_()
+    else:
+        rows, mix = out
+    _chk(rows)
+    _chk(mix)
+    if rows.dim() != 2 or rows.stride(1) != 1 or rows.shape[0] < nrows or rows.shape[1] < width:
+        raise _lib.SepkernError("stft_ipd: rows must be (>= %d, >= %d) float32 with unit column stride" % (nrows, width))
+    if mix is not None and (mix.dim() != 2 or tuple(mix.shape[1:]) != (F,) or mix.shape[0] < nrows or not mix.is_contiguous()):
+        raise _lib.SepkernError("stft_ipd: mix must be a contiguous (>= %d, 257) float32 tensor" % nrows)
+    ld = int(rows.stride(0)) if rows.shape[0] > 1 else int(rows.shape[1])
+    if ws is None:
+        ws = torch.empty(nrows * F, 2, dtype=torch.float32, device=dev)  # the reference's complex bins on their way to the contractions
+    _chk(ws)
+    if not ws.is_contiguous() or ws.numel() < nrows * F * 2:
+        raise _lib.SepkernError("stft_ipd: ws must be a contiguous float32 tensor of at least %d elements" % (nrows * F * 2))
+    # descriptor arrays must outlive the (asynchronous) launch call: keep references until it returns
+    d64 = _i64([o for offs in sig_offs for o in offs] + (bases or []), dev)
+    d_ns = torch.tensor(ns, dtype=torch.int32, device=dev)
+    # algorithmic bytes per frame: 128 new samples of each of the 1 + P signals in; 257 (1 + 2P) features (+ 257 of mix) out
+    nbytes = (1 + P) * 128 * (2 if pcm16 else 4) + (width + (F if mix is not None else 0)) * 4
+    with _timed("stft_ipd_kernel", repeat * float(sum(Ts)) * nbytes):
+        for _ in range(repeat):
+            _lib.call("sk_stft_ipd", _ptr(flat), int(pcm16), _ptr(d64), _ptr(d_ns), B, 1 + P, 512, 128,
+                      _ptr(pk.offs) if pk is not None else None, _ptr(d64[(1 + P) * B:]) if pk is None else None,
+                      _ptr(rows), ld, _ptr(mix), _ptr(ws), min(ns), max(Ts), _stream())
+    return rows, mix
+
+
+def ipd_rows(Y, ref, channels, mag, out=None, repeat=1):
+    """The input rows of an IPD model from spectra in memory (sk_ipd_rows; sepkern/ipd.py).  Y (C, T, 257) complex64 with unit bin
+    stride (any channel / row stride), ref: the reference channel, channels: the listed ones; mag (T, >= 257) float32: the
+    reference channel's magnitude rows as the caller holds them, copied into columns 0..256 unchanged.
+    -> rows (T, ld) float32, ld = 257 (1 + 2P) rounded up to 16, the columns behind the features zero.  out (T, >= width) with
+    unit column stride is written in place."""
+    from . import ipd as _ipd
+    _chk(Y, torch.complex64)
+    _chk(mag)
+    channels = [int(c) for c in channels]
+    if Y.dim() != 3 or Y.shape[2] != 257 or Y.stride(2) != 1:
+        raise _lib.SepkernError("ipd_rows: Y must be (C, T, 257) complex64 with unit bin stride")
+    nch, T, P = int(Y.shape[0]), int(Y.shape[1]), len(channels)
+    if mag.dim() != 2 or mag.shape[0] != T or mag.shape[1] < 257 or mag.stride(1) != 1:
+        raise _lib.SepkernError("ipd_rows: mag must be (T, >= 257) float32 rows of the %d frames" % T)
+    if out is None:
+        out = torch.empty(T, _ipd.padded_dim(P) if 1 <= P <= _ipd.MAX_PAIRS else 257, dtype=torch.float32, device=Y.device)
+    _chk(out)
+    if out.dim() != 2 or out.shape[0] != T or out.stride(1) != 1:
+        raise _lib.SepkernError("ipd_rows: out must be (T, >= 257 (1 + 2P)) float32 with unit column stride")
+    chans = (C.c_int32 * max(P, 1))(*channels)          # (host array: the entry point checks and copies it before it returns)
+    ld = int(out.stride(0)) if T > 1 else int(out.shape[1])
+    ld_mag = int(mag.stride(0)) if T > 1 else int(mag.shape[1])
+    # algorithmic bytes per frame: the 1 + P channels' complex bins and the magnitude row in, the feature row out
+    with _timed("ipd_rows_kernel", repeat * float(T) * 257 * ((1 + P) * 8 + 4 + (1 + 2 * P) * 4)):
+        for _ in range(repeat):
+            _lib.call("sk_ipd_rows", _ptr(Y), int(Y.stride(0)), int(Y.stride(1)) if T > 1 else 257, T, nch, int(ref), chans, P,
+                      _ptr(mag), ld_mag, _ptr(out), ld, _stream())
+    return out
+
+
 # ----------------------------------------------------------------------------- RSH loss / attention
 def rsh_loss_fwd(mask, x, srcs, lens, used):
     """One greedy-assignment pass.  mask (T,B,F), x (T,B,2F) [mixture | attention], srcs list of S (T,B,F),

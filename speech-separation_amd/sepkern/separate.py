@@ -23,7 +23,7 @@ WORKING_RATE = 8000      # Hz: the rate the recipe's data (wav8k) and therefore 
 
 
 def window_masks(model, mag, window_frames, hop_frames, batch_windows):
-    """The network on every window of mag (T, 257): -> [(tensor, offset, row stride)] per window, the descriptors ops.stitch
+    """The network on every window of mag (T, 257) -- or of an IPD model's wider input rows (T, ld), ops.ipd_rows --: -> [(tensor, offset, row stride)] per window, the descriptors ops.stitch
     takes.  Full windows go in uniform batches of up to batch_windows (window j of a batch of B is offset j * ld, stride B * ld
     of its packed output); a short last window runs as a batch of its own."""
     T, dev = int(mag.shape[0]), mag.device
@@ -95,6 +95,7 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
     before."""
     if not hasattr(model, "forward_packed"):
         raise SepkernError("separate_recording needs a model with forward_packed (the uPIT arch)")
+    ipd_chans = [int(c) for c in getattr(model, "ipd_channels", ())]
     st.check_geometry(1, window_frames, hop_frames)
     if batch_windows < 1:
         raise ValueError("separate_recording: batch_windows = %d, at least 1 expected" % batch_windows)
@@ -114,6 +115,17 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
             raise ValueError("separate_recording: cacgmm needs a (C, n) pcm and mvdr or wpd")
         cg.check_arguments(int(pcm.shape[0]), int(model.num_spk), 1, int(cacgmm_iterations), int(cacgmm_block_frames),
                            int(cacgmm_context_frames), float(cacgmm_loading))
+    if ipd_chans:
+        if pcm.dim() != 2:
+            raise ValueError("separate_recording: the model has ipd_channels = %s and needs a (C, n) pcm, the array it was trained "
+                             "on" % ",".join(str(c) for c in ipd_chans))
+        if int(ref_channel) != int(model.ipd_ref):
+            raise ValueError("separate_recording: ref_channel = %d, but the model was trained with ipd_ref = %d: its masks belong "
+                             "to that channel" % (int(ref_channel), int(model.ipd_ref)))
+        if max(ipd_chans + [int(model.ipd_ref)]) >= int(pcm.shape[0]):
+            raise ValueError("separate_recording: the recording has %d channels, the model's ipd_ref = %d and ipd_channels = %s "
+                             "need channel %d" % (int(pcm.shape[0]), int(model.ipd_ref), ",".join(str(c) for c in ipd_chans),
+                                                  max(ipd_chans + [int(model.ipd_ref)])))
     pcm = pcm.to(dev, non_blocking=True)
     if wpe:
         wp.check_arguments(int(pcm.shape[0]) if pcm.dim() == 2 else 1, 1, int(wpe_taps), int(wpe_delay), int(wpe_iterations),
@@ -123,7 +135,7 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
         C, n = int(pcm.shape[0]), int(pcm.shape[1])
         if mvdr:
             mv.check_arguments(C, int(model.num_spk), 1, int(mvdr_block_frames), int(mvdr_context_blocks), int(ref_channel), float(mvdr_loading))
-        elif not (wpe or wpd):
+        elif not (wpe or wpd or ipd_chans):
             raise ValueError("separate_recording: a (C, n) pcm needs mvdr or wpe")
         flat = pcm.contiguous().view(-1)
         if int(sample_rate) != int(working_rate):           # all channels in one call
@@ -159,13 +171,18 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
     ramp = torch.from_numpy(st.default_ramp(O)).to(dev) if ramp is None else torch.as_tensor(ramp, dtype=torch.float32).to(dev).contiguous()
     was_training = model.training
     model.eval()
+    # an IPD model reads [ |ref| | cos, sin of every listed channel against ref ] (sepkern/ipd.py) of the spectra the masks will be
+    # applied to -- X after wpe --, the magnitude columns being `mag` itself; stitching and everything behind it keep reading mag
+    net_rows = ops.ipd_rows(Y if X is None else X, int(ref_channel), ipd_chans, mag) if ipd_chans else mag
     try:
         with torch.no_grad():
-            windows = window_masks(model, mag, window_frames, hop_frames, batch_windows)
+            windows = window_masks(model, net_rows, window_frames, hop_frames, batch_windows)
     finally:
         model.train(was_training)
     stitched, perms, cost = ops.stitch(mag, windows, T, window_frames, hop_frames, S, ramp)
     details = dict(masks=windows, stitched=stitched, perms=perms, cost=cost, mag=mag, mixc=mixc)
+    if ipd_chans:
+        details.update(net_rows=net_rows)
     if X is not None:
         details.update(X=X, Y=Yw)
     if wpd:

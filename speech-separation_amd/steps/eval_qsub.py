@@ -72,6 +72,17 @@ def restore_model(m, args, gpu):
   return model
 
 
+def refuse_ipd_model(m, args):
+  """A model conf with ipd_channels (archs/uPIT.py, sepkern/ipd.py) sees an array; the npz features this script reads hold one
+  channel's magnitudes.  Ends the run before anything is loaded, with a pointer to steps/separate_wav.py."""
+  if not hasattr(m, "ipd_conf") or not args.model_config:
+    return
+  with open(args.model_config) as f:
+    conf = dict(line.rstrip().split('=', 1) for line in f if '=' in line)
+  if m.ipd_conf(conf)[1]:
+    raise SystemExit(m.IPD_NO_NPZ)
+
+
 def write_masks(dirout, name, arrays):
   np.savez_compressed(os.path.join(dirout, name), **arrays)
 
@@ -85,6 +96,7 @@ def main(argv=None):
   from sepkern.data import host_threads
   host_threads()
   m = load_arch(args.arch_file)
+  refuse_ipd_model(m, args)
   if rank == 0:
     print("mask generation with", args.arch_file, "on", world, "GPU(s)")
 

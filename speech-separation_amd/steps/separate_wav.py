@@ -25,6 +25,11 @@ beamformers (sk_cacgmm, sepkern/cacgmm.py: a cACGMM spatial mixture model with t
 --wpd (instead of --mvdr, multi-channel recordings only) beamforms with one WPD convolutional beamformer per stream (sk_wpd,
 sepkern/wpd.py: dereverberation, separation and denoising in one filter over the present frame and the channels' past).  With
 --wpe the network still sees the dereverberated reference channel, and the WPD beamformers the recording as it is.
+
+A model trained with the conf key ipd_channels (sepkern/ipd.py) sees the array itself: besides the magnitudes of its reference
+channel ipd_ref, the phase differences of the listed channels against it (sk_ipd_rows; after --wpe those of the dereverberated
+spectra).  It takes multi-channel recordings with or without a beamformer -- without one the masks are applied to the
+reference channel --, --ref-channel must be its ipd_ref, and a recording must have every listed channel.
 """
 import argparse
 import concurrent.futures
@@ -117,6 +122,11 @@ def main(argv=None):
   torch.cuda.set_device(args.gpu_id)
   host_threads()
   model = eval_qsub.restore_model(m, args, args.gpu_id)
+  ipd = bool(getattr(model, "ipd_channels", ()))
+  if ipd and args.ref_channel != model.ipd_ref:
+    print("separate_wav: --ref-channel %d, but the model was trained with ipd_ref = %d: its masks belong to that channel"
+          % (args.ref_channel, model.ipd_ref), file=sys.stderr)
+    return 1
 
   def read_scp(scp):
     out = []
@@ -142,7 +152,7 @@ def main(argv=None):
     rates, chans = [], []
     for path in paths:
       fs, x = scipy.io.wavfile.read(path)
-      if x.dtype.name != 'int16' or x.ndim > 2 or (x.ndim == 2 and not (args.mvdr or args.wpe or args.wpd)):
+      if x.dtype.name != 'int16' or x.ndim > 2 or (x.ndim == 2 and not (args.mvdr or args.wpe or args.wpd or ipd)):
         raise ValueError("%s: only mono 16-bit PCM wav is supported" % path)
       rates.append(int(fs))
       chans += [x] if x.ndim == 1 else [x[:, c] for c in range(x.shape[1])]
@@ -167,7 +177,7 @@ def main(argv=None):
       _, pcm16 = separate_recording(model, pcm, rate, args.window_frames, args.hop_frames, args.batch_windows,
                                     working_rate=args.sample_rate, want_float=False, want_pcm=True, ref_channel=args.ref_channel,
                                     mvdr_block_frames=args.mvdr_block_frames, mvdr_context_blocks=args.mvdr_context_blocks,
-                                    mvdr_loading=args.mvdr_loading, mvdr_postmask=args.mvdr_postmask, mvdr=args.mvdr or not (args.wpe or args.wpd),
+                                    mvdr_loading=args.mvdr_loading, mvdr_postmask=args.mvdr_postmask, mvdr=args.mvdr or not (args.wpe or args.wpd or ipd),
                                     wpe=args.wpe, wpe_taps=args.wpe_taps, wpe_delay=args.wpe_delay, wpe_iterations=args.wpe_iterations,
                                     wpe_block_frames=args.wpe_block_frames, wpe_context_frames=args.wpe_context_frames,
                                     wpe_loading=args.wpe_loading, cacgmm=args.cacgmm, cacgmm_iterations=args.cacgmm_iterations,

@@ -248,12 +248,41 @@ def prefetch_targets(m, args):
   return kind
 
 
+def ipd_model(m, args):
+  """{'ipd_ref': r, 'ipd_channels': (c, ...)} when the conf file makes it an IPD model (archs/uPIT.py conf key ipd_channels,
+  sepkern/ipd.py: the network also sees the phase differences between the channels of an array), else {}.  Such a model trains
+  on multi-channel wav files: without --wav-input, with --dynamic-mix (its mixtures have one channel) or with loss=mixit the
+  run ends here, not at its first batch."""
+  if not hasattr(m, "ipd_conf"):
+    return {}
+  conf = read_model_conf(args.model_config)
+  try:
+    ref, chans = m.ipd_conf(conf, m.parse_loss(conf.get('loss', 'mse')))
+  except ValueError as e:
+    raise SystemExit(str(e))
+  if not chans:
+    return {}
+  if not args.wav_input:
+    raise SystemExit(m.IPD_NEEDS_WAVEFORMS)
+  if getattr(args, "dynamic_mix", False):
+    raise SystemExit(m.IPD_NO_DYNAMIC_MIX)
+  return {"ipd_ref": ref, "ipd_channels": chans}
+
+
 # ----------------------------------------------------------------------------------------------- data
 def wav_train_set(m, args, data_dir):
-  """The arch's WavTrainSet over data_dir; --sample-rate is handed on only when given (an arch without the argument keeps working)."""
-  if getattr(args, "sample_rate", None) is None:
-    return m.WavTrainSet(data_dir)
-  return m.WavTrainSet(data_dir, sample_rate=args.sample_rate)
+  """The arch's WavTrainSet over data_dir; --sample-rate and an IPD model's channels (ipd_model) are handed on only when given
+  (an arch without the arguments keeps working).  A set whose files do not fit the model -- mono files for an IPD model, array
+  files for any other -- is refused by the arch here, when it is built."""
+  extra = dict(getattr(args, "ipd", None) or {})
+  if getattr(args, "sample_rate", None) is not None:
+    extra["sample_rate"] = args.sample_rate
+  try:
+    return m.WavTrainSet(data_dir, **extra)
+  except ValueError as e:
+    if not extra.get("ipd_channels") and "ipd_channels" not in str(e):
+      raise
+    raise SystemExit(str(e))
 
 
 def mixing_seed(args, rank, world):
@@ -558,6 +587,7 @@ def main(argv=None):
   m = __import__(args.arch_file)
   args.keep_wave = waveform_loss(m, args)        # (the prefetcher then carries the waveforms with the staged batch)
   args.prefetch_targets = prefetch_targets(m, args)     # (... or stages phase-sensitive targets in place of the source magnitudes)
+  args.ipd = ipd_model(m, args)                  # (an IPD model's channels: the loader ships them, the prefetcher stages the wide rows)
   torch.cuda.set_device(gpu)
   from sepkern.data import host_threads
   host_threads()                                 # (the arithmetic is on the GPU; see sepkern.data.host_threads)
