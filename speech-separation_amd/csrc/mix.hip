@@ -15,6 +15,10 @@
 // second and third reads of the samples (at most a few hundred KB per mixture) come from L2.  A launch lasts as long as its
 // longest mixture takes on one CU -- three dependent passes through that CU's memory pipeline --, not as long as HBM would need:
 // 37 us for 32 two-source mixtures of up to 64 000 samples, 52 us for 100 (profiles/dynamic_mix.txt).
+//
+// Shape coverage: tests/test_gpu_wave_cases.py runs dynamic_mix_kernel<1..4, int16 | float32> at 1, 63 | 64, 1023 | 1024 | 1025,
+// 4095 | 4096 | 4097 and 8191 | 8192 | 8193 samples, with the maximum alone in the last trip, on and below the silence threshold,
+// all silent, and with a clipping quantize, against fp64 (tests/_wave_cases.py names the edge each case is there for).
 #include "sk_common.h"
 
 namespace {

@@ -6,6 +6,9 @@
 //   P_n = sum x_n^2,  c_nk = sum x_n e_k,  G_kl = sum e_k e_l (k <= l)        (NQ = 2 + 2 M + M (M + 1) / 2 values)
 // in fp64, on the sums skeleton of wave_loss.h (which states the order of operations), as sisdr.hip forms its sums.  The
 // error of every one of the 2^M assignments follows from these sums alone.
+//
+// Shape coverage: tests/test_gpu_wave_cases.py runs mixit_sums_kernel<2..4> and the finalize kernel at the lengths and batch
+// sizes named under sisdr.hip, at tau = 0, 1e-3 and 1, with both references silent, an exact partition and exact ties, against fp64.
 #include "wave_loss.h"
 
 #include <math.h>
@@ -125,7 +128,8 @@ extern "C" int sk_mixit_fwd(const float* est, const int64_t* est_offs, const voi
   SK_CHECK_ARG(M >= 2 && M <= MAXM, "sk_mixit_fwd: %d estimates per utterance, outside 2..%d", M, MAXM);
   SK_CHECK_ARG(est && est_offs && ref && ref_offs && nsamp && assign_score && best_code && out && coef && ws,
                "sk_mixit_fwd: null pointer");
-  SK_CHECK_ARG(B > 0 && B <= 65535 && max_samples > 0, "sk_mixit_fwd: bad sizes");
+  SK_CHECK_ARG(B > 0 && B <= 65535, "sk_mixit_fwd: B = %d utterances outside 1..65535", B);
+  SK_CHECK_ARG(max_samples > 0, "sk_mixit_fwd: max_samples = %d, at least 1 expected", max_samples);
   SK_CHECK_ARG(tau >= 0.0 && tau <= 1.0, "sk_mixit_fwd: tau %g outside 0..1", tau);
   const int nch = (int)sk_cdiv(max_samples, CHUNK);
   double* partial = (double*)ws;

@@ -5,6 +5,10 @@
 // One streaming pass reads every estimate and every reference sample once and forms, per utterance, the plain sums
 //   sum e_k, sum r_i, sum e_k^2, sum r_i^2, sum e_k r_i        (4 S + S^2 values)
 // in fp64, on the sums skeleton of wave_loss.h (which states the order of operations).
+//
+// Shape coverage: tests/test_gpu_wave_cases.py runs sisdr_sums_kernel<1..4> and the finalize kernel at 1, 2, 255 | 256 | 257,
+// 4095 | 4096 | 4097, 8192 | 8193 and 12289 samples, at B * NQ and B either side of 256, and on every zero-coefficient branch and
+// exact tie, against fp64 (tests/_wave_cases.py names the edge each case is there for).
 #include "wave_loss.h"
 
 #include <math.h>
@@ -149,7 +153,8 @@ extern "C" int sk_sisdr_pit_fwd(const float* est, const int64_t* est_offs, const
   SK_CHECK_ARG(S >= 1 && S <= MAXS, "sk_sisdr_pit_fwd: num_spk %d outside 1..%d", S, MAXS);
   SK_CHECK_ARG(est && est_offs && ref && ref_offs && nsamp && pair && perm_score && best_perm && out && coef && ws,
                "sk_sisdr_pit_fwd: null pointer");
-  SK_CHECK_ARG(B > 0 && B <= 65535 && max_samples > 0, "sk_sisdr_pit_fwd: bad sizes");
+  SK_CHECK_ARG(B > 0 && B <= 65535, "sk_sisdr_pit_fwd: B = %d utterances outside 1..65535", B);
+  SK_CHECK_ARG(max_samples > 0, "sk_sisdr_pit_fwd: max_samples = %d, at least 1 expected", max_samples);
   const int nch = (int)sk_cdiv(max_samples, CHUNK);
   double* partial = (double*)ws;
   double* best_score = (double*)((char*)ws + partial_bytes(B, nq_of(S), max_samples));

@@ -4,6 +4,10 @@
 // tree; the finalize kernel (one workgroup) adds an utterance's chunks in chunk order (gather_chunks), searches per utterance
 // (the loss's own code), and adds the best scores in utterance order (tally_scores).  No atomics; the chunk grid of an
 // utterance depends on its own length only, so each value has one order of operations whatever else is in the batch.
+//
+// Shape coverage: tests/test_gpu_wave_cases.py runs the skeleton through both losses -- a second trip of gather_chunks' stride
+// loop (B * NQ > 256), of the finalize loops and a tally over B = 257, grids with more chunks than any utterance has over a
+// workspace of exactly the queried size that holds NaN -- against fp64 (cases and the edges they claim: tests/_wave_cases.py).
 #pragma once
 #include "sk_common.h"
 
