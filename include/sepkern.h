@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 146
+#define SK_VERSION 147
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -122,6 +122,36 @@ size_t sk_fir_workspace_bytes(const int32_t* nsamp_host, const int32_t* ntaps_ho
 int sk_fir_convolve(const void* in, int pcm16, const int64_t* in_offs_host, const int32_t* nsamp_host, const float* rir,
                     const int64_t* rir_offs_host, const int32_t* ntaps_host, const int32_t* delay_host, int J, void* ws,
                     float* out, const int64_t* out_offs_host, sk_stream_t stream);
+
+/* ---------------------------------------------------------------- simulated rooms (array dynamic mixing)
+ * Image-method room impulse responses made on the device, J per call; sepkern/room.py defines the result (ism_rir) and
+ * restates the arithmetic in numpy (ism_rir_f32).  Job j: a rigid shoebox room[3j..] = (Lx, Ly, Lz) metres with the wall
+ * reflection coefficients beta[6j..] = (x0, x1, y0, y1, z0, z1), a source src[3j..] and a microphone mic[3j..], c = 343 m/s.
+ * Every image (p in {0,1}^3, m in Z^3) at R_a = (1 - 2 p_a) src_a + 2 m_a L_a - mic_a, d = |R|, tau = d rate / c adds
+ *   A 0.5 (1 + cos(2 pi t / 64)) sinc(t),  t = n - tau,  to the taps n = floor(tau) - 31 .. floor(tau) + 32 inside [0, ntaps[j]),
+ *   A = scale[j] prod_a beta_a0^|m_a - p_a| beta_a1^|m_a| / (4 pi d)                                               (0^0 = 1)
+ * and exactly ntaps[j] floats are written at rir + rir_offs[j].  Geometry (position, d, tau, A) in fp64, the taps in fp32.
+ * One workgroup per job builds the RIR in LDS, one private copy per wave, the images in an order fixed by the job's own
+ * arguments: no atomics, no hand-off between workgroups, and a job's bits depend neither on the batch around it nor on the run.
+ * The job arrays (names ending in _host) are HOST arrays, copied into the workspace on `stream`.  1 <= J <= 65535, 1 <= ntaps <=
+ * 8192, room dimensions > 0, 0 <= beta <= 1, source and microphone strictly inside the room and at least 0.01 m apart, rate >= 1,
+ * offsets >= 0, scale finite, at most 2^27 image positions to scan per job (8192 taps at 8 kHz in 2 x 2 x 2 m need 4.5e7).
+ * ws >= sk_room_workspace_bytes(...) (0 for arguments out of range).  Bad arguments return SK_EINVAL before anything is launched. */
+size_t sk_room_workspace_bytes(const double* room_host, const double* beta_host, const double* src_host, const double* mic_host,
+                               const double* scale_host, const int32_t* ntaps_host, const int64_t* rir_offs_host, int J, double rate);
+int sk_room_rirs(const double* room_host, const double* beta_host, const double* src_host, const double* mic_host,
+                 const double* scale_host, const int32_t* ntaps_host, const int64_t* rir_offs_host, int J, double rate, void* ws,
+                 float* rir, sk_stream_t stream);
+
+/* The other channels of B array mixtures at the gains sk_dynamic_mix returned for the reference channel.  Channel p (0 <= p < P) of
+ * mixture u: source s is the nsamp[u] float32 samples at in + in_offs[(s*P + p)*B + u], and
+ *   out[out_offs[p*B + u] + n] = fmaf(G_s, x_{s,p,u}[n], acc), s ascending from acc = 0, G_s = gains[s*B + u]
+ * -- sk_dynamic_mix's own chain: fed the reference channel's signals it reproduces that mixture bit for bit.  quantize != 0:
+ * the same clip(rint(32768 v), -32768, 32767) / 32768.  Levels and the peak are DEFINED on the reference channel: another
+ * channel may exceed `peak` (and, quantized, clip).  One writer per element; the descriptor arrays live on the device.
+ * 1 <= S <= 4, 1 <= P <= 7, 1 <= B <= 65535, nsamp[u] >= 1. */
+int sk_mix_channels(const float* in, const int64_t* in_offs, const int32_t* nsamp, int B, int S, int P, const float* gains,
+                    int quantize, float* out, const int64_t* out_offs, sk_stream_t stream);
 
 /* ---------------------------------------------------------------- mask-apply + iSTFT back end
  * Replaces np.multiply(mix_spec, mask) + librosa.core.istft(hop_length=128) + (*32767).astype(int16)

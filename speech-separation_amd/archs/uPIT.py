@@ -45,13 +45,17 @@ Beyond the reference (all optional, defaults reproduce it):
   * DynMixTrainSet / DynMixCollator (steps/train_qsub.py --dynamic-mix): training mixtures drawn afresh every epoch from
     single-speaker utterances and mixed on the GPU (sk_dynamic_mix); every loss above trains on them.  With rir_scp / rir_synth
     (--mix-rir-scp / --mix-rir-synth) every source is first convolved with a room impulse response, also on the GPU
-    (sk_fir_convolve; sepkern/reverb.py): reverberant mixtures, reverberant sources as targets.
+    (sk_fir_convolve; sepkern/reverb.py): reverberant mixtures, reverberant sources as targets.  With room_t60
+    (--mix-room-t60 [--mix-array FILE]) every mixture is made in a simulated shoebox room of its own: image-method RIRs from every
+    source to every microphone of the array, made on the GPU (sk_room_rirs; sepkern/room.py), and the listed channels' mixtures
+    at the reference channel's gains (sk_mix_channels) -- an array batch for an IPD model, or one microphone for any other.
   * conf keys ipd_channels (e.g. 1,2,3) and ipd_ref (0): an IPD model (sepkern/ipd.py).  The network's input is the magnitude
     of channel ipd_ref of an array recording followed by cos and sin of the phase difference of every listed channel against
     it, in_dim = 257 (1 + 2P); feat_dim, out_dim and the losses mse / psa / tpsa / dpcl / sisdr are what they are without.
     It trains on WavTrainSet(ipd_ref=, ipd_channels=) batches of multi-channel wav files (steps/train_qsub.py --wav-input hands
     the conf keys on): the mixture's listed channels travel as 'chan<c>' behind 'mix' and 'source<N>', and one sk_stft_ipd
-    launch makes the wide rows.  Not with loss=mixit, --dynamic-mix or npz features; steps/separate_wav.py separates with it.
+    launch makes the wide rows.  With --dynamic-mix it trains only in simulated rooms (--mix-room-t60 with --mix-array).  Not with
+    loss=mixit or npz features; steps/separate_wav.py separates with it.
 """
 import collections
 import itertools
@@ -79,6 +83,7 @@ from sepkern import ipd as _ipd
 from sepkern import ops
 from sepkern.data import features_from_pcm as _features_from_pcm, wave_features_from_pcm as _wave_features_from_pcm
 from sepkern.data import psa_features_from_pcm as _psa_features_from_pcm, ipd_rows_from_pcm as _ipd_rows_from_pcm
+from sepkern.data import batch_chan_keys as _batch_chan_keys
 from sepkern.collate import collate_sorted, eval_magnitudes, read_scp, stage_copies, train_sample
 from sepkern.model import SepDNNBase, UnpackFn, to_packed as _to_packed
 from sepkern.packing import Packing
@@ -303,10 +308,21 @@ class DynMixTrainSet(Dataset):
   probability rir_prob: a RIR drawn uniformly from rir_scp (lines `<rir-id> <path>` of mono 16-bit wav or 1-D float npy files at
   the working rate, read once, here), or synthesised with t60 ~ U(rir_synth) seconds and a direct-to-reverberant ratio ~
   U(rir_drr_db) dB; otherwise the identity [1.0].  These draws come from a generator of their own, seeded (seed, idx, 1): draw(idx)
-  and everything else an item carries are bit for bit what they are without reverberation."""
+  and everything else an item carries are bit for bit what they are without reverberation.
+
+  Simulated rooms (room_t60 = (lo, hi) seconds; sepkern/room.py): every mixture gets a shoebox room of its own -- dimensions uniform
+  in room_dims = (lo, hi), a NOMINAL t60 uniform in room_t60 that sets the walls' reflection coefficients (Eyring), the microphone
+  array `array` ((C, 3) offsets from its centre in metres; None: one microphone) somewhere in it at a random yaw, and the S
+  sources -- and the image-method RIRs from every source to every microphone are made ON THE GPU (sk_room_rirs) in front of the
+  convolution.  An item then carries 'room': the fp64 geometry {'L', 'beta', 'mics': the reference microphone ipd_ref followed
+  by those of ipd_channels (only they travel), 'srcs', 'ntaps' = min(round(t60 rate), 8192) at the rate the convolution runs
+  at, 'rate', 'chans'}.  With ipd_channels the mixed batch is an array batch ('chan<c>' behind the sources) for an IPD model.
+  These draws come from a generator of their own, seeded (seed, idx, 2): draw(idx) and every other key are bit for bit what they
+  are without a room.  Not together with rir_scp / rir_synth."""
 
   def __init__(self, datadir, num_spk, mixes_per_epoch=None, snr_db=2.5, peak=(0.9, 0.9), max_samples=0, seed=0, sample_rate=None,
-               quantize=False, rir_scp=None, rir_synth=None, rir_drr_db=(0.0, 15.0), rir_prob=1.0):
+               quantize=False, rir_scp=None, rir_synth=None, rir_drr_db=(0.0, 15.0), rir_prob=1.0,
+               room_t60=None, room_dims=((3, 3, 2.5), (8, 6, 4)), array=None, ipd_ref=0, ipd_channels=()):
     import wave
     self.num_spk, self.seed = int(num_spk), int(seed)
     self.snr_db, self.peak, self.max_samples = float(snr_db), (float(peak[0]), float(peak[1])), int(max_samples)
@@ -347,6 +363,46 @@ class DynMixTrainSet(Dataset):
     self.longest = max(n for u in self.speakers for _, n in u)
     self.collator = DynMixCollator(self.sample_rate, quantize)
     self._init_reverb(rir_scp, rir_synth, rir_drr_db, rir_prob)
+    self._init_room(room_t60, room_dims, array, ipd_ref, ipd_channels)
+
+  def _init_room(self, room_t60, room_dims, array, ipd_ref, ipd_channels):
+    from sepkern import room as _room
+    self.room_t60 = None
+    self.ipd_ref = _ipd.parse_ref(ipd_ref)
+    self.ipd_channels = _ipd.parse_channels(ipd_channels, self.ipd_ref)
+    if room_t60 is None:
+      if array is not None or self.ipd_channels:
+        raise ValueError("DynMixTrainSet: an array and ipd_channels need simulated rooms (room_t60): the mixtures made on the GPU "
+                         "have one channel without")
+      return
+    if self.reverb:
+      raise ValueError("DynMixTrainSet: room_t60 simulates the rooms; rir_scp / rir_synth are another source of RIRs, give one of them")
+    self.room_t60 = (float(room_t60[0]), float(room_t60[1]))
+    self.room_dims = (tuple(float(v) for v in room_dims[0]), tuple(float(v) for v in room_dims[1]))
+    self.array = np.zeros((1, 3)) if array is None else np.asarray(array, dtype=np.float64).reshape(-1, 3)
+    if not 0.0 < self.room_t60[0] <= self.room_t60[1] or len(self.room_dims[0]) != 3 or len(self.room_dims[1]) != 3:
+      raise ValueError("DynMixTrainSet: room_t60 = (lo, hi) seconds with 0 < lo <= hi and room_dims = ((x, y, z), (x, y, z)) expected")
+    if not 1 <= len(self.array) <= _room.MAX_MICS:
+      raise ValueError("DynMixTrainSet: an array of 1..%d microphones expected (got %d)" % (_room.MAX_MICS, len(self.array)))
+    need = max(self.ipd_channels + (self.ipd_ref,)) + 1
+    if need > len(self.array):
+      raise ValueError("DynMixTrainSet: the array has %d microphone(s): ipd_ref = %d with ipd_channels = %s needs %d"
+                       % (len(self.array), self.ipd_ref, ",".join(str(c) for c in self.ipd_channels), need))
+    # the direct path must lie inside the shortest RIR (sk_fir_convolve: delay < ntaps), whatever the draw
+    far = _room.direct_delay(self.room_dims[1], (0.0, 0.0, 0.0), self.rir_rate)
+    if min(int(round(self.room_t60[0] * self.rir_rate)), _room.MAX_TAPS) <= far:
+      raise ValueError("DynMixTrainSet: room_t60[0] = %g s is %d taps at %d Hz; the direct path across the largest room takes %d"
+                       % (self.room_t60[0], int(round(self.room_t60[0] * self.rir_rate)), self.rir_rate, far))
+
+  def draw_room(self, idx):
+    """The room of item idx, from a generator of its own: the 'room' block an item carries."""
+    from sepkern import room as _room
+    rng = np.random.default_rng([self.seed, int(idx), 2])
+    r = _room.draw_room(rng, self.room_dims[0], self.room_dims[1], self.room_t60, self.array, self.num_spk)
+    picked = [self.ipd_ref] + list(self.ipd_channels)
+    return {'L': r['L'], 'beta': r['beta'], 'mics': r['mics'][picked], 'srcs': r['srcs'],
+            'ntaps': min(int(round(r['t60'] * self.rir_rate)), _room.MAX_TAPS), 'rate': int(self.rir_rate),
+            'chans': [int(c) for c in self.ipd_channels]}
 
   def _init_reverb(self, rir_scp, rir_synth, rir_drr_db, rir_prob):
     self.rirs, self.rir_synth, self.rir_prob = None, None, float(rir_prob)
@@ -433,6 +489,8 @@ class DynMixTrainSet(Dataset):
       rirs, out['rir_delay'] = self.draw_rirs(idx)
       for s, h in enumerate(rirs):
         out['rir' + str(s + 1)] = h
+    if self.room_t60 is not None:
+      out['room'] = self.draw_room(idx)
     return out
 
 
@@ -489,6 +547,14 @@ class DynMixCollator():
       pcm['reverb'] = {'flat': torch.from_numpy(np.concatenate([h for row in rirs for h in row])), 'offs': offs,
                        'taps': [[int(len(h)) for h in row] for row in rirs],
                        'delay': [[int(batch[i]['rir_delay'][s]) for i in order] for s in range(S)]}
+    if any('room' in d for d in batch):    # simulated rooms: every item's geometry (fp64), in the batch's order
+      rooms = [batch[i].get('room') for i in order]
+      if any(r is None or r['chans'] != rooms[0]['chans'] or r['rate'] != rooms[0]['rate'] or len(r['srcs']) != len(keys) for r in rooms):
+        raise ValueError("DynMixCollator: an item with a room carries S source positions, and every item of its batch has a room "
+                         "with the same channels at the same rate")
+      pcm['room'] = {'L': np.stack([r['L'] for r in rooms]), 'beta': np.stack([r['beta'] for r in rooms]),
+                     'mics': np.stack([r['mics'] for r in rooms]), 'srcs': np.stack([r['srcs'] for r in rooms]),
+                     'ntaps': [int(r['ntaps']) for r in rooms], 'rate': rooms[0]['rate'], 'chans': list(rooms[0]['chans'])}
     return {'pcm': pcm}
 
 
@@ -816,7 +882,7 @@ def _pcm_front(model, pcm, dev, front, **front_args):
   """A PCM batch through `front` (one of sepkern.data's front ends) -> (its result, net_in): for an IPD model net_in is the
   wide input rows, made with the front end's rows from one copy of the samples (sepkern.data.ipd_rows_from_pcm); for any other
   model None -- the call is the one it was."""
-  _match_channels(model, _ipd.chan_keys(pcm['keys']))
+  _match_channels(model, _batch_chan_keys(pcm))
   if getattr(model, 'ipd_channels', ()):
     return _ipd_rows_from_pcm(pcm, dev, front, **front_args)
   return front(pcm, dev, **front_args), None

@@ -1,4 +1,5 @@
-// mix.hip -- dynamic mixing: training mixtures made on the device from single-speaker signals (sk_dynamic_mix), gfx950.
+// mix.hip -- dynamic mixing: training mixtures made on the device from single-speaker signals (sk_dynamic_mix), and the other
+// channels of an array mixture at the gains it found (sk_mix_channels, at the end), gfx950.
 //
 // The arithmetic is defined in sepkern/mixing.py (the WSJ0-2mix rule: plain mean-square power, one scale for the mixture and
 // its sources, the largest of them at `peak`).  For mixture u with sources x_s of n samples, amplitudes amp_s and peak p:
@@ -164,7 +165,56 @@ void mx_launch(bool pcm16, int B, hipStream_t stream, const void* in, const int6
                        peak, quantize, out, out_offs, gains);
 }
 
+// ---- the other channels of an array mixture (sk_mix_channels) ------------------------------------------------------------------
+// out_{p,u}[n] = chain_n(G) over channel p's S signals, with the gains sk_dynamic_mix found on the reference channel.
+// grid (B, P, MC_SPLIT), 256 threads: workgroup z of a signal takes samples z 256 + t, then every MC_SPLIT 256-th -- one writer
+// per element, nothing shared.
+constexpr int MC_THREADS = 256;
+constexpr int MC_SPLIT = 16;
+constexpr int MC_MAXP = 7;
+
+template <int S>
+__global__ __launch_bounds__(MC_THREADS) void mix_channels_kernel(const float* __restrict__ in, const int64_t* __restrict__ in_offs,
+                                                                  const int32_t* __restrict__ nsamp, int B, int P,
+                                                                  const float* __restrict__ gains, int quantize,
+                                                                  float* __restrict__ out, const int64_t* __restrict__ out_offs) {
+  const int u = blockIdx.x, p = blockIdx.y;
+  const unsigned n = (unsigned)nsamp[u];
+  const float* x[S];
+  float G[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    x[s] = in + in_offs[((int64_t)s * P + p) * B + u];
+    G[s] = gains[s * B + u];
+  }
+  float* const y = out + out_offs[(int64_t)p * B + u];
+  for (unsigned i = blockIdx.z * MC_THREADS + threadIdx.x; i < n; i += MC_SPLIT * MC_THREADS) {
+    float acc = 0.f;
+#pragma unroll
+    for (int s = 0; s < S; ++s) acc = fmaf(G[s], x[s][i], acc);
+    y[i] = quantize ? mx_quant(acc) : acc;
+  }
+}
+
 }  // namespace
+
+extern "C" int sk_mix_channels(const float* in, const int64_t* in_offs, const int32_t* nsamp, int B, int S, int P, const float* gains,
+                               int quantize, float* out, const int64_t* out_offs, sk_stream_t stream) {
+  SK_CHECK_ARG(S >= 1 && S <= SK_MAXS, "sk_mix_channels: S = %d sources outside 1..%d", S, SK_MAXS);
+  SK_CHECK_ARG(P >= 1 && P <= MC_MAXP, "sk_mix_channels: P = %d channels outside 1..%d", P, MC_MAXP);
+  SK_CHECK_ARG(B >= 1 && B <= 65535, "sk_mix_channels: B = %d mixtures outside 1..65535", B);
+  SK_CHECK_ARG(in && in_offs && nsamp && gains && out && out_offs, "sk_mix_channels: null pointer");
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)B, (unsigned)P, MC_SPLIT);
+  const int qz = quantize != 0;
+  sk_dispatch_int<1, SK_MAXS>(S, [&](auto s) {
+    hipLaunchKernelGGL((mix_channels_kernel<decltype(s)::value>), grid, dim3(MC_THREADS), 0, st, in, in_offs, nsamp, B, P, gains, qz, out,
+                       out_offs);
+    return 0;
+  });
+  SK_CHECK_LAUNCH("sk_mix_channels");
+  return SK_OK;
+}
 
 extern "C" int sk_dynamic_mix(const void* in, int pcm16, const int64_t* in_offs, const int32_t* nsamp, int B, int S,
                               const float* amp, const float* peak, int quantize, float* out, const int64_t* out_offs,

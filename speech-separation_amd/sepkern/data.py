@@ -69,6 +69,38 @@ def signal_keys(keys):
   return pick(keys)
 
 
+def batch_chan_keys(pcm):
+  """The 'chan<c>' signals a PCM batch holds -- or, for a batch still to be mixed in simulated rooms (DynMixCollator with 'room'),
+  will hold once mixed_pcm has made them --, in order."""
+  from .ipd import chan_key, chan_keys
+  if 'mixing' in pcm:
+    return [chan_key(c) for c in (pcm.get('room') or {}).get('chans', ())]
+  return chan_keys(pcm['keys'])
+
+
+def _room_jobs(room, S, B):
+  """The S C B jobs of a batch's 'room' block, source-major, then microphone (the reference first), then mixture -> (rooms, betas,
+  srcs, mics, scales, ntaps, delays): every RIR scaled by 4 pi |src - mic_ref| so that the direct path at the reference is ~ 1,
+  and every microphone of a source at the REFERENCE microphone's direct delay: the time differences between the channels survive."""
+  import numpy as np
+  from .room import FOUR_PI, direct_delay
+  L, beta, mics, srcs = (np.asarray(room[k], dtype=np.float64) for k in ('L', 'beta', 'mics', 'srcs'))
+  C = mics.shape[1]
+  if L.shape != (B, 3) or beta.shape != (B, 6) or mics.shape != (B, C, 3) or srcs.shape != (B, S, 3) or len(room['ntaps']) != B \
+      or C != 1 + len(room.get('chans', ())):
+    raise ValueError("mixed_pcm: 'room' holds per mixture a room (3), reflection coefficients (6), the reference microphone and "
+                     "one per listed channel (3 each), %d sources (3 each) and a tap count" % S)
+  rooms, betas, ss, ms, scales, ntaps, delays = [], [], [], [], [], [], []
+  for s in range(S):
+    for c in range(C):
+      for b in range(B):
+        rooms.append(L[b]); betas.append(beta[b]); ss.append(srcs[b, s]); ms.append(mics[b, c])
+        scales.append(FOUR_PI * float(np.sqrt(np.sum((srcs[b, s] - mics[b, 0]) ** 2))))
+        ntaps.append(int(room['ntaps'][b]))
+        delays.append(direct_delay(srcs[b, s], mics[b, 0], room['rate']))
+  return rooms, betas, ss, ms, scales, ntaps, delays
+
+
 def mixed_pcm(pcm, dev):
   """A DynMixCollator batch -- pcm carries 'mixing' = {'amp': [S][B], 'peak': [B], 'quantize'} and the int16 samples of the
   SOURCES only, keys 'source1' .. 'source<S>', no 'mix' -- mixed on the device (ops.dynamic_mix: one sk_dynamic_mix launch;
@@ -78,6 +110,13 @@ def mixed_pcm(pcm, dev):
   With 'reverb' = {'flat': float32 tensor of all RIRs, 'offs' / 'taps' / 'delay': [S][B]} every source is then convolved with its
   RIR (ops.fir_convolve: one sk_fir_convolve call over the S B signals; sepkern/reverb.py) and the levels are set on the
   reverberant signals: the targets are the reverberant sources.  A batch without 'reverb' takes the path it took before.
+  With 'room' (DynMixTrainSet(room_t60=...): per mixture the fp64 geometry of a simulated room, C = 1 + P microphones -- the
+  reference, then the listed channels 'chans') the image-method RIRs from every source to every microphone are made first
+  (ops.room_rirs: one sk_room_rirs launch over the S C B jobs; sepkern/room.py), ONE ops.fir_convolve convolves the S C B
+  signals (the channels of a source share its dry signal), ops.dynamic_mix sets the levels on the reference channel and one
+  ops.mix_channels forms the P other channels' mixtures at those gains: 'keys' = ['mix', 'source1', ..., 'chan<c>', ...], what
+  WavCollator gives for an array recording.  Levels and peak are defined on the reference channel; another channel may exceed
+  the peak.  A batch without 'room' takes the path it took before, launch for launch.
   The front ends below start with this and go on as they do for a batch that came mixed from disk; enqueued on the CURRENT
   stream."""
   import torch
@@ -99,7 +138,11 @@ def mixed_pcm(pcm, dev):
     ends = [sum(outs[:k]) for k in range(len(outs))]
     offs = [ends[s * len(ns):(s + 1) * len(ns)] for s in range(S)]
     ns = [min(outs[s * len(ns) + j] for s in range(S)) for j in range(len(ns))]
-  rv = pcm.get('reverb')
+  rv, room = pcm.get('reverb'), pcm.get('room')
+  if room is not None:
+    if rv is not None:
+      raise ValueError("mixed_pcm: a batch carries 'room' or 'reverb', not both")
+    return _mixed_in_rooms(flat, src, offs, ns, keys, mixing, room, dev)
   if rv is not None:      # reverberant sources: ONE sk_fir_convolve launch pair over all S B signals; the levels are set on its result
     rirs = rv['flat']
     if rirs.device != torch.device(dev):
@@ -115,6 +158,30 @@ def mixed_pcm(pcm, dev):
   src.record_stream(torch.cuda.current_stream(dev))
   flat.record_stream(torch.cuda.current_stream(dev))
   return {'flat': out, 'keys': ['mix'] + keys, 'lens': ns}
+
+
+def _mixed_in_rooms(flat, src, offs, ns, keys, mixing, room, dev):
+  """mixed_pcm's tail for a batch with 'room': flat = the dry sources at the working rate, offs[s][b] their offsets."""
+  import torch
+  from . import ops
+  from .ipd import chan_key
+  S, B, P = len(keys), len(ns), len(room.get('chans', ()))
+  C = 1 + P
+  rooms, betas, ss, ms, scales, ntaps, delays = _room_jobs(room, S, B)
+  rirs, roffs = ops.room_rirs(rooms, betas, ss, ms, ntaps, room['rate'], scales=scales, device=dev)
+  wet, at = ops.fir_convolve(flat, [offs[s][b] for s in range(S) for _ in range(C) for b in range(B)], ns * (S * C), rirs, roffs, ntaps, delays)
+  job = lambda s, c: at[(s * C + c) * B:(s * C + c + 1) * B]  # noqa: E731
+  total = sum(ns)
+  out = torch.empty((S + 1 + P) * total, dtype=torch.float32, device=wet.device)
+  _, gains = ops.dynamic_mix(wet, [job(s, 0) for s in range(S)], ns, mixing['amp'], mixing['peak'],
+                             quantize=bool(mixing.get('quantize', False)), out=out)
+  if P:
+    ops.mix_channels(wet, [[job(s, 1 + p) for p in range(P)] for s in range(S)], ns, gains,
+                     quantize=bool(mixing.get('quantize', False)), out=out[(S + 1) * total:])
+  cur = torch.cuda.current_stream(dev)
+  for t in (src, flat, rirs, wet):
+    t.record_stream(cur)
+  return {'flat': out, 'keys': ['mix'] + keys + [chan_key(c) for c in room.get('chans', ())], 'lens': ns}
 
 
 def features_from_pcm(pcm, dev):
@@ -232,7 +299,9 @@ def ipd_rows_from_pcm(pcm, dev, front=features_from_pcm, **front_args):
   from . import ops
   from .ipd import chan_keys
   if 'mixing' in pcm:
-    raise ValueError("ipd_rows_from_pcm: a batch mixed on the device (--dynamic-mix) has one channel")
+    if not batch_chan_keys(pcm):
+      raise ValueError("ipd_rows_from_pcm: a batch mixed on the device (--dynamic-mix) has one channel")
+    pcm = mixed_pcm(pcm, dev)            # simulated rooms with listed channels: mixed first, an array batch from here on
   keys = list(pcm['keys'])
   chans = chan_keys(keys)
   if not chans or keys[0] != 'mix':
@@ -411,10 +480,9 @@ class Prefetcher:
         out['targets'] = targets         # (says what 'packed' holds in place of the source magnitudes)
       else:
         front, front_args = features_from_pcm, {}
-      from .ipd import chan_keys
-      if chan_keys(pcm['keys']):         # an array batch: the IPD model's wide input rows are made here too
+      if batch_chan_keys(pcm):           # an array batch: the IPD model's wide input rows are made here too
         res, out['ipd'] = ipd_rows_from_pcm(dict(pcm, flat=host), dev, front, **front_args)
-        out['ipd_keys'] = chan_keys(pcm['keys'])
+        out['ipd_keys'] = batch_chan_keys(pcm)
       else:
         res = front(dict(pcm, flat=host), dev, **front_args)
       mix, sources, pk = res[:3]

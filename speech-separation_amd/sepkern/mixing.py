@@ -65,6 +65,23 @@ def mix(sources, amp, peak, quantized=False):
     return mixture, outs, G
 
 
+def mix_channels(channels, G, quantized=False):
+    """The other channels of an array mixture (sk_mix_channels): channels[p][s] = source s as microphone p picked it up, G the
+    gains `mix` / `gains` found on the REFERENCE channel -> [sum_s G_s x_{s,p}] per channel p, float64.  Levels and the peak are
+    defined on the reference channel: another channel may exceed the peak (and clip when quantized).  The kernel forms the sum
+    as mix's chain, fmaf(G_s, x_s, acc) with s ascending from acc = 0, so that the reference channel's own signals give `mix`'s
+    mixture bit for bit."""
+    G = [float(g) for g in G]
+    outs = []
+    for chan in channels:
+        xs = [as_float(x) for x in chan]
+        if len(xs) != len(G) or not 1 <= len(xs) <= MAX_SOURCES or any(x.ndim != 1 or x.shape != xs[0].shape or x.size < 1 for x in xs):
+            raise ValueError("mixing: every channel holds one signal per gain, 1..%d of one length >= 1" % MAX_SOURCES)
+        y = sum(g * x for g, x in zip(G, xs))
+        outs.append(quantize(y) if quantized else y)
+    return outs
+
+
 def snr_to_amp(snr_db):
     """The linear amplitude of a level in dB, 10^(snr / 20), as float32 (what the host hands the kernel)."""
     return np.float32(10.0 ** (float(snr_db) / 20.0))

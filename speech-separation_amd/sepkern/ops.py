@@ -526,6 +526,86 @@ def fir_convolve(flat, in_offs, ns, rir_flat, rir_offs, taps, delay, repeat=1):
     return out, out_offs
 
 
+# ----------------------------------------------------------------------------- simulated rooms
+def room_rirs(rooms, betas, srcs, mics, ntaps, rate, scales=None, device=None, repeat=1):
+    """Image-method room impulse responses made on the device in one launch (sk_room_rirs; sepkern/room.py defines the result).
+    Job j: the room rooms[j] = (Lx, Ly, Lz), the reflection coefficients betas[j] (six), a source srcs[j] and a microphone
+    mics[j] (three numbers each, metres), ntaps[j] taps at `rate` Hz, every image's amplitude times scales[j] (default 1).
+    The geometry is HOST data (numpy float64).  -> (rirs, offsets): float32 on `device` (default: the current one), the jobs'
+    taps back to back, job j's at offsets[j]."""
+    import numpy as np
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.SepkernError("room_rirs makes its impulse responses on a CUDA(HIP) device (there is no CPU path)")
+    ntaps = [int(t) for t in ntaps]
+    J = len(ntaps)
+    h_room, h_beta, h_src, h_mic = (np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(J, -1) if J else np.zeros((0, w)))
+                                    for a, w in ((rooms, 3), (betas, 6), (srcs, 3), (mics, 3)))
+    h_scale = np.ones(J, dtype=np.float64) if scales is None else np.ascontiguousarray(np.asarray(scales, dtype=np.float64).reshape(-1))
+    if J == 0 or h_room.shape != (J, 3) or h_beta.shape != (J, 6) or h_src.shape != (J, 3) or h_mic.shape != (J, 3) or h_scale.shape != (J,):
+        raise _lib.SepkernError("room_rirs: per job a room (3), reflection coefficients (6), a source (3), a microphone (3), a tap count and a scale")
+    offs, at = [], 0
+    for t in ntaps:
+        offs.append(at)
+        at += max(t, 0)
+    h_taps, h_offs = (C.c_int32 * J)(*ntaps), (C.c_int64 * J)(*offs)
+    hp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    nbytes = _lib.load().sk_room_workspace_bytes(hp(h_room), hp(h_beta), hp(h_src), hp(h_mic), hp(h_scale), h_taps, h_offs, J, float(rate))
+    if nbytes == 0:
+        raise _lib.SepkernError("room_rirs: 1..65535 jobs of 1..8192 taps at rate >= 1, rooms with positive dimensions, reflection "
+                                "coefficients in [0, 1], sources and microphones strictly inside their room and at least 0.01 m apart "
+                                "(sk_room_workspace_bytes refused the jobs)")
+    with torch.cuda.device(dev):
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        out = torch.empty(at, dtype=torch.float32, device=dev)
+        with _timed("room_rirs_kernel"):
+            for _ in range(repeat):
+                _lib.call("sk_room_rirs", hp(h_room), hp(h_beta), hp(h_src), hp(h_mic), hp(h_scale), h_taps, h_offs, J, float(rate), _ptr(ws),
+                          _ptr(out), _stream())
+    return out, offs
+
+
+def mix_channels(flat, chan_offs, nsamp, gains, quantize=False, out=None, repeat=1):
+    """The other channels of array mixtures at the gains dynamic_mix returned for the reference channel (sk_mix_channels;
+    sepkern/mixing.py mix_channels states the rule).  flat: ONE 1-D CUDA float32 tensor; chan_offs[s][p][u]: the offset of source
+    s on channel p of mixture u (nsamp[u] samples); gains: dynamic_mix's (S, B) tensor.
+    -> out_flat float32, channel-major, the utterances of every channel back to back in the order given: P sum(nsamp) samples.
+    Levels and the peak are defined on the reference channel: another channel may exceed the peak.  out: a float32 buffer of
+    that size to write into."""
+    _chk(flat)
+    _chk(gains)
+    ns = [int(n) for n in nsamp]
+    B, dev = len(ns), flat.device
+    S = len(chan_offs)
+    P = len(chan_offs[0]) if S else 0
+    if flat.dim() != 1 or not flat.is_contiguous() or B == 0 or min(ns) < 1:
+        raise _lib.SepkernError("mix_channels needs one contiguous 1-D tensor of samples and at least one mixture of at least one sample")
+    if not 1 <= S <= 4 or not 1 <= P <= 7 or any(len(row) != P or any(len(o) != B for o in row) for row in chan_offs):
+        raise _lib.SepkernError("mix_channels needs offsets [S][P][B] with 1 <= S <= 4 sources and 1 <= P <= 7 channels of %d mixtures" % B)
+    offs = [int(o) for row in chan_offs for chan in row for o in chan]
+    if any(o < 0 or o + ns[q % B] > flat.numel() for q, o in enumerate(offs)):
+        raise _lib.SepkernError("mix_channels: a signal runs past the sample buffer")
+    if tuple(gains.shape) != (S, B) or not gains.is_contiguous() or gains.device != dev:
+        raise _lib.SepkernError("mix_channels: gains is dynamic_mix's contiguous (S, B) = (%d, %d) tensor on the samples' device" % (S, B))
+    total = sum(ns)
+    if out is None:
+        out = torch.empty(P * total, dtype=torch.float32, device=dev)
+    _chk(out)
+    if out.dim() != 1 or not out.is_contiguous() or out.numel() < P * total:
+        raise _lib.SepkernError("mix_channels: out must be a contiguous 1-D float32 tensor of P * sum(nsamp) samples")
+    starts, at = [], 0
+    for n in ns:
+        starts.append(at)
+        at += n
+    d64 = _i64(offs + [p * total + st for p in range(P) for st in starts], dev)
+    d_ns = torch.tensor(ns, dtype=torch.int32, device=dev)
+    with _timed("mix_channels_kernel", repeat * float(total) * P * (S + 1) * 4):
+        for _ in range(repeat):
+            _lib.call("sk_mix_channels", _ptr(flat), _ptr(d64), _ptr(d_ns), B, S, P, _ptr(gains), int(bool(quantize)), _ptr(out),
+                      _ptr(d64[S * P * B:]), _stream())
+    return out[:P * total]
+
+
 def mask_istft_flat(mixcat, maskcat, Ts, S, want_pcm=True, want_float=True, repeat=1):
     """Mask-apply + iSTFT on buffers that crossed PCIe as ONE copy each: mixcat = the utterances' (257, T_u) complex64
     spectra back to back (flattened), maskcat = None or, per utterance and source (utterance-major), the (257, T_u) float32

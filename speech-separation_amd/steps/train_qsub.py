@@ -97,6 +97,14 @@ def get_args(argv=None):
                       help="with --dynamic-mix: synthetic room impulse responses in place of --mix-rir-scp, T60 uniform in [LO, HI] seconds")
   parser.add_argument("--mix-rir-prob", type=float, default=None, metavar="P",
                       help="with --mix-rir-scp / --mix-rir-synth: the probability that a source is reverberant (default 1.0)")
+  parser.add_argument("--mix-room-t60", type=rir_synth, default=None, metavar="LO,HI",
+                      help="with --dynamic-mix: every mixture is made in a simulated shoebox room of its own (image method, sk_room_rirs), "
+                           "nominal T60 uniform in [LO, HI] seconds; in place of --mix-rir-scp / --mix-rir-synth")
+  parser.add_argument("--mix-array", type=str, default=None, metavar="FILE",
+                      help="with --mix-room-t60: the microphone array, one line `x y z` (metres from its centre) per microphone, at most 8; "
+                           "an IPD model trains on its channels ipd_ref / ipd_channels.  Default: one microphone")
+  parser.add_argument("--mix-room-dims", type=room_dims, default=None, metavar="x,y,z:x,y,z",
+                      help="with --mix-room-t60: the smallest and the largest room in metres (default 3,3,2.5:8,6,4)")
   parser.add_argument("--seed", type=int, default=None, help="seed for weights, shuffling, mixture draws and h0/c0")
   args = parser.parse_args(argv)
   dynamic_mixing(args)
@@ -119,8 +127,22 @@ def rir_synth(text):
   return (parts[0], parts[1])
 
 
+def room_dims(text):
+  """--mix-room-dims x,y,z:x,y,z -> ((x, y, z), (x, y, z)), the smallest and the largest room."""
+  try:
+    lo, hi = [tuple(float(v) for v in part.split(',')) for part in text.split(':')]
+  except ValueError:
+    raise argparse.ArgumentTypeError("x,y,z:x,y,z expected")
+  if len(lo) != 3 or len(hi) != 3 or not all(0.0 < a <= b for a, b in zip(lo, hi)):
+    raise argparse.ArgumentTypeError("x,y,z:x,y,z with 0 < smallest <= largest expected")
+  return (lo, hi)
+
+
 NEEDS_WAV_INPUT = "`--dynamic-mix` needs `--wav-input`: the mixtures are made from waveforms on the GPU"
 NEEDS_DYNAMIC_MIX = "`%s` needs `--dynamic-mix`: room impulse responses are applied to the sources of mixtures made on the GPU"
+ROOM_NEEDS_DYNAMIC_MIX = "`%s` needs `--dynamic-mix`: the rooms are simulated for mixtures made on the GPU"
+ROOM_OR_RIRS = "`--mix-room-t60` simulates the rooms; `%s` is another source of room impulse responses: give one of them"
+ARRAY_NEEDS_ROOM = "`%s` needs `--mix-room-t60`: an array stands in a simulated room"
 ONE_RIR_SOURCE = "`--mix-rir-scp` and `--mix-rir-synth` are two sources of room impulse responses: give one of them"
 
 
@@ -131,16 +153,44 @@ def reverb_options(args):
   return {k: v for k, v in given.items() if v is not None}
 
 
+def room_options(args):
+  """The simulated-room options that were given, as DynMixTrainSet's keyword arguments ({} without any); the array file is read
+  here (sepkern/room.py read_array)."""
+  given = {"room_t60": getattr(args, "mix_room_t60", None), "array": getattr(args, "mix_array", None),
+           "room_dims": getattr(args, "mix_room_dims", None)}
+  given = {k: v for k, v in given.items() if v is not None}
+  if isinstance(given.get("array"), str):
+    from sepkern.room import read_array
+    try:
+      given["array"] = read_array(given["array"]) if os.path.exists(given["array"]) else None
+    except ValueError as e:
+      raise SystemExit("--mix-array: %s" % e)
+    if given["array"] is None:
+      raise SystemExit("--mix-array: there is no file %s" % args.mix_array)
+  return given
+
+
+ROOM_FLAGS = {"room_t60": "--mix-room-t60", "array": "--mix-array", "room_dims": "--mix-room-dims"}
+
+
 def dynamic_mixing(args):
   """True with --dynamic-mix.  The mixtures are made from waveforms: without --wav-input the run ends here, not at its first batch;
-  so does a run with a --mix-rir-* option and no --dynamic-mix, or with both sources of RIRs."""
+  so does a run with a --mix-rir-* or --mix-room-* option and no --dynamic-mix, with two sources of RIRs, or with an array and
+  no simulated room."""
   rir = reverb_options(args)
+  room = [k for k in ("room_t60", "array", "room_dims") if getattr(args, "mix_" + k, None) is not None]
   if not getattr(args, "dynamic_mix", False):
     if rir:
       raise SystemExit(NEEDS_DYNAMIC_MIX % ("--mix-" + sorted(rir)[0].replace("_", "-")))
+    if room:
+      raise SystemExit(ROOM_NEEDS_DYNAMIC_MIX % ROOM_FLAGS[room[0]])
     return False
   if not args.wav_input:
     raise SystemExit(NEEDS_WAV_INPUT)
+  if room and "room_t60" not in room:
+    raise SystemExit(ARRAY_NEEDS_ROOM % ROOM_FLAGS[room[0]])
+  if room and rir:
+    raise SystemExit(ROOM_OR_RIRS % ("--mix-" + sorted(rir)[0].replace("_", "-")))
   if "rir_scp" in rir and "rir_synth" in rir:
     raise SystemExit(ONE_RIR_SOURCE)
   if "rir_prob" in rir and len(rir) == 1:
@@ -248,11 +298,15 @@ def prefetch_targets(m, args):
   return kind
 
 
+IPD_WANTS_ROOMS = " -- unless they are made in simulated rooms: give `--mix-room-t60` and `--mix-array`"
+
+
 def ipd_model(m, args):
   """{'ipd_ref': r, 'ipd_channels': (c, ...)} when the conf file makes it an IPD model (archs/uPIT.py conf key ipd_channels,
   sepkern/ipd.py: the network also sees the phase differences between the channels of an array), else {}.  Such a model trains
-  on multi-channel wav files: without --wav-input, with --dynamic-mix (its mixtures have one channel) or with loss=mixit the
-  run ends here, not at its first batch."""
+  on multi-channel wav files, or on mixtures made in simulated rooms (--dynamic-mix --mix-room-t60 --mix-array): without
+  --wav-input, with --dynamic-mix alone (its mixtures have one channel), with an array that lacks one of the model's microphones
+  or with loss=mixit the run ends here, not at its first batch."""
   if not hasattr(m, "ipd_conf"):
     return {}
   conf = read_model_conf(args.model_config)
@@ -265,7 +319,13 @@ def ipd_model(m, args):
   if not args.wav_input:
     raise SystemExit(m.IPD_NEEDS_WAVEFORMS)
   if getattr(args, "dynamic_mix", False):
-    raise SystemExit(m.IPD_NO_DYNAMIC_MIX)
+    # only in simulated rooms with an array that has the model's microphones (--mix-room-t60 with --mix-array)
+    if getattr(args, "mix_room_t60", None) is None or getattr(args, "mix_array", None) is None:
+      raise SystemExit(m.IPD_NO_DYNAMIC_MIX + IPD_WANTS_ROOMS)
+    have = len(room_options(args)["array"])
+    if max(chans + (ref,)) >= have:
+      raise SystemExit("`--mix-array` %s has %d microphone(s): ipd_ref = %d with ipd_channels = %s needs %d"
+                       % (args.mix_array, have, ref, ",".join(str(c) for c in chans), max(chans + (ref,)) + 1))
   return {"ipd_ref": ref, "ipd_channels": chans}
 
 
@@ -309,7 +369,8 @@ def dynamic_mix_batches(m, args, rank, world):
   dataset = m.DynMixTrainSet(args.data_dir, mixed_recordings(m, args),
                              mixes_per_epoch=args.mixes_per_epoch, snr_db=args.mix_snr_db, peak=args.mix_peak,
                              max_samples=args.mix_max_samples, seed=seed, sample_rate=getattr(args, "sample_rate", None),
-                             quantize=args.mix_quantize, **reverb_options(args))      # (an arch without RIRs is given none)
+                             quantize=args.mix_quantize, **reverb_options(args),      # (an arch without RIRs is given none)
+                             **room_options(args), **(getattr(args, "ipd", None) or {}))
   draws = skdist.MixDraws(dataset.mixes_per_epoch, args.batch_size, rank, world, seed=seed)
   workers = loader_workers(args, world)
   extra = dict(persistent_workers=True, prefetch_factor=2) if workers > 0 else {}
