@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define SK_VERSION 147
+#define SK_VERSION 148
 
 #define SK_OK 0
 #define SK_EINVAL (-1)   /* bad argument / unsupported shape */
@@ -152,6 +152,43 @@ int sk_room_rirs(const double* room_host, const double* beta_host, const double*
  * 1 <= S <= 4, 1 <= P <= 7, 1 <= B <= 65535, nsamp[u] >= 1. */
 int sk_mix_channels(const float* in, const int64_t* in_offs, const int32_t* nsamp, int B, int S, int P, const float* gains,
                     int quantize, float* out, const int64_t* out_offs, sk_stream_t stream);
+
+/* ---------------------------------------------------------------- noisy dynamic mixing (additive and diffuse array noise)
+ * sepkern/noise.py defines the three results (Habets, Cohen & Gannot 2008 on the library's 512 / 128 transform) and restates
+ * sk_diffuse_noise in numpy float32 (diffuse_f32).
+ *
+ * sk_noise_factors: for mixture u with C microphones at mics_host[(u*C + i)*3 ..] (HOST, fp64, metres) and bins k = 0 .. 256 at
+ * f_k = k rate / 512: Gamma_k[i,j] = sinc(2 f_k d_ij / 343), and L_k = the lower-triangular Cholesky factor of
+ * (1 - 2^-20) Gamma_k + 2^-20 I, all in fp64, one thread per (mixture, bin); L[(u*257 + k)*C(C+1)/2 + i(i+1)/2 + j] = fp32(L_k[i,j]),
+ * j <= i.  The microphones travel as kernel arguments, 16 mixtures per launch.  2 <= C <= 8, 1 <= B <= 65535, rate >= 1,
+ * microphones of a mixture at least 0.01 m apart.
+ *
+ * sk_diffuse_noise: channel c of mixture u: the nsamp[u] samples N_c at in + in_offs[c*B + u] (float32, or int16 PCM scaled by
+ * 1/32768 when pcm16 != 0), C mutually independent noise signals, zero outside [0, nsamp[u]).  T = ceil(n / 128) + 3 frames,
+ * frame t covering samples 128 (t - 3) .. + 511, periodic Hann for analysis and synthesis; per frame and bin
+ *   X_i = L[i,0] N_0, then fmaf(L[i,j], N_j, .) with j ascending to i                (L: sk_noise_factors' layout)
+ * and out[out_offs[c*B + u] + n] = fp32(2/3) times the sum of the four windowed inverse frames that cover sample n, in ascending
+ * frame order.  Exactly nsamp[u] floats are written per signal.  A workgroup owns 13 hops of one mixture and transforms the 16
+ * frames that touch them, the C spectra in registers; no atomics, no workspace, one writer per element: a mixture's bits depend
+ * neither on the batch around it nor on the run, and int16 samples give the bits of their float32 copies.  The descriptor
+ * arrays live on the device; max_nsamp >= max_u nsamp[u] sizes the grid (a longer signal is cut to it).  2 <= C <= 8,
+ * 1 <= B <= 65535, 1 <= max_nsamp <= 2^30.
+ *
+ * sk_add_noise: IN PLACE on the C channels y_c of B mixtures (nsamp[u] float32 at sig + sig_offs[c*B + u], the reference channel
+ * c = 0 first), with the noise v_c at noise + noise_offs[c*B + u] (float32, or int16 PCM when noise_pcm16 != 0):
+ *   P_y = mean y_0^2, P_v = mean v_0^2 (fp64);  a = fp32(amp[u] sqrt(P_y / P_v)), 0 where either is below 2^-40
+ *   y_c[n] = fmaf(a, v_c[n], y_c[n]);   quantize != 0: then clip(rint(32768 v), -32768, 32767) / 32768
+ * amp is LINEAR (the host computes 10^(-snr/20)); one gain serves all channels, so a diffuse field keeps its coherence.  The
+ * SNR is that of the whole mixture over the noise on the reference channel; the clean mixture's peak may be exceeded (and,
+ * quantized, clipped).  gains_out (B floats, may be NULL) receives a.  One workgroup per mixture as sk_dynamic_mix: bitwise
+ * reproducible, independent of the batch.  The descriptor arrays live on the device.  1 <= C <= 8, 1 <= B <= 65535, nsamp[u] >= 1.
+ *
+ * Bad arguments return SK_EINVAL before anything is launched. */
+int sk_noise_factors(const double* mics_host, int B, int C, double rate, float* L, sk_stream_t stream);
+int sk_diffuse_noise(const void* in, int pcm16, const int64_t* in_offs, const int32_t* nsamp, int B, int C, int max_nsamp,
+                     const float* L, float* out, const int64_t* out_offs, sk_stream_t stream);
+int sk_add_noise(float* sig, const int64_t* sig_offs, const void* noise, int noise_pcm16, const int64_t* noise_offs,
+                 const int32_t* nsamp, int B, int C, const float* amp, int quantize, float* gains_out, sk_stream_t stream);
 
 /* ---------------------------------------------------------------- mask-apply + iSTFT back end
  * Replaces np.multiply(mix_spec, mask) + librosa.core.istft(hop_length=128) + (*32767).astype(int16)

@@ -49,6 +49,8 @@ Beyond the reference (all optional, defaults reproduce it):
     (--mix-room-t60 [--mix-array FILE]) every mixture is made in a simulated shoebox room of its own: image-method RIRs from every
     source to every microphone of the array, made on the GPU (sk_room_rirs; sepkern/room.py), and the listed channels' mixtures
     at the reference channel's gains (sk_mix_channels) -- an array batch for an IPD model, or one microphone for any other.
+    With noise_scp (--mix-noise-scp [--mix-noise-snr]) a noise recording is added to every mixture at a drawn SNR (sk_add_noise),
+    and to an array mixture a diffuse field with the microphones' coherence (sk_noise_factors, sk_diffuse_noise; sepkern/noise.py).
   * conf keys ipd_channels (e.g. 1,2,3) and ipd_ref (0): an IPD model (sepkern/ipd.py).  The network's input is the magnitude
     of channel ipd_ref of an array recording followed by cos and sin of the phase difference of every listed channel against
     it, in_dim = 257 (1 + 2P); feat_dim, out_dim and the losses mse / psa / tpsa / dpcl / sisdr are what they are without.
@@ -318,11 +320,22 @@ class DynMixTrainSet(Dataset):
   by those of ipd_channels (only they travel), 'srcs', 'ntaps' = min(round(t60 rate), 8192) at the rate the convolution runs
   at, 'rate', 'chans'}.  With ipd_channels the mixed batch is an array batch ('chan<c>' behind the sources) for an IPD model.
   These draws come from a generator of their own, seeded (seed, idx, 2): draw(idx) and every other key are bit for bit what they
-  are without a room.  Not together with rir_scp / rir_synth."""
+  are without a room.  Not together with rir_scp / rir_synth.
+
+  Noise (noise_scp: lines `<noise-id> <path>` of mono 16-bit wav files at the working rate -- another rate is an error here, as
+  for RIRs; the files are read lazily, with mmap; sepkern/noise.py): a noise recording is added ON THE GPU to every mixture
+  (sk_add_noise) at a ratio of mixture to noise, on the reference channel, of snr ~ U(noise_snr_db) dB.  An item then carries
+  'noise1' .. 'noise<C>' (int16, as long as the mixture at the working rate) -- one crop per microphone that travels, 1 without an
+  array -- and 'noise_amp' = 10^(-snr / 20).  With an array the C crops are the independent inputs of a spherically isotropic
+  field with the microphones' coherence (sk_noise_factors, sk_diffuse_noise).  Every crop is a (file, start) pair drawn on its
+  own, and a file shorter than the mixture wraps around; crops that overlap -- a short list -- make the field less diffuse.
+  These draws come from a generator of their own, seeded (seed, idx, 3): draw_noise(idx); every other key an item carries is bit
+  for bit what it is without noise.  The sources stay clean: the targets of a noisy mixture are its noise-free sources."""
 
   def __init__(self, datadir, num_spk, mixes_per_epoch=None, snr_db=2.5, peak=(0.9, 0.9), max_samples=0, seed=0, sample_rate=None,
                quantize=False, rir_scp=None, rir_synth=None, rir_drr_db=(0.0, 15.0), rir_prob=1.0,
-               room_t60=None, room_dims=((3, 3, 2.5), (8, 6, 4)), array=None, ipd_ref=0, ipd_channels=()):
+               room_t60=None, room_dims=((3, 3, 2.5), (8, 6, 4)), array=None, ipd_ref=0, ipd_channels=(),
+               noise_scp=None, noise_snr_db=(-3.0, 6.0)):
     import wave
     self.num_spk, self.seed = int(num_spk), int(seed)
     self.snr_db, self.peak, self.max_samples = float(snr_db), (float(peak[0]), float(peak[1])), int(max_samples)
@@ -364,6 +377,47 @@ class DynMixTrainSet(Dataset):
     self.collator = DynMixCollator(self.sample_rate, quantize)
     self._init_reverb(rir_scp, rir_synth, rir_drr_db, rir_prob)
     self._init_room(room_t60, room_dims, array, ipd_ref, ipd_channels)
+    self._init_noise(noise_scp, noise_snr_db)
+
+  def _init_noise(self, noise_scp, noise_snr_db):
+    import wave
+    self.noises = None
+    self.noise_snr_db = (float(noise_snr_db[0]), float(noise_snr_db[1]))
+    if not noise_scp:
+      return
+    if not self.noise_snr_db[0] <= self.noise_snr_db[1]:
+      raise ValueError("DynMixTrainSet: noise_snr_db = (lo, hi) dB with lo <= hi expected")
+    self.noises = []
+    for line in open(noise_scp):
+      if not line.strip():
+        continue
+      _, path = line.rstrip('\n').split(' ', 1)
+      path = path.strip()
+      with wave.open(path, "rb") as w:
+        if w.getnchannels() != 1 or w.getsampwidth() != 2:
+          raise ValueError("%s: only mono 16-bit PCM wav is supported for a noise recording" % path)
+        if w.getframerate() != int(self.rir_rate):
+          raise ValueError("noise recording %s is sampled at %d Hz, the run works at %d Hz: noise is not resampled"
+                           % (path, w.getframerate(), int(self.rir_rate)))
+        if w.getnframes() < 1:
+          raise ValueError("%s: an empty noise recording" % path)
+        self.noises.append((path, w.getnframes()))
+    if not self.noises:
+      raise ValueError("%s lists no noise recording" % noise_scp)
+
+  def noise_channels(self):
+    """Microphones that travel: the reference and, in a simulated room, those of ipd_channels."""
+    return 1 + (len(self.ipd_channels) if self.room_t60 is not None else 0)
+
+  def draw_noise(self, idx):
+    """The noise of item idx, from a generator of its own: (snr dB, [(path, crop start, file length)] per microphone)."""
+    rng = np.random.default_rng([self.seed, int(idx), 3])
+    snr = float(rng.uniform(self.noise_snr_db[0], self.noise_snr_db[1]))
+    crops = []
+    for _ in range(self.noise_channels()):
+      path, m = self.noises[int(rng.integers(len(self.noises)))]
+      crops.append((path, int(rng.integers(m)), m))
+    return snr, crops
 
   def _init_room(self, room_t60, room_dims, array, ipd_ref, ipd_channels):
     from sepkern import room as _room
@@ -491,6 +545,19 @@ class DynMixTrainSet(Dataset):
         out['rir' + str(s + 1)] = h
     if self.room_t60 is not None:
       out['room'] = self.draw_room(idx)
+    if self.noises is not None:
+      from sepkern.noise import snr_to_amp as noise_amp
+      snr_n, crops = self.draw_noise(idx)
+      nn = self._at_rate(n)                # the mixture's length at the working rate, where the noise is added
+      for c, (path, st, m) in enumerate(crops):
+        _, v = scipy.io.wavfile.read(path, mmap=True)
+        if v.dtype != np.int16 or v.ndim != 1 or len(v) != m:
+          raise ValueError("%s: changed since the set was built (mono 16-bit PCM of %d samples expected)" % (path, m))
+        if st + nn <= m:
+          out['noise' + str(c + 1)] = np.array(v[st:st + nn])
+        else:                              # a file shorter than the mixture (or a crop near its end) wraps around
+          out['noise' + str(c + 1)] = np.asarray(v).take(np.arange(st, st + nn) % m)
+      out['noise_amp'] = float(noise_amp(snr_n))
     return out
 
 
@@ -498,7 +565,9 @@ class DynMixCollator():
   """WavCollator for DynMixTrainSet's items: sorted by frame count, longest first, the SOURCES' int16 samples as one tensor,
   key-major ('source1', ...), and what the GPU needs to mix them -- {'pcm': {'flat', 'keys': ['source1', ...], 'lens', 'mixing':
   {'amp': [S][B], 'peak': [B], 'quantize'}}} (+ 'rate' / 'target_rate' as WavCollator).  The batch holds no 'mix': sepkern.data's
-  front ends make it (mixed_pcm) and go on as they do for a WavCollator batch."""
+  front ends make it (mixed_pcm) and go on as they do for a WavCollator batch.  Noisy items ('noise1' .. 'noise<C>', 'noise_amp')
+  add 'noise' = {'flat': int16 tensor, channel-major in the batch's order, 'lens': samples per item, 'amp': [B]}; every item of a
+  batch has noise or none does."""
 
   def __init__(self, sample_rate=None, quantize=False):
     self.sample_rate = None if sample_rate is None else int(sample_rate)
@@ -555,6 +624,14 @@ class DynMixCollator():
       pcm['room'] = {'L': np.stack([r['L'] for r in rooms]), 'beta': np.stack([r['beta'] for r in rooms]),
                      'mics': np.stack([r['mics'] for r in rooms]), 'srcs': np.stack([r['srcs'] for r in rooms]),
                      'ntaps': [int(r['ntaps']) for r in rooms], 'rate': rooms[0]['rate'], 'chans': list(rooms[0]['chans'])}
+    if any('noise1' in d for d in batch):  # noisy items: one crop per microphone, channel-major in the batch's order, as ONE tensor
+      nk = sorted((k for k in batch[0] if k.startswith('noise') and k[5:].isdigit()), key=lambda k: int(k[5:]))
+      if any('noise_amp' not in d or sorted(k for k in d if k.startswith('noise') and k[5:].isdigit()) != sorted(nk)
+             or any(len(d[k]) != len(d[nk[0]]) for k in nk) for d in batch) or nk != ['noise' + str(c + 1) for c in range(len(nk))]:
+        raise ValueError("DynMixCollator: a noisy item carries 'noise1' .. 'noise<C>' of one length and 'noise_amp', and so does "
+                         "every item of its batch, with the same C")
+      pcm['noise'] = {'flat': torch.from_numpy(np.concatenate([np.asarray(batch[i][k], dtype=np.int16) for k in nk for i in order])),
+                      'lens': [int(len(batch[i][nk[0]])) for i in order], 'amp': [float(batch[i]['noise_amp']) for i in order]}
     return {'pcm': pcm}
 
 

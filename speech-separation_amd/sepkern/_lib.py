@@ -21,7 +21,7 @@ BUILD_FLAG_NAMES = {0x1: "TIMING_ONLY (wrong results by construction)", 0x2: "AR
 def build_flag_names(mask):
     return [n for b, n in sorted(BUILD_FLAG_NAMES.items()) if mask & b] + (["unknown 0x%x" % (mask & ~0xf)] if mask & ~0xf else [])
 
-SK_VERSION = 147
+SK_VERSION = 148
 
 _p, _i, _i64, _f, _sz = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t
 
@@ -39,6 +39,9 @@ PROTOTYPES = {
     "sk_room_workspace_bytes": (_sz, [_p, _p, _p, _p, _p, _p, _p, _i, C.c_double]),
     "sk_room_rirs": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, C.c_double, _p, _p, _p]),
     "sk_mix_channels": (_i, [_p, _p, _p, _i, _i, _i, _p, _i, _p, _p, _p]),
+    "sk_noise_factors": (_i, [_p, _i, _i, C.c_double, _p, _p]),
+    "sk_diffuse_noise": (_i, [_p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "sk_add_noise": (_i, [_p, _p, _p, _i, _p, _p, _i, _i, _p, _i, _p, _p]),
     "sk_mask_istft": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _i, _p]),
     "sk_stitch_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "sk_stitch": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p]),

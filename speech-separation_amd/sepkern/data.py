@@ -117,6 +117,11 @@ def mixed_pcm(pcm, dev):
   ops.mix_channels forms the P other channels' mixtures at those gains: 'keys' = ['mix', 'source1', ..., 'chan<c>', ...], what
   WavCollator gives for an array recording.  Levels and peak are defined on the reference channel; another channel may exceed
   the peak.  A batch without 'room' takes the path it took before, launch for launch.
+  With 'noise' (DynMixTrainSet(noise_scp=...): {'flat': int16 crops, channel-major, 'lens', 'amp': [B]}; sepkern/noise.py) noise is
+  added after all that, in place: to a batch of one channel -- plain, reverberant or a mono room -- the crop itself by ONE
+  ops.add_noise; to an array batch a diffuse field, ops.noise_factors from the room's microphones, ops.diffuse_noise over the C
+  crops, then ONE ops.add_noise over 'mix' and the 'chan<c>' signals at the reference channel's gain.  'source<s>' stay as they
+  are: the targets are clean.  A batch without 'noise' takes the path it took before, launch for launch.
   The front ends below start with this and go on as they do for a batch that came mixed from disk; enqueued on the CURRENT
   stream."""
   import torch
@@ -142,7 +147,7 @@ def mixed_pcm(pcm, dev):
   if room is not None:
     if rv is not None:
       raise ValueError("mixed_pcm: a batch carries 'room' or 'reverb', not both")
-    return _mixed_in_rooms(flat, src, offs, ns, keys, mixing, room, dev)
+    return _with_noise(_mixed_in_rooms(flat, src, offs, ns, keys, mixing, room, dev), pcm.get('noise'), mixing, room, dev)
   if rv is not None:      # reverberant sources: ONE sk_fir_convolve launch pair over all S B signals; the levels are set on its result
     rirs = rv['flat']
     if rirs.device != torch.device(dev):
@@ -157,7 +162,44 @@ def mixed_pcm(pcm, dev):
   out, _ = ops.dynamic_mix(flat, offs, ns, mixing['amp'], mixing['peak'], quantize=bool(mixing.get('quantize', False)))
   src.record_stream(torch.cuda.current_stream(dev))
   flat.record_stream(torch.cuda.current_stream(dev))
-  return {'flat': out, 'keys': ['mix'] + keys, 'lens': ns}
+  return _with_noise({'flat': out, 'keys': ['mix'] + keys, 'lens': ns}, pcm.get('noise'), mixing, None, dev)
+
+
+def _with_noise(mixed, nz, mixing, room, dev):
+  """mixed_pcm's last step: the batch as it came without 'noise' (nz is None), else noise added in place to 'mix' and the
+  'chan<c>' signals of the mixed batch.  The crops are as long as the mixtures at the working rate, or longer: they are cut."""
+  if nz is None:
+    return mixed
+  import torch
+  from . import ops
+  from .ipd import chan_keys
+  keys, ns, out = mixed['keys'], mixed['lens'], mixed['flat']
+  B, total = len(ns), sum(ns)
+  starts = [sum(ns[:j]) for j in range(B)]
+  chans = ['mix'] + chan_keys(keys)
+  C = len(chans)
+  nl = [int(v) for v in nz['lens']]
+  crops = nz['flat']
+  if len(nl) != B or len(nz['amp']) != B or crops.numel() != C * sum(nl) or any(a < b for a, b in zip(nl, ns)):
+    raise ValueError("mixed_pcm: 'noise' holds one crop per channel (%d) and mixture (%d), each at least as long as its mixture, "
+                     "and one amplitude per mixture" % (C, B))
+  if crops.device != torch.device(dev):
+    crops = (crops if crops.is_pinned() else crops.pin_memory()).to(dev, non_blocking=True)
+  nstarts = [sum(nl[:j]) for j in range(B)]
+  noffs = [[c * sum(nl) + st for st in nstarts] for c in range(C)]
+  soffs = [[keys.index(k) * total + st for st in starts] for k in chans]
+  quant = bool(mixing.get('quantize', False))
+  cur = torch.cuda.current_stream(dev)
+  if C == 1:
+    ops.add_noise(out, soffs, crops, noffs, ns, nz['amp'], quantize=quant)
+  else:
+    L = ops.noise_factors(room['mics'], room['rate'], device=dev)
+    field = ops.diffuse_noise(crops, noffs, ns, L)
+    ops.add_noise(out, soffs, field, [[c * total + st for st in starts] for c in range(C)], ns, nz['amp'], quantize=quant)
+    L.record_stream(cur)
+    field.record_stream(cur)
+  crops.record_stream(cur)
+  return mixed
 
 
 def _mixed_in_rooms(flat, src, offs, ns, keys, mixing, room, dev):

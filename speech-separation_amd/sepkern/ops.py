@@ -606,6 +606,105 @@ def mix_channels(flat, chan_offs, nsamp, gains, quantize=False, out=None, repeat
     return out[:P * total]
 
 
+# ----------------------------------------------------------------------------- noisy dynamic mixing
+def noise_factors(mics, rate, device=None, repeat=1):
+    """The Cholesky factors of a diffuse field's coherence at B arrays (sk_noise_factors; sepkern/noise.py factors defines the
+    result).  mics: HOST data (numpy float64) of shape (B, C, 3), metres, 2 <= C <= 8.  -> L float32 (B, 257, C (C + 1) / 2) on
+    `device` (default: the current one), entry i (i + 1) / 2 + j = L_k[i, j], j <= i: what diffuse_noise takes."""
+    import numpy as np
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.SepkernError("noise_factors makes its factors on a CUDA(HIP) device (there is no CPU path)")
+    h = np.ascontiguousarray(np.asarray(mics, dtype=np.float64))
+    if h.ndim != 3 or h.shape[2] != 3 or h.shape[0] < 1 or not 2 <= h.shape[1] <= 8:
+        raise _lib.SepkernError("noise_factors: microphones (B, C, 3) with B >= 1 and 2 <= C <= 8 expected (got shape %s)" % (h.shape,))
+    B, Cm = h.shape[:2]
+    with torch.cuda.device(dev):
+        L = torch.empty(B, 257, Cm * (Cm + 1) // 2, dtype=torch.float32, device=dev)
+        with _timed("noise_factors_kernel"):
+            for _ in range(repeat):
+                _lib.call("sk_noise_factors", h.ctypes.data_as(C.c_void_p), B, Cm, float(rate), _ptr(L), _stream())
+    return L
+
+
+def _noise_offsets(who, flat, offs, ns, lo, hi):
+    """offs[c][u] -> (C, the flat list), checked against the buffer."""
+    offs = [[int(o) for o in row] for row in offs]
+    Cn, B = len(offs), len(ns)
+    if not lo <= Cn <= hi or any(len(row) != B for row in offs):
+        raise _lib.SepkernError("%s needs %d..%d lists of %d offsets (got %d)" % (who, lo, hi, B, Cn))
+    if any(o < 0 or o + n > flat.numel() for row in offs for o, n in zip(row, ns)):
+        raise _lib.SepkernError("%s: a signal runs past its buffer" % who)
+    return Cn, [o for row in offs for o in row]
+
+
+def diffuse_noise(flat, chan_offs, nsamp, L, out=None, repeat=1):
+    """A diffuse noise field from C independent noise signals per mixture in one launch (sk_diffuse_noise; sepkern/noise.py
+    diffuse defines the result).  flat: ONE 1-D CUDA tensor of samples, float32 or int16 PCM; chan_offs[c][u]: the offset of
+    mixture u's signal c (nsamp[u] samples); L: noise_factors' (B, 257, C (C + 1) / 2) tensor.
+    -> out_flat float32, channel-major, the mixtures of every channel back to back in the order given: C sum(nsamp) samples.
+    out: a float32 buffer of that size to write into."""
+    pcm16 = flat.dtype == torch.int16
+    _chk(flat, torch.int16 if pcm16 else torch.float32)
+    _chk(L)
+    ns = [int(n) for n in nsamp]
+    B, dev = len(ns), flat.device
+    if flat.dim() != 1 or not flat.is_contiguous() or B == 0 or min(ns) < 1:
+        raise _lib.SepkernError("diffuse_noise needs one contiguous 1-D tensor of samples and at least one mixture of at least one sample")
+    Cn, offs = _noise_offsets("diffuse_noise", flat, chan_offs, ns, 2, 8)
+    if tuple(L.shape) != (B, 257, Cn * (Cn + 1) // 2) or not L.is_contiguous() or L.device != dev:
+        raise _lib.SepkernError("diffuse_noise: L is noise_factors' contiguous (B, 257, C (C + 1) / 2) = (%d, 257, %d) tensor on the samples' device"
+                                % (B, Cn * (Cn + 1) // 2))
+    total = sum(ns)
+    if out is None:
+        out = torch.empty(Cn * total, dtype=torch.float32, device=dev)
+    _chk(out)
+    if out.dim() != 1 or not out.is_contiguous() or out.numel() < Cn * total:
+        raise _lib.SepkernError("diffuse_noise: out must be a contiguous 1-D float32 tensor of C * sum(nsamp) samples")
+    starts, at = [], 0
+    for n in ns:
+        starts.append(at)
+        at += n
+    d64 = _i64(offs + [c * total + st for c in range(Cn) for st in starts], dev)
+    d_ns = torch.tensor(ns, dtype=torch.int32, device=dev)
+    # 5 N log2 N per 512-point transform, 2 C per frame, and 4 flops per bin and factor entry
+    frames = sum(-(-n // 128) + 3 for n in ns)
+    with _timed("diffuse_noise_kernel", repeat * frames * (5.0 * 512 * 9 * 2 * Cn + 4.0 * 257 * Cn * (Cn + 1) / 2)):
+        for _ in range(repeat):
+            _lib.call("sk_diffuse_noise", _ptr(flat), int(pcm16), _ptr(d64), _ptr(d_ns), B, Cn, max(ns), _ptr(L), _ptr(out),
+                      _ptr(d64[Cn * B:]), _stream())
+    return out[:Cn * total]
+
+
+def add_noise(sig, sig_offs, noise, noise_offs, nsamp, amp, quantize=False, repeat=1):
+    """Noise added IN PLACE to the channels of B mixtures at the given amplitudes in one launch (sk_add_noise; sepkern/noise.py
+    add_noise states the rule).  sig: ONE 1-D CUDA float32 tensor, sig_offs[c][u] the offset of channel c of mixture u (nsamp[u]
+    samples), the reference channel first; noise / noise_offs: the same for the noise, float32 or int16 PCM; amp: B linear
+    amplitudes, 10^(-snr / 20).  -> the B gains a (float32 tensor): a = amp sqrt(P_mix / P_noise) on the reference channel."""
+    pcm16 = noise.dtype == torch.int16
+    _chk(sig)
+    _chk(noise, torch.int16 if pcm16 else torch.float32)
+    ns = [int(n) for n in nsamp]
+    B, dev = len(ns), sig.device
+    if sig.dim() != 1 or noise.dim() != 1 or not sig.is_contiguous() or not noise.is_contiguous() or noise.device != dev or B == 0 or min(ns) < 1:
+        raise _lib.SepkernError("add_noise needs two contiguous 1-D tensors on one device and at least one mixture of at least one sample")
+    Cn, so = _noise_offsets("add_noise", sig, sig_offs, ns, 1, 8)
+    Cv, no = _noise_offsets("add_noise", noise, noise_offs, ns, 1, 8)
+    amp = [float(a) for a in amp]
+    if Cv != Cn or len(amp) != B:
+        raise _lib.SepkernError("add_noise needs one noise signal per channel (%d, got %d) and one amplitude per mixture" % (Cn, Cv))
+    d64 = _i64(so + no, dev)
+    d_ns = torch.tensor(ns, dtype=torch.int32, device=dev)
+    d_amp = torch.tensor(amp, dtype=torch.float32, device=dev)
+    gains = torch.empty(B, dtype=torch.float32, device=dev)
+    total = sum(ns)
+    with _timed("add_noise_kernel", repeat * float(total) * (8 + (2 if pcm16 else 4) + Cn * (8 + (2 if pcm16 else 4)))):
+        for _ in range(repeat):
+            _lib.call("sk_add_noise", _ptr(sig), _ptr(d64), _ptr(noise), int(pcm16), _ptr(d64[Cn * B:]), _ptr(d_ns), B, Cn, _ptr(d_amp),
+                      int(bool(quantize)), _ptr(gains), _stream())
+    return gains
+
+
 def mask_istft_flat(mixcat, maskcat, Ts, S, want_pcm=True, want_float=True, repeat=1):
     """Mask-apply + iSTFT on buffers that crossed PCIe as ONE copy each: mixcat = the utterances' (257, T_u) complex64
     spectra back to back (flattened), maskcat = None or, per utterance and source (utterance-major), the (257, T_u) float32

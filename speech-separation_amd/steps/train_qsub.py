@@ -105,6 +105,13 @@ def get_args(argv=None):
                            "an IPD model trains on its channels ipd_ref / ipd_channels.  Default: one microphone")
   parser.add_argument("--mix-room-dims", type=room_dims, default=None, metavar="x,y,z:x,y,z",
                       help="with --mix-room-t60: the smallest and the largest room in metres (default 3,3,2.5:8,6,4)")
+  parser.add_argument("--mix-noise-scp", type=str, default=None, metavar="FILE",
+                      help="with --dynamic-mix: lines of `<noise-id> <path>`: noise recordings (mono 16-bit wav at the working rate); a "
+                           "crop of one is added to every mixture on the GPU (sk_add_noise), and an array mixture gets a diffuse "
+                           "field made of one crop per microphone (sk_diffuse_noise; sepkern/noise.py)")
+  parser.add_argument("--mix-noise-snr", type=noise_snr, default=None, metavar="LO,HI",
+                      help="with --mix-noise-scp: the ratio of the mixture to the noise on the reference channel, uniform in [LO, HI] dB "
+                           "(default -3,6)")
   parser.add_argument("--seed", type=int, default=None, help="seed for weights, shuffling, mixture draws and h0/c0")
   args = parser.parse_args(argv)
   dynamic_mixing(args)
@@ -124,6 +131,17 @@ def rir_synth(text):
   parts = [float(v) for v in text.split(',')]
   if len(parts) != 2 or not 0.0 < parts[0] <= parts[1]:
     raise argparse.ArgumentTypeError("LO,HI with 0 < LO <= HI expected")
+  return (parts[0], parts[1])
+
+
+def noise_snr(text):
+  """--mix-noise-snr LO,HI -> (lo, hi) dB."""
+  try:
+    parts = [float(v) for v in text.split(',')]
+  except ValueError:
+    parts = []
+  if len(parts) != 2 or not parts[0] <= parts[1]:
+    raise argparse.ArgumentTypeError("LO,HI with LO <= HI expected")
   return (parts[0], parts[1])
 
 
@@ -171,14 +189,40 @@ def room_options(args):
 
 
 ROOM_FLAGS = {"room_t60": "--mix-room-t60", "array": "--mix-array", "room_dims": "--mix-room-dims"}
+NOISE_FLAGS = {"noise_scp": "--mix-noise-scp", "noise_snr_db": "--mix-noise-snr"}
+NOISE_NEEDS_DYNAMIC_MIX = "`%s` needs `--dynamic-mix`: the noise is added to mixtures made on the GPU"
+NOISE_NOT_WITH_MIXIT = ("`--mix-noise-scp` does not go with loss=mixit: with noise on it the mixture is no longer the sum of its "
+                        "two references, which is what the mixture-invariant loss assumes")
+
+
+def noise_options(args):
+  """The --mix-noise-* options that were given, as DynMixTrainSet's keyword arguments ({} without any)."""
+  given = {"noise_scp": getattr(args, "mix_noise_scp", None), "noise_snr_db": getattr(args, "mix_noise_snr", None)}
+  return {k: v for k, v in given.items() if v is not None}
+
+
+def noisy_mixing(m, args):
+  """True with --mix-noise-scp.  With loss=mixit the run ends here, not at its first batch; a list that cannot be read or holds a
+  file at another rate ends it when the set is built (dynamic_mix_batches), before any file of the corpus is mixed."""
+  if "noise_scp" not in noise_options(args):
+    return False
+  conf = read_model_conf(args.model_config)
+  if hasattr(m, "parse_loss") and m.parse_loss(conf.get('loss', 'mse')) in getattr(m, "MIXIT_LOSSES", ()):
+    raise SystemExit(NOISE_NOT_WITH_MIXIT)
+  return True
 
 
 def dynamic_mixing(args):
   """True with --dynamic-mix.  The mixtures are made from waveforms: without --wav-input the run ends here, not at its first batch;
-  so does a run with a --mix-rir-* or --mix-room-* option and no --dynamic-mix, with two sources of RIRs, or with an array and
-  no simulated room."""
+  so does a run with a --mix-rir-*, --mix-room-* or --mix-noise-* option and no --dynamic-mix, with two sources of RIRs, with an
+  array and no simulated room, or with a noise level and no noise."""
   rir = reverb_options(args)
   room = [k for k in ("room_t60", "array", "room_dims") if getattr(args, "mix_" + k, None) is not None]
+  noise = noise_options(args)
+  if noise and not getattr(args, "dynamic_mix", False):
+    raise SystemExit(NOISE_NEEDS_DYNAMIC_MIX % NOISE_FLAGS[sorted(noise)[0]])
+  if "noise_snr_db" in noise and "noise_scp" not in noise:
+    raise SystemExit("`--mix-noise-snr` needs `--mix-noise-scp`: there is no noise to set the level of")
   if not getattr(args, "dynamic_mix", False):
     if rir:
       raise SystemExit(NEEDS_DYNAMIC_MIX % ("--mix-" + sorted(rir)[0].replace("_", "-")))
@@ -366,11 +410,16 @@ def dynamic_mix_batches(m, args, rank, world):
   if not hasattr(m, "DynMixTrainSet"):
     raise SystemExit("--dynamic-mix: the arch %s provides no DynMixTrainSet" % getattr(m, "__name__", m))
   seed = mixing_seed(args, rank, world)
-  dataset = m.DynMixTrainSet(args.data_dir, mixed_recordings(m, args),
-                             mixes_per_epoch=args.mixes_per_epoch, snr_db=args.mix_snr_db, peak=args.mix_peak,
-                             max_samples=args.mix_max_samples, seed=seed, sample_rate=getattr(args, "sample_rate", None),
-                             quantize=args.mix_quantize, **reverb_options(args),      # (an arch without RIRs is given none)
-                             **room_options(args), **(getattr(args, "ipd", None) or {}))
+  try:
+    dataset = m.DynMixTrainSet(args.data_dir, mixed_recordings(m, args),
+                               mixes_per_epoch=args.mixes_per_epoch, snr_db=args.mix_snr_db, peak=args.mix_peak,
+                               max_samples=args.mix_max_samples, seed=seed, sample_rate=getattr(args, "sample_rate", None),
+                               quantize=args.mix_quantize, **reverb_options(args),      # (an arch without RIRs is given none)
+                               **room_options(args), **noise_options(args), **(getattr(args, "ipd", None) or {}))
+  except ValueError as e:
+    if "noise" not in str(e) or not noise_options(args):
+      raise
+    raise SystemExit("--mix-noise-scp: %s" % e)
   draws = skdist.MixDraws(dataset.mixes_per_epoch, args.batch_size, rank, world, seed=seed)
   workers = loader_workers(args, world)
   extra = dict(persistent_workers=True, prefetch_factor=2) if workers > 0 else {}
@@ -649,6 +698,7 @@ def main(argv=None):
   args.keep_wave = waveform_loss(m, args)        # (the prefetcher then carries the waveforms with the staged batch)
   args.prefetch_targets = prefetch_targets(m, args)     # (... or stages phase-sensitive targets in place of the source magnitudes)
   args.ipd = ipd_model(m, args)                  # (an IPD model's channels: the loader ships them, the prefetcher stages the wide rows)
+  noisy_mixing(m, args)                          # (--mix-noise-scp with loss=mixit ends the run here)
   torch.cuda.set_device(gpu)
   from sepkern.data import host_threads
   host_threads()                                 # (the arithmetic is on the GPU; see sepkern.data.host_threads)
