@@ -108,4 +108,11 @@ __device__ __forceinline__ void fft256_g16(v2f (&z)[16], float* xch, const float
   dft16(z);  // over n2: z[k2] = Z[j + 16 k2]
 }
 
+// The two tables fft256_g16 and the real split read, into LDS by a workgroup of 256 threads.  No barrier: the caller's next one
+// publishes them.
+__device__ __forceinline__ void fft512_tables(float2* tw, float2* t256, int tid) {
+  for (int i = tid; i < NFFT; i += 256) tw[i] = g_tw512[i];
+  t256[tid] = g_tw512[(2 * (tid & 15) * (tid >> 4)) & 511];
+}
+
 }  // namespace

@@ -90,12 +90,6 @@ __device__ __forceinline__ int fir_find(const FirJob* __restrict__ jobs, int J, 
   return lo;
 }
 
-__device__ __forceinline__ void fir_tables(float2* tw, float2* t256, int tid) {
-  for (int i = tid; i < NFFT; i += 256) tw[i] = g_tw512[i];
-  t256[tid] = g_tw512[(2 * (tid & 15) * (tid >> 4)) & 511];
-  __syncthreads();
-}
-
 // acc += h * x, the same two fmas per part wherever it is formed
 __device__ __forceinline__ v2f fir_cmac(v2f h, v2f x, v2f acc) {
   v2f r;
@@ -113,7 +107,8 @@ __global__ __launch_bounds__(256) void fir_spectra_kernel(const void* __restrict
   __shared__ float2 t256[256];
   __shared__ float xch[16][16 * XLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  fir_tables(tw, t256, tid);
+  fft512_tables(tw, t256, tid);
+  __syncthreads();
   const int l = lane & 15, g = lane >> 4;
   const int t = blockIdx.x * 16 + 4 * wave + g;
   const bool active = t < total;
@@ -173,7 +168,8 @@ __global__ __launch_bounds__(256) void fir_output_kernel(const FirJob* __restric
   __shared__ float2 t256[256];
   __shared__ float xch[16][16 * XLD];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  fir_tables(tw, t256, tid);
+  fft512_tables(tw, t256, tid);
+  __syncthreads();
   const int l = lane & 15, g = lane >> 4;
   const int ob = blockIdx.x * 16 + 4 * wave + g;
   const bool active = ob < total;

@@ -29,12 +29,6 @@ constexpr int MX_WAVES = MX_THREADS / SK_WAVE;
 constexpr int MX_UNROLL = 4;  // samples per source a thread loads before it uses the first
 constexpr double MX_SILENT = 1.0 / 1099511627776.0;  // 2^-40: a source whose mean square is below this gets gain 0
 
-template <bool PCM>
-__device__ __forceinline__ float mx_load(const void* base, unsigned i) {
-  if (PCM) return (float)((const int16_t*)base)[i] * (1.0f / 32768.0f);  // exact
-  return ((const float*)base)[i];
-}
-
 // The samples i0, i0 + 1024, .. (MX_UNROLL of them) of every source, zero beyond the signal's end: all loads of a trip are issued
 // before the first is used, so a thread has MX_UNROLL S loads in flight instead of one (a zero adds nothing to a sum or a maximum).
 template <int S, bool PCM>
@@ -43,11 +37,9 @@ __device__ __forceinline__ void mx_load_trip(const void* const* x, unsigned i0, 
   for (int k = 0; k < MX_UNROLL; ++k) {
     const unsigned i = i0 + (unsigned)k * MX_THREADS;
 #pragma unroll
-    for (int s = 0; s < S; ++s) v[k][s] = (i < n) ? mx_load<PCM>(x[s], i) : 0.f;
+    for (int s = 0; s < S; ++s) v[k][s] = (i < n) ? sk_sample<PCM>(x[s], i) : 0.f;
   }
 }
-
-__device__ __forceinline__ float mx_quant(float v) { return fminf(fmaxf(rintf(v * 32768.0f), -32768.0f), 32767.0f) * (1.0f / 32768.0f); }
 
 template <int S, bool PCM>
 __global__ __launch_bounds__(MX_THREADS) void dynamic_mix_kernel(const void* __restrict__ in, const int64_t* __restrict__ in_offs,
@@ -147,22 +139,11 @@ __global__ __launch_bounds__(MX_THREADS) void dynamic_mix_kernel(const void* __r
       for (int s = 0; s < S; ++s) {
         const float r = G[s] * v[k][s];
         acc = fmaf(G[s], v[k][s], acc);
-        y[1 + s][i] = quantize ? mx_quant(r) : r;
+        y[1 + s][i] = quantize ? sk_quant16(r) : r;
       }
-      y[0][i] = quantize ? mx_quant(acc) : acc;
+      y[0][i] = quantize ? sk_quant16(acc) : acc;
     }
   }
-}
-
-template <int S>
-void mx_launch(bool pcm16, int B, hipStream_t stream, const void* in, const int64_t* in_offs, const int32_t* nsamp,
-               const float* amp, const float* peak, int quantize, float* out, const int64_t* out_offs, float* gains) {
-  if (pcm16)
-    hipLaunchKernelGGL((dynamic_mix_kernel<S, true>), dim3((unsigned)B), dim3(MX_THREADS), 0, stream, in, in_offs, nsamp, B, amp,
-                       peak, quantize, out, out_offs, gains);
-  else
-    hipLaunchKernelGGL((dynamic_mix_kernel<S, false>), dim3((unsigned)B), dim3(MX_THREADS), 0, stream, in, in_offs, nsamp, B, amp,
-                       peak, quantize, out, out_offs, gains);
 }
 
 // ---- the other channels of an array mixture (sk_mix_channels) ------------------------------------------------------------------
@@ -192,7 +173,7 @@ __global__ __launch_bounds__(MC_THREADS) void mix_channels_kernel(const float* _
     float acc = 0.f;
 #pragma unroll
     for (int s = 0; s < S; ++s) acc = fmaf(G[s], x[s][i], acc);
-    y[i] = quantize ? mx_quant(acc) : acc;
+    y[i] = quantize ? sk_quant16(acc) : acc;
   }
 }
 
@@ -225,12 +206,16 @@ extern "C" int sk_dynamic_mix(const void* in, int pcm16, const int64_t* in_offs,
   const hipStream_t st = (hipStream_t)stream;
   const bool p = pcm16 != 0;
   const int qz = quantize != 0;
-  switch (S) {
-    case 1: mx_launch<1>(p, B, st, in, in_offs, nsamp, amp, peak, qz, out, out_offs, gains); break;
-    case 2: mx_launch<2>(p, B, st, in, in_offs, nsamp, amp, peak, qz, out, out_offs, gains); break;
-    case 3: mx_launch<3>(p, B, st, in, in_offs, nsamp, amp, peak, qz, out, out_offs, gains); break;
-    default: mx_launch<4>(p, B, st, in, in_offs, nsamp, amp, peak, qz, out, out_offs, gains); break;
-  }
+  sk_dispatch_int<1, SK_MAXS>(S, [&](auto s) {
+    constexpr int SS = decltype(s)::value;
+    if (p)
+      hipLaunchKernelGGL((dynamic_mix_kernel<SS, true>), dim3((unsigned)B), dim3(MX_THREADS), 0, st, in, in_offs, nsamp, B, amp, peak, qz,
+                         out, out_offs, gains);
+    else
+      hipLaunchKernelGGL((dynamic_mix_kernel<SS, false>), dim3((unsigned)B), dim3(MX_THREADS), 0, st, in, in_offs, nsamp, B, amp, peak, qz,
+                         out, out_offs, gains);
+    return 0;
+  });
   SK_CHECK_LAUNCH("sk_dynamic_mix");
   return SK_OK;
 }

@@ -113,8 +113,7 @@ __global__ __launch_bounds__(256) void diffuse_noise_kernel(const void* __restri
   const int i_lo = q * NZ_TILE;
   if (i_lo >= n) return;   // (the whole workgroup: no barrier has been met)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int i = tid; i < NFFT; i += 256) tw[i] = g_tw512[i];
-  t256[tid] = g_tw512[(2 * (tid & 15) * (tid >> 4)) & 511];
+  fft512_tables(tw, t256, tid);   // (published by the barrier behind the first channel's samples)
   const float* const Lu = L + (int64_t)u * NBIN * TRI;
   const int l = lane & 15, g = lane >> 4, grp = 4 * wave + g;
   const int partner = (lane & 48) | ((16 - l) & 15);
@@ -243,14 +242,6 @@ constexpr int AN_THREADS = 1024;
 constexpr int AN_WAVES = AN_THREADS / SK_WAVE;
 
 template <bool PCM>
-__device__ __forceinline__ float an_load(const void* base, unsigned i) {
-  if (PCM) return (float)((const int16_t*)base)[i] * (1.0f / 32768.0f);  // exact
-  return ((const float*)base)[i];
-}
-
-__device__ __forceinline__ float an_quant(float v) { return fminf(fmaxf(rintf(v * 32768.0f), -32768.0f), 32767.0f) * (1.0f / 32768.0f); }
-
-template <bool PCM>
 __global__ __launch_bounds__(AN_THREADS) void add_noise_kernel(float* __restrict__ sig, const int64_t* __restrict__ sig_offs,
                                                                const void* __restrict__ noise, const int64_t* __restrict__ noise_offs,
                                                                const int32_t* __restrict__ nsamp, int B, int C,
@@ -266,7 +257,7 @@ __global__ __launch_bounds__(AN_THREADS) void add_noise_kernel(float* __restrict
     const void* const v = PCM ? (const void*)((const int16_t*)noise + o) : (const void*)((const float*)noise + o);
     double sy = 0.0, sv = 0.0;
     for (unsigned i = tid; i < n; i += AN_THREADS) {
-      const double a = (double)y[i], b = (double)an_load<PCM>(v, i);
+      const double a = (double)y[i], b = (double)sk_sample<PCM>(v, i);
       sy += a * a;
       sv += b * b;
     }
@@ -296,8 +287,8 @@ __global__ __launch_bounds__(AN_THREADS) void add_noise_kernel(float* __restrict
     const int64_t o = noise_offs[c * B + u];
     const void* const v = PCM ? (const void*)((const int16_t*)noise + o) : (const void*)((const float*)noise + o);
     for (unsigned i = tid; i < n; i += AN_THREADS) {
-      const float r = fmaf(a, an_load<PCM>(v, i), y[i]);
-      y[i] = quantize ? an_quant(r) : r;
+      const float r = fmaf(a, sk_sample<PCM>(v, i), y[i]);
+      y[i] = quantize ? sk_quant16(r) : r;
     }
   }
 }

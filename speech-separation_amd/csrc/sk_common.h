@@ -95,6 +95,17 @@ __device__ __forceinline__ float sk_block_sum256(float v, float* red /* >= 4 flo
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// ---- what the waveform-batch kernels (mix.hip, noise.hip) share ---------------------------------------------------------------
+// sample i of a signal: float32 as it is, int16 PCM scaled by 1/32768 (exact)
+template <bool PCM>
+__device__ __forceinline__ float sk_sample(const void* base, unsigned i) {
+  if (PCM) return (float)((const int16_t*)base)[i] * (1.0f / 32768.0f);
+  return ((const float*)base)[i];
+}
+
+// v on the int16 grid: what a 16-bit wav file would hand back
+__device__ __forceinline__ float sk_quant16(float v) { return fminf(fmaxf(rintf(v * 32768.0f), -32768.0f), 32767.0f) * (1.0f / 32768.0f); }
+
 // Lexicographic permutation number `idx` of {0..S-1} (itertools.permutations order), S <= SK_MAXS: element i of the
 // permutation in bits 2i, 2i+1 of the result (no arrays: nothing a kernel would keep in scratch).
 #define SK_MAXS 4

@@ -101,68 +101,96 @@ def _room_jobs(room, S, B):
   return rooms, betas, ss, ms, scales, ntaps, delays
 
 
+def _to_device(t, dev):
+  """A tensor on `dev`: as it came if it is there, else ONE pinned host-to-device copy, asynchronous on the current stream."""
+  import torch
+  if t.device == torch.device(dev):
+    return t
+  return (t if t.is_pinned() else t.pin_memory()).to(dev, non_blocking=True)
+
+
+def key_offsets(ns, which):
+  """The offsets of a key-major batch: the signal with index q among the batch's keys holds utterance j at
+  q * sum(ns) + sum(ns[:j]) -> [[offset of utterance j] for q in which]: what the ops wrappers take as offsets [list][B]."""
+  from .ops import prefix_sums
+  starts, total = prefix_sums(ns)
+  return [[q * total + st for st in starts] for q in which]
+
+
+def _staged(pcm, dev):
+  """The head the front ends below share: a batch still to be mixed is mixed (mixed_pcm), the samples cross to the device in one
+  copy and signals at another rate are resampled (_at_target_rate) -> (pcm as the front end goes on with it, src, flat, ns):
+  flat and ns are the working-rate samples and their counts, src the tensor that crossed -- flat itself unless a signal was
+  resampled -- whose use on the current stream the caller records."""
+  if 'mixing' in pcm:                                  # DynMixCollator: the mixture is made here, on the device
+    pcm = mixed_pcm(pcm, dev)
+  src = _to_device(pcm['flat'], dev)
+  flat, ns = _at_target_rate(pcm, src)
+  return pcm, src, flat, ns
+
+
 def mixed_pcm(pcm, dev):
   """A DynMixCollator batch -- pcm carries 'mixing' = {'amp': [S][B], 'peak': [B], 'quantize'} and the int16 samples of the
-  SOURCES only, keys 'source1' .. 'source<S>', no 'mix' -- mixed on the device (ops.dynamic_mix: one sk_dynamic_mix launch;
-  sepkern/mixing.py states the rule) -> an ordinary pcm dict ON the device: 'flat' float32 in WavCollator's layout, 'keys' =
-  ['mix', 'source1', ...], 'lens', no 'rate'.  One pinned H2D copy of the samples.  With 'rate' / 'target_rate' and an utterance
-  at another rate the sources are resampled first (ops.pcm_to_rate) and a mixture is as long as its shortest resampled source.
-  With 'reverb' = {'flat': float32 tensor of all RIRs, 'offs' / 'taps' / 'delay': [S][B]} every source is then convolved with its
-  RIR (ops.fir_convolve: one sk_fir_convolve call over the S B signals; sepkern/reverb.py) and the levels are set on the
-  reverberant signals: the targets are the reverberant sources.  A batch without 'reverb' takes the path it took before.
-  With 'room' (DynMixTrainSet(room_t60=...): per mixture the fp64 geometry of a simulated room, C = 1 + P microphones -- the
-  reference, then the listed channels 'chans') the image-method RIRs from every source to every microphone are made first
-  (ops.room_rirs: one sk_room_rirs launch over the S C B jobs; sepkern/room.py), ONE ops.fir_convolve convolves the S C B
-  signals (the channels of a source share its dry signal), ops.dynamic_mix sets the levels on the reference channel and one
-  ops.mix_channels forms the P other channels' mixtures at those gains: 'keys' = ['mix', 'source1', ..., 'chan<c>', ...], what
-  WavCollator gives for an array recording.  Levels and peak are defined on the reference channel; another channel may exceed
-  the peak.  A batch without 'room' takes the path it took before, launch for launch.
-  With 'noise' (DynMixTrainSet(noise_scp=...): {'flat': int16 crops, channel-major, 'lens', 'amp': [B]}; sepkern/noise.py) noise is
-  added after all that, in place: to a batch of one channel -- plain, reverberant or a mono room -- the crop itself by ONE
-  ops.add_noise; to an array batch a diffuse field, ops.noise_factors from the room's microphones, ops.diffuse_noise over the C
-  crops, then ONE ops.add_noise over 'mix' and the 'chan<c>' signals at the reference channel's gain.  'source<s>' stay as they
-  are: the targets are clean.  A batch without 'noise' takes the path it took before, launch for launch.
+  SOURCES only, keys 'source1' .. 'source<S>', no 'mix' -- mixed on the device -> an ordinary pcm dict ON the device: 'flat'
+  float32 in WavCollator's layout, 'keys' = ['mix', 'source1', ..., 'chan<c>', ...], 'lens', no 'rate'.  One pinned H2D copy of
+  the samples, then ONE pipeline whose stages a batch switches on by what it carries; a stage it does not carry costs no launch:
+    1. 'rate' / 'target_rate' with an utterance at another rate: the sources resampled (ops.pcm_to_rate); a mixture is as long
+       as its shortest resampled source;
+    2. RIRs for S C B jobs, source-major, then microphone, then mixture: GIVEN with 'reverb' = {'flat': float32 tensor of all
+       RIRs, 'offs' / 'taps' / 'delay': [S][B]} (C = 1; sepkern/reverb.py) or MADE with 'room' (per mixture the fp64 geometry of a
+       simulated room and C = 1 + P microphones, the reference, then the listed 'chans': _room_jobs, then ONE ops.room_rirs;
+       sepkern/room.py) -- not both;
+    3. with RIRs, ONE ops.fir_convolve over the jobs (the channels of a source share its dry signal): the targets are the
+       reverberant sources;
+    4. ONE ops.dynamic_mix (sepkern/mixing.py states the rule) sets the levels on the reference channel, into a buffer of
+       (S + 1 + P) sum(lens) samples;
+    5. with P listed channels, ONE ops.mix_channels forms their mixtures at those gains behind it: levels and peak are
+       defined on the reference channel, another channel may exceed the peak;
+    6. with 'noise' (sepkern/noise.py), noise added in place to the mixture's channels, the sources stay clean: _with_noise.
   The front ends below start with this and go on as they do for a batch that came mixed from disk; enqueued on the CURRENT
   stream."""
   import torch
   from . import ops
+  from .ipd import chan_key
   mixing, keys = pcm['mixing'], list(pcm['keys'])
   S, ns = len(keys), [int(n) for n in pcm['lens']]
+  B = len(ns)
   if keys != ['source' + str(s + 1) for s in range(S)]:
     raise ValueError("mixed_pcm: a batch to be mixed holds the signals 'source1' .. 'source<S>' (got %r)" % keys)
-  flat = pcm['flat']
-  if flat.device != torch.device(dev):
-    flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
-  src = flat
-  total = sum(ns)
-  starts = [sum(ns[:j]) for j in range(len(ns))]
-  offs = [[s * total + st for st in starts] for s in range(S)]
+  src = flat = _to_device(pcm['flat'], dev)
+  offs = key_offsets(ns, range(S))
   rates, target = pcm.get('rate'), pcm.get('target_rate')
   if rates is not None and target is not None and any(int(r) != int(target) for r in rates):
     flat, outs = ops.pcm_to_rate(flat, ns * S, [int(r) for r in rates] * S, target)
-    ends = [sum(outs[:k]) for k in range(len(outs))]
-    offs = [ends[s * len(ns):(s + 1) * len(ns)] for s in range(S)]
-    ns = [min(outs[s * len(ns) + j] for s in range(S)) for j in range(len(ns))]
+    ends = ops.prefix_sums(outs)[0]
+    offs = [ends[s * B:(s + 1) * B] for s in range(S)]
+    ns = [min(outs[s * B + j] for s in range(S)) for j in range(B)]
   rv, room = pcm.get('reverb'), pcm.get('room')
+  if room is not None and rv is not None:
+    raise ValueError("mixed_pcm: a batch carries 'room' or 'reverb', not both")
+  chans = list(room.get('chans', ())) if room is not None else []
+  P = len(chans)
+  C, held, rirs = 1 + P, [src, flat], None
   if room is not None:
-    if rv is not None:
-      raise ValueError("mixed_pcm: a batch carries 'room' or 'reverb', not both")
-    return _with_noise(_mixed_in_rooms(flat, src, offs, ns, keys, mixing, room, dev), pcm.get('noise'), mixing, room, dev)
-  if rv is not None:      # reverberant sources: ONE sk_fir_convolve launch pair over all S B signals; the levels are set on its result
-    rirs = rv['flat']
-    if rirs.device != torch.device(dev):
-      rirs = (rirs if rirs.is_pinned() else rirs.pin_memory()).to(dev, non_blocking=True)
-    B = len(ns)
-    dry = flat
-    flat, at = ops.fir_convolve(dry, [o for row in offs for o in row], ns * S, rirs, [o for row in rv['offs'] for o in row],
-                                [t for row in rv['taps'] for t in row], [d for row in rv['delay'] for d in row])
-    offs = [at[s * B:(s + 1) * B] for s in range(S)]
-    dry.record_stream(torch.cuda.current_stream(dev))
-    rirs.record_stream(torch.cuda.current_stream(dev))
-  out, _ = ops.dynamic_mix(flat, offs, ns, mixing['amp'], mixing['peak'], quantize=bool(mixing.get('quantize', False)))
-  src.record_stream(torch.cuda.current_stream(dev))
-  flat.record_stream(torch.cuda.current_stream(dev))
-  return _with_noise({'flat': out, 'keys': ['mix'] + keys, 'lens': ns}, pcm.get('noise'), mixing, None, dev)
+    rooms, betas, ss, ms, scales, taps, delays = _room_jobs(room, S, B)
+    rirs, roffs = ops.room_rirs(rooms, betas, ss, ms, taps, room['rate'], scales=scales, device=dev)
+  elif rv is not None:
+    rirs = _to_device(rv['flat'], dev)
+    roffs, taps, delays = ([v for row in rv[k] for v in row] for k in ('offs', 'taps', 'delay'))
+  if rirs is not None:      # ONE sk_fir_convolve launch pair over all S C B signals; the levels are set on its result
+    flat, at = ops.fir_convolve(flat, [offs[s][b] for s in range(S) for _ in range(C) for b in range(B)], ns * (S * C), rirs, roffs, taps, delays)
+    held += [rirs, flat]
+    job = lambda s, c: at[(s * C + c) * B:(s * C + c + 1) * B]  # noqa: E731
+    offs, chan_offs = [job(s, 0) for s in range(S)], [[job(s, 1 + p) for p in range(P)] for s in range(S)]
+  total, quant = sum(ns), bool(mixing.get('quantize', False))
+  out = torch.empty((S + 1 + P) * total, dtype=torch.float32, device=flat.device)
+  _, gains = ops.dynamic_mix(flat, offs, ns, mixing['amp'], mixing['peak'], quantize=quant, out=out)
+  if P:
+    ops.mix_channels(flat, chan_offs, ns, gains, quantize=quant, out=out[(S + 1) * total:])
+  cur = torch.cuda.current_stream(dev)
+  for t in held:
+    t.record_stream(cur)
+  return _with_noise({'flat': out, 'keys': ['mix'] + keys + [chan_key(c) for c in chans], 'lens': ns}, pcm.get('noise'), mixing, room, dev)
 
 
 def _with_noise(mixed, nz, mixing, room, dev):
@@ -174,8 +202,7 @@ def _with_noise(mixed, nz, mixing, room, dev):
   from . import ops
   from .ipd import chan_keys
   keys, ns, out = mixed['keys'], mixed['lens'], mixed['flat']
-  B, total = len(ns), sum(ns)
-  starts = [sum(ns[:j]) for j in range(B)]
+  B = len(ns)
   chans = ['mix'] + chan_keys(keys)
   C = len(chans)
   nl = [int(v) for v in nz['lens']]
@@ -183,11 +210,8 @@ def _with_noise(mixed, nz, mixing, room, dev):
   if len(nl) != B or len(nz['amp']) != B or crops.numel() != C * sum(nl) or any(a < b for a, b in zip(nl, ns)):
     raise ValueError("mixed_pcm: 'noise' holds one crop per channel (%d) and mixture (%d), each at least as long as its mixture, "
                      "and one amplitude per mixture" % (C, B))
-  if crops.device != torch.device(dev):
-    crops = (crops if crops.is_pinned() else crops.pin_memory()).to(dev, non_blocking=True)
-  nstarts = [sum(nl[:j]) for j in range(B)]
-  noffs = [[c * sum(nl) + st for st in nstarts] for c in range(C)]
-  soffs = [[keys.index(k) * total + st for st in starts] for k in chans]
+  crops = _to_device(crops, dev)
+  noffs, soffs = key_offsets(nl, range(C)), key_offsets(ns, [keys.index(k) for k in chans])
   quant = bool(mixing.get('quantize', False))
   cur = torch.cuda.current_stream(dev)
   if C == 1:
@@ -195,35 +219,11 @@ def _with_noise(mixed, nz, mixing, room, dev):
   else:
     L = ops.noise_factors(room['mics'], room['rate'], device=dev)
     field = ops.diffuse_noise(crops, noffs, ns, L)
-    ops.add_noise(out, soffs, field, [[c * total + st for st in starts] for c in range(C)], ns, nz['amp'], quantize=quant)
+    ops.add_noise(out, soffs, field, key_offsets(ns, range(C)), ns, nz['amp'], quantize=quant)
     L.record_stream(cur)
     field.record_stream(cur)
   crops.record_stream(cur)
   return mixed
-
-
-def _mixed_in_rooms(flat, src, offs, ns, keys, mixing, room, dev):
-  """mixed_pcm's tail for a batch with 'room': flat = the dry sources at the working rate, offs[s][b] their offsets."""
-  import torch
-  from . import ops
-  from .ipd import chan_key
-  S, B, P = len(keys), len(ns), len(room.get('chans', ()))
-  C = 1 + P
-  rooms, betas, ss, ms, scales, ntaps, delays = _room_jobs(room, S, B)
-  rirs, roffs = ops.room_rirs(rooms, betas, ss, ms, ntaps, room['rate'], scales=scales, device=dev)
-  wet, at = ops.fir_convolve(flat, [offs[s][b] for s in range(S) for _ in range(C) for b in range(B)], ns * (S * C), rirs, roffs, ntaps, delays)
-  job = lambda s, c: at[(s * C + c) * B:(s * C + c + 1) * B]  # noqa: E731
-  total = sum(ns)
-  out = torch.empty((S + 1 + P) * total, dtype=torch.float32, device=wet.device)
-  _, gains = ops.dynamic_mix(wet, [job(s, 0) for s in range(S)], ns, mixing['amp'], mixing['peak'],
-                             quantize=bool(mixing.get('quantize', False)), out=out)
-  if P:
-    ops.mix_channels(wet, [[job(s, 1 + p) for p in range(P)] for s in range(S)], ns, gains,
-                     quantize=bool(mixing.get('quantize', False)), out=out[(S + 1) * total:])
-  cur = torch.cuda.current_stream(dev)
-  for t in (src, flat, rirs, wet):
-    t.record_stream(cur)
-  return {'flat': out, 'keys': ['mix'] + keys + [chan_key(c) for c in room.get('chans', ())], 'lens': ns}
 
 
 def features_from_pcm(pcm, dev):
@@ -235,13 +235,7 @@ def features_from_pcm(pcm, dev):
   import torch
   from . import ops
   from .packing import Packing
-  if 'mixing' in pcm:                                  # DynMixCollator: the mixture is made here, on the device
-    pcm = mixed_pcm(pcm, dev)
-  flat = pcm['flat']
-  if flat.device != torch.device(dev):
-    flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
-  src = flat
-  flat, ns = _at_target_rate(pcm, flat)                # (another tensor only when a signal had to be resampled)
+  pcm, src, flat, ns = _staged(pcm, dev)                # (another tensor only when a signal had to be resampled)
   B, F = len(ns), 257
   pk = Packing.from_lens([1 + n // 128 for n in ns], dev)
   feats, at, total = [], 0, sum(ns)
@@ -267,19 +261,12 @@ def wave_features_from_pcm(pcm, dev, source_mags=True):
   import torch
   from . import ops
   from .packing import Packing
-  if 'mixing' in pcm:                                  # DynMixCollator: the mixture is made here, on the device
-    pcm = mixed_pcm(pcm, dev)
-  flat = pcm['flat']
-  if flat.device != torch.device(dev):
-    flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
-  src = flat
-  flat, ns = _at_target_rate(pcm, flat)                # resampled: float32 signals and their counts from here on
+  pcm, src, flat, ns = _staged(pcm, dev)                # resampled: float32 signals and their counts from here on
   B, F = len(ns), 257
   pk = Packing.from_lens([1 + n // 128 for n in ns], dev)
   if pk.perm is not None:
     raise ValueError("wave_features_from_pcm: the batch must be sorted by frame count, longest first (WavCollator does)")
   total = sum(ns)
-  starts = [sum(ns[:j]) for j in range(B)]
   grid = dict(lengths=ns, out_offs=[b * F for b in range(B)], stride_t=[B * F] * B, stride_f=[1] * B)
   feats = []
   for q, _ in enumerate(signal_keys(pcm['keys']) if source_mags else pcm['keys'][:1]):
@@ -292,7 +279,7 @@ def wave_features_from_pcm(pcm, dev, source_mags=True):
   src.record_stream(torch.cuda.current_stream(dev))
   flat.record_stream(torch.cuda.current_stream(dev))
   wave = {'mixc': mixc, 'flat': flat, 'nsamp': ns,
-          'sig_offs': {k: [q * total + st for st in starts] for q, k in enumerate(pcm['keys'])}}
+          'sig_offs': dict(zip(pcm['keys'], key_offsets(ns, range(len(pcm['keys'])))))}
   return feats[0], feats[1:], pk, wave
 
 
@@ -309,21 +296,14 @@ def psa_features_from_pcm(pcm, dev, clamp=False):
   import torch
   from . import ops
   from .packing import Packing
-  if 'mixing' in pcm:                                  # DynMixCollator: the mixture is made here, on the device
-    pcm = mixed_pcm(pcm, dev)
-  flat = pcm['flat']
-  if flat.device != torch.device(dev):
-    flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
-  src = flat
-  flat, ns = _at_target_rate(pcm, flat)                # (another tensor only when a signal had to be resampled)
-  nk, total = len(signal_keys(pcm['keys'])), sum(ns)
+  pcm, src, flat, ns = _staged(pcm, dev)                # (another tensor only when a signal had to be resampled)
+  nk = len(signal_keys(pcm['keys']))
   if nk < 2:
     raise ValueError("psa_features_from_pcm: the batch holds no source waveform")
   pk = Packing.from_lens([1 + n // 128 for n in ns], dev)
   if pk.perm is not None:
     raise ValueError("psa_features_from_pcm: the batch must be sorted by frame count, longest first (WavCollator does)")
-  starts = [sum(ns[:j]) for j in range(len(ns))]
-  mix, targets = ops.stft_psa(flat, [[q * total + st for st in starts] for q in range(nk)], ns, nk - 1, pk=pk, clamp=clamp)
+  mix, targets = ops.stft_psa(flat, key_offsets(ns, range(nk)), ns, nk - 1, pk=pk, clamp=clamp)
   src.record_stream(torch.cuda.current_stream(dev))
   flat.record_stream(torch.cuda.current_stream(dev))
   return mix, targets, pk
@@ -340,23 +320,15 @@ def ipd_rows_from_pcm(pcm, dev, front=features_from_pcm, **front_args):
   import torch
   from . import ops
   from .ipd import chan_keys
-  if 'mixing' in pcm:
+  if 'mixing' in pcm:                    # simulated rooms with listed channels: mixed first (_staged), an array batch from there on
     if not batch_chan_keys(pcm):
       raise ValueError("ipd_rows_from_pcm: a batch mixed on the device (--dynamic-mix) has one channel")
-    pcm = mixed_pcm(pcm, dev)            # simulated rooms with listed channels: mixed first, an array batch from here on
+  elif not chan_keys(pcm['keys']) or pcm['keys'][0] != 'mix':
+    raise ValueError("ipd_rows_from_pcm: the batch holds no 'chan<c>' signals behind 'mix' (got %r)" % list(pcm['keys']))
+  pcm, src, flat, ns = _staged(pcm, dev)
   keys = list(pcm['keys'])
-  chans = chan_keys(keys)
-  if not chans or keys[0] != 'mix':
-    raise ValueError("ipd_rows_from_pcm: the batch holds no 'chan<c>' signals behind 'mix' (got %r)" % keys)
-  flat = pcm['flat']
-  if flat.device != torch.device(dev):
-    flat = (flat if flat.is_pinned() else flat.pin_memory()).to(dev, non_blocking=True)
-  src = flat
-  flat, ns = _at_target_rate(pcm, flat)
   res = front({'flat': flat, 'keys': keys, 'lens': ns}, dev, **front_args)
-  pk, total = res[2], sum(ns)
-  starts = [sum(ns[:j]) for j in range(len(ns))]
-  wide, _ = ops.stft_ipd(flat, [[keys.index(k) * total + st for st in starts] for k in ['mix'] + chans], ns, pk=pk, want_mix=False)
+  wide, _ = ops.stft_ipd(flat, key_offsets(ns, [keys.index(k) for k in ['mix'] + chan_keys(keys)]), ns, pk=res[2], want_mix=False)
   src.record_stream(torch.cuda.current_stream(dev))
   flat.record_stream(torch.cuda.current_stream(dev))
   return res, wide

@@ -4,6 +4,7 @@ PyTorch supplies device memory and the current HIP stream; all arithmetic is in 
 Every wrapper takes fp32 CUDA tensors and passes raw device pointers.
 """
 import ctypes as C
+import itertools
 
 import torch
 
@@ -283,11 +284,91 @@ def pick_splitk_bf16(M, N, K, batch=1):
     return best
 
 
-# ----------------------------------------------------------------------------- STFT / iSTFT
+# ----------------------------------------------------------------------------- signal batches
+# ONE flat 1-D tensor of samples, nested lists of offsets [list][B] into it and the samples per utterance: what every wrapper
+# that takes such a batch checks and builds, stated once.  `who` is the wrapper's name, for the message.  The descriptor tensors
+# must outlive the (asynchronous) launch call: a wrapper keeps its references until the call returns.
 def _i64(vals, device):
     return torch.tensor(vals, dtype=torch.int64, device=device)
 
 
+def _i32(vals, device):
+    return torch.tensor(vals, dtype=torch.int32, device=device)
+
+
+def _samples(who, t, what="samples", pcm=True):
+    """t holds samples: on the device, 1-D, contiguous, float32 or (pcm) int16 PCM, which the kernels scale by 1/32768 -> pcm16."""
+    pcm16 = pcm and t.dtype == torch.int16
+    _chk(t, torch.int16 if pcm16 else torch.float32)
+    if t.dim() != 1 or not t.is_contiguous():
+        raise _lib.SepkernError("%s needs one contiguous 1-D tensor of %s (got strides %s for shape %s)" % (who, what, tuple(t.stride()), tuple(t.shape)))
+    return pcm16
+
+
+def prefix_sums(ns):
+    """Lengths -> (where each begins when they lie back to back, their sum): one linear prefix sum."""
+    starts = list(itertools.accumulate(ns, initial=0))
+    total = starts.pop()
+    return starts, total
+
+
+def _lengths(who, nsamp, least=None, what="signal"):
+    """nsamp -> (ns, starts, total); an empty batch is refused, and a length below `least` (None: the C side refuses short ones)."""
+    ns = [int(n) for n in nsamp]
+    if not ns or (least is not None and min(ns) < least):
+        raise _lib.SepkernError("%s needs at least one %s%s" % (who, what, "" if least is None else ", each of at least %d samples" % least))
+    return (ns,) + prefix_sums(ns)
+
+
+def _offsets(who, offs, ns, numel, *counts):
+    """Nested offset lists (any iterables) -> (the flat list in the order the kernels read them: the outermost list slowest, the
+    B = len(ns) utterances fastest; then the number of lists found at every level).  counts: one (lo, hi, what) per level of
+    lists above [B] -- none for a plain [B] list, one for [S][B], two for [S][P][B] --, the range their number must lie in and
+    what they are, for the message; every list of a level is as long as the first.  Signal u of every innermost list is the
+    ns[u] samples at its offset and must lie inside the buffer of numel elements (a negative length is refused here)."""
+    rows, B, found = [offs], len(ns), []
+    for lo, hi, what in counts:
+        rows = [list(r) for r in rows]
+        n = len(rows[0])
+        if not lo <= n <= hi or any(len(r) != n for r in rows):
+            raise _lib.SepkernError("%s needs %s lists of offsets, one per %s, each with one offset for each of the %d signals (got %d)"
+                                    % (who, lo if lo == hi else "%d..%d" % (lo, hi), what, B, n))
+        found.append(n)
+        rows = [x for r in rows for x in r]
+    rows = [[int(o) for o in r] for r in rows]
+    if any(len(r) != B for r in rows):
+        raise _lib.SepkernError("%s needs one offset per signal: lists of %d (got %s)" % (who, B, sorted({len(r) for r in rows})))
+    if min(ns) < 0 or any(o < 0 or o + n > numel for r in rows for o, n in zip(r, ns)):
+        raise _lib.SepkernError("%s: a signal runs past its buffer (or has a negative offset or length)" % who)
+    return ([o for r in rows for o in r], *found)
+
+
+def _out(who, out, size, like):
+    """A flat float32 buffer of at least `size` elements on the device of `like`: a new one, or the caller's, checked."""
+    if out is None:
+        return torch.empty(size, dtype=torch.float32, device=like.device)
+    _chk(out)
+    if out.dim() != 1 or not out.is_contiguous() or out.numel() < size or out.device != like.device:
+        raise _lib.SepkernError("%s: out must be a contiguous 1-D float32 tensor of at least %d samples on the samples' device" % (who, size))
+    return out
+
+
+def _row_layout(who, ns, pk):
+    """Where the frames of signals of ns samples go as rows -> (Ts, rows, rows_p, bases).  With pk, the batch's Packing: its packed
+    rows (bases None) -- it has no perm and its frame counts are the signals'; without: utterance u's T_u = 1 + ns[u] // 128 rows
+    start at bases[u] = sum_{v<u} T_v."""
+    Ts = [1 + n // 128 for n in ns]
+    if pk is None:
+        bases, rows = prefix_sums(Ts)
+        return Ts, rows, rows, bases
+    if pk.perm is not None:
+        raise _lib.SepkernError("%s needs a length-sorted batch (Packing without perm)" % who)
+    if pk.B != len(ns) or [int(t) for t in pk.lens_host] != Ts:
+        raise _lib.SepkernError("%s: the Packing's frame counts are not those of the signals" % who)
+    return Ts, pk.R, pk.Rp, None
+
+
+# ----------------------------------------------------------------------------- STFT / iSTFT
 def stft_batch(wavs, want_complex=False, layout="TF", out=None, out_offs=None, stride_t=None, stride_f=None, lengths=None, repeat=1):
     """STFT (n_fft 512, hop 128, reflect-centred, periodic Hann) of a list of 1-D waveforms.
 
@@ -299,12 +380,11 @@ def stft_batch(wavs, want_complex=False, layout="TF", out=None, out_offs=None, s
     repeat (bench.py's aux leg): the launch is enqueued that many times back to back (same result) between the profile's events.
     """
     if lengths is not None:
-        cat = wavs.contiguous()
-        ns = [int(n) for n in lengths]
-        dev, pcm16 = cat.device, cat.dtype == torch.int16
-        _chk(cat, torch.int16 if pcm16 else torch.float32)
-        if cat.dim() != 1 or sum(ns) != cat.numel() or min(ns) <= 256:
-            raise _lib.SepkernError("stft needs 1-D waveforms longer than n_fft/2 samples (and lengths that add up)")
+        cat, dev = wavs, wavs.device
+        pcm16 = _samples("stft", cat)
+        ns, woffs, total = _lengths("stft", lengths, 257, "waveform longer than n_fft/2 samples")
+        if total != cat.numel():
+            raise _lib.SepkernError("stft needs lengths that add up to the tensor of samples")
     else:
         dev = wavs[0].device
         pcm16 = wavs[0].dtype == torch.int16
@@ -313,27 +393,18 @@ def stft_batch(wavs, want_complex=False, layout="TF", out=None, out_offs=None, s
             if w.dim() != 1 or w.numel() <= 256:
                 raise _lib.SepkernError("stft needs 1-D waveforms longer than n_fft/2 samples")
         ns = [int(w.numel()) for w in wavs]
-        cat = torch.cat(wavs) if len(wavs) > 1 else wavs[0].contiguous()
+        cat, woffs = torch.cat(wavs) if len(wavs) > 1 else wavs[0].contiguous(), prefix_sums(ns)[0]
     Ts = [1 + n // 128 for n in ns]
-    woffs, acc = [], 0
-    for n in ns:
-        woffs.append(acc)
-        acc += n
     F = 257
     ret = None
     if out is None:
         odt = torch.complex64 if want_complex else torch.float32
-        total = sum(Ts) * F
-        out = torch.empty(total, dtype=odt, device=dev)
-        out_offs, stride_t, stride_f, acc = [], [], [], 0
-        for T in Ts:
-            out_offs.append(acc)
-            stride_t.append(F if layout == "TF" else 1)
-            stride_f.append(1 if layout == "TF" else T)
-            acc += T * F
+        out_offs, size = prefix_sums([T * F for T in Ts])
+        out = torch.empty(size, dtype=odt, device=dev)
+        stride_t = [F if layout == "TF" else 1 for T in Ts]
+        stride_f = [1 if layout == "TF" else T for T in Ts]
         ret = [out[o:o + T * F].view((T, F) if layout == "TF" else (F, T)) for o, T in zip(out_offs, Ts)]
-    # descriptor arrays must outlive the (asynchronous) launch call: keep references until it returns
-    d_woffs, d_ns = _i64(woffs, dev), torch.tensor(ns, dtype=torch.int32, device=dev)
+    d_woffs, d_ns = _i64(woffs, dev), _i32(ns, dev)
     d_ooffs, d_st, d_sf = _i64(out_offs, dev), _i64(stride_t, dev), _i64(stride_f, dev)
     frame_major = all(int(v) == 1 for v in stride_f)
     # algorithmic bytes: 128 new samples in, 257 bins out per frame
@@ -350,26 +421,19 @@ def resample_into(src, in_offs, n_in, out, out_offs, n_out, sr_in, sr_out, repea
     (sepkern/resample.py defines the arithmetic and holds the tap table).  Nothing else of `out` is written.  Any number of
     signals: the kernel takes 65535 per launch, more go in as many launches."""
     from . import resample as rs
-    pcm16 = src.dtype == torch.int16
-    _chk(src, torch.int16 if pcm16 else torch.float32)
-    _chk(out)
-    in_offs, n_in, out_offs, n_out = ([int(v) for v in a] for a in (in_offs, n_in, out_offs, n_out))
+    pcm16 = _samples("resample_into", src)
+    _samples("resample_into", out, "output samples", pcm=False)
+    n_in, n_out = _lengths("resample_into", n_in, 0)[0], _lengths("resample_into", n_out, 0)[0]
     nsig = len(n_in)
-    if src.dim() != 1 or out.dim() != 1 or not src.is_contiguous() or not out.is_contiguous():
-        raise _lib.SepkernError("resample: source and destination must be contiguous 1-D tensors")
-    if nsig == 0 or not (len(in_offs) == len(out_offs) == len(n_out) == nsig):
-        raise _lib.SepkernError("resample: one offset and one length per signal, in and out")
-    if any(o < 0 or n < 0 or o + n > src.numel() for o, n in zip(in_offs, n_in)) or \
-            any(o < 0 or n < 0 or o + n > out.numel() for o, n in zip(out_offs, n_out)):
-        raise _lib.SepkernError("resample: a signal runs past its buffer")
+    if len(n_out) != nsig:
+        raise _lib.SepkernError("resample_into: one length per signal, in and out")
+    in_offs, = _offsets("resample_into", in_offs, n_in, src.numel())
+    out_offs, = _offsets("resample_into", out_offs, n_out, out.numel())
     if max(n_out) == 0:
         return out
     pl = rs.plan(sr_in, sr_out)
     taps = pl.device_taps(src.device)
-    dev = src.device
-    # descriptor arrays must outlive the (asynchronous) launch call: keep references until it returns
-    d_offs = _i64(in_offs + out_offs, dev)
-    d_ns = torch.tensor(n_in + n_out, dtype=torch.int32, device=dev)
+    d_offs, d_ns = _i64(in_offs + out_offs, src.device), _i32(n_in + n_out, src.device)
     # algorithmic bytes: every input sample once, every output sample once
     with _timed("resample_kernel", repeat * float(sum(n_in) * (2 if pcm16 else 4) + sum(n_out) * 4)):
         for _ in range(repeat):
@@ -386,18 +450,14 @@ def resample_batch(flat, lengths, sr_in, sr_out, repeat=1):
     samples per signal, all at sr_in Hz -> (out_flat float32: the signals at sr_out Hz back to back, out_lengths);
     out_lengths[u] = ceil(lengths[u] sr_out / sr_in).  Enqueued on the current stream."""
     from . import resample as rs
-    ns = [int(n) for n in lengths]
-    if flat.dim() != 1 or sum(ns) != flat.numel():
-        raise _lib.SepkernError("resample_batch needs one 1-D tensor and lengths that add up to it")
+    _samples("resample_batch", flat)
+    ns, in_offs, total = _lengths("resample_batch", lengths, 0)
+    if total != flat.numel():
+        raise _lib.SepkernError("resample_batch needs lengths that add up to the tensor of samples")
     outs = [rs.out_len(n, sr_in, sr_out) for n in ns]
-    in_offs, out_offs, ai, ao = [], [], 0, 0
-    for n, m in zip(ns, outs):
-        in_offs.append(ai)
-        out_offs.append(ao)
-        ai += n
-        ao += m
-    out = torch.empty(ao, dtype=torch.float32, device=flat.device)
-    resample_into(flat.contiguous(), in_offs, ns, out, out_offs, outs, sr_in, sr_out, repeat=repeat)
+    out_offs, size = prefix_sums(outs)
+    out = _out("resample_batch", None, size, flat)
+    resample_into(flat, in_offs, ns, out, out_offs, outs, sr_in, sr_out, repeat=repeat)
     return out, outs
 
 
@@ -407,18 +467,14 @@ def pcm_to_rate(flat, lengths, rates, target):
     already at `target` is only scaled by 1/32768 (exact: what sk_stft's pcm16 path does to it).
     Returns (out_flat float32, out_lengths)."""
     from . import resample as rs
-    _chk(flat, torch.int16)
-    ns, rates, target = [int(n) for n in lengths], [int(r) for r in rates], int(target)
-    if flat.dim() != 1 or sum(ns) != flat.numel() or len(rates) != len(ns):
-        raise _lib.SepkernError("pcm_to_rate needs one 1-D tensor, lengths that add up to it and one rate per signal")
+    if not _samples("pcm_to_rate", flat):
+        raise _lib.SepkernError("pcm_to_rate takes int16 PCM (got %s)" % flat.dtype)
+    (ns, in_offs, total), rates, target = _lengths("pcm_to_rate", lengths, 0), [int(r) for r in rates], int(target)
+    if total != flat.numel() or len(rates) != len(ns):
+        raise _lib.SepkernError("pcm_to_rate needs lengths that add up to the tensor of samples and one rate per signal")
     outs = [rs.out_len(n, r, target) if r != target else n for n, r in zip(ns, rates)]
-    in_offs, out_offs, ai, ao = [], [], 0, 0
-    for n, m in zip(ns, outs):
-        in_offs.append(ai)
-        out_offs.append(ao)
-        ai += n
-        ao += m
-    out = torch.empty(ao, dtype=torch.float32, device=flat.device)
+    out_offs, size = prefix_sums(outs)
+    out = _out("pcm_to_rate", None, size, flat)
     for r in sorted(set(rates)):
         idx = [u for u, ru in enumerate(rates) if ru == r]
         if r != target:
@@ -447,35 +503,16 @@ def dynamic_mix(flat, src_offs, nsamp, amp, peak, quantize=False, out=None, repe
     key back to back in the order given, (S + 1) sum(nsamp) samples -- and gains (S, B), the final gain of every source.
     quantize: every output sample lands on the int16 grid (clip(rint(32768 v)) / 32768).  out: a float32 buffer of that size to
     write into."""
-    pcm16 = flat.dtype == torch.int16
-    _chk(flat, torch.int16 if pcm16 else torch.float32)
-    ns = [int(n) for n in nsamp]
+    pcm16 = _samples("dynamic_mix", flat)
+    ns, starts, total = _lengths("dynamic_mix", nsamp, 1, "mixture")
     B, dev = len(ns), flat.device
-    src_offs = [[int(o) for o in offs] for offs in src_offs]
-    S = len(src_offs)
-    if flat.dim() != 1 or not flat.is_contiguous() or B == 0 or min(ns) < 1:
-        raise _lib.SepkernError("dynamic_mix needs one contiguous 1-D tensor of samples and at least one mixture of at least one sample")
-    if not 1 <= S <= 4 or any(len(o) != B for o in src_offs):
-        raise _lib.SepkernError("dynamic_mix needs 1..4 lists of %d source offsets (got %d)" % (B, S))
-    if any(o < 0 or o + n > flat.numel() for offs in src_offs for o, n in zip(offs, ns)):
-        raise _lib.SepkernError("dynamic_mix: a source runs past the sample buffer")
+    offs, S = _offsets("dynamic_mix", src_offs, ns, flat.numel(), (1, 4, "source"))
     amp = [[float(a) for a in row] for row in amp]
     peak = [float(p) for p in peak]
     if len(amp) != S or any(len(row) != B for row in amp) or len(peak) != B:
         raise _lib.SepkernError("dynamic_mix needs one amplitude per source signal (%d x %d) and one peak per mixture" % (S, B))
-    total = sum(ns)
-    if out is None:
-        out = torch.empty((S + 1) * total, dtype=torch.float32, device=dev)
-    _chk(out)
-    if out.dim() != 1 or not out.is_contiguous() or out.numel() < (S + 1) * total:
-        raise _lib.SepkernError("dynamic_mix: out must be a contiguous 1-D float32 tensor of (S + 1) * sum(nsamp) samples")
-    starts, at = [], 0
-    for n in ns:
-        starts.append(at)
-        at += n
-    # descriptor arrays must outlive the (asynchronous) launch call: keep references until it returns
-    d64 = _i64([o for offs in src_offs for o in offs] + [q * total + st for q in range(S + 1) for st in starts], dev)
-    d_ns = torch.tensor(ns, dtype=torch.int32, device=dev)
+    out = _out("dynamic_mix", out, (S + 1) * total, flat)
+    d64, d_ns = _i64(offs + [q * total + st for q in range(S + 1) for st in starts], dev), _i32(ns, dev)
     d_f = torch.tensor([a for row in amp for a in row] + peak, dtype=torch.float32, device=dev)
     gains = torch.empty(S, B, dtype=torch.float32, device=dev)
     # algorithmic bytes: every input sample once, every output sample once
@@ -492,29 +529,22 @@ def fir_convolve(flat, in_offs, ns, rir_flat, rir_offs, taps, delay, repeat=1):
     ONE 1-D CUDA tensor of samples, float32 or int16 PCM (scaled by 1/32768 in-kernel); job j: the ns[j] samples at in_offs[j]
     with the taps[j] float32 taps at rir_offs[j] of rir_flat (1-D CUDA float32), at delay[j] in [0, taps[j]) -- jobs may share a
     signal or a RIR.  -> (out, offsets): out float32, the jobs' ns[j] output samples back to back, job j's at offsets[j]."""
-    pcm16 = flat.dtype == torch.int16
-    _chk(flat, torch.int16 if pcm16 else torch.float32)
-    _chk(rir_flat)
-    in_offs, ns, rir_offs, taps, delay = ([int(v) for v in a] for a in (in_offs, ns, rir_offs, taps, delay))
+    pcm16 = _samples("fir_convolve", flat)
+    _samples("fir_convolve", rir_flat, "RIR taps", pcm=False)
+    ns, out_offs, at = _lengths("fir_convolve", ns, 1, "job")
+    taps, delay = _lengths("fir_convolve", taps, 1, "RIR")[0], [int(d) for d in delay]
     J = len(ns)
-    if flat.dim() != 1 or rir_flat.dim() != 1 or not flat.is_contiguous() or not rir_flat.is_contiguous():
-        raise _lib.SepkernError("fir_convolve: samples and RIRs must be contiguous 1-D tensors")
-    if J == 0 or not (len(in_offs) == len(rir_offs) == len(taps) == len(delay) == J):
+    if not len(taps) == len(delay) == J:
         raise _lib.SepkernError("fir_convolve: one offset, length, RIR offset, tap count and delay per job")
-    if any(o < 0 or n < 1 or o + n > flat.numel() for o, n in zip(in_offs, ns)) or \
-            any(o < 0 or t < 1 or o + t > rir_flat.numel() for o, t in zip(rir_offs, taps)):
-        raise _lib.SepkernError("fir_convolve: a signal or a RIR runs past its buffer (or is empty)")
-    out_offs, at = [], 0
-    for n in ns:
-        out_offs.append(at)
-        at += n
+    in_offs, = _offsets("fir_convolve", in_offs, ns, flat.numel())
+    rir_offs, = _offsets("fir_convolve", rir_offs, taps, rir_flat.numel())
     h_in, h_rir, h_out = (C.c_int64 * J)(*in_offs), (C.c_int64 * J)(*rir_offs), (C.c_int64 * J)(*out_offs)
     h_ns, h_taps, h_delay = (C.c_int32 * J)(*ns), (C.c_int32 * J)(*taps), (C.c_int32 * J)(*delay)
     nbytes = _lib.load().sk_fir_workspace_bytes(h_ns, h_taps, h_delay, J)
     if nbytes == 0:
         raise _lib.SepkernError("fir_convolve: 1..65535 jobs of 1..8192 taps, 0 <= delay < taps and 1..2^30 samples (sk_fir_workspace_bytes refused the jobs)")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=flat.device)
-    out = torch.empty(at, dtype=torch.float32, device=flat.device)
+    out = _out("fir_convolve", None, at, flat)
     # 5 N log2 N per 512-point transform (N = 512) and 8 flops per bin and partition product
     nb = [(d + n - 1) // 256 - d // 256 + 1 for n, d in zip(ns, delay)]
     kk = [-(-t // 256) for t in taps]
@@ -572,33 +602,15 @@ def mix_channels(flat, chan_offs, nsamp, gains, quantize=False, out=None, repeat
     -> out_flat float32, channel-major, the utterances of every channel back to back in the order given: P sum(nsamp) samples.
     Levels and the peak are defined on the reference channel: another channel may exceed the peak.  out: a float32 buffer of
     that size to write into."""
-    _chk(flat)
+    _samples("mix_channels", flat, pcm=False)
     _chk(gains)
-    ns = [int(n) for n in nsamp]
+    ns, starts, total = _lengths("mix_channels", nsamp, 1, "mixture")
     B, dev = len(ns), flat.device
-    S = len(chan_offs)
-    P = len(chan_offs[0]) if S else 0
-    if flat.dim() != 1 or not flat.is_contiguous() or B == 0 or min(ns) < 1:
-        raise _lib.SepkernError("mix_channels needs one contiguous 1-D tensor of samples and at least one mixture of at least one sample")
-    if not 1 <= S <= 4 or not 1 <= P <= 7 or any(len(row) != P or any(len(o) != B for o in row) for row in chan_offs):
-        raise _lib.SepkernError("mix_channels needs offsets [S][P][B] with 1 <= S <= 4 sources and 1 <= P <= 7 channels of %d mixtures" % B)
-    offs = [int(o) for row in chan_offs for chan in row for o in chan]
-    if any(o < 0 or o + ns[q % B] > flat.numel() for q, o in enumerate(offs)):
-        raise _lib.SepkernError("mix_channels: a signal runs past the sample buffer")
+    offs, S, P = _offsets("mix_channels", chan_offs, ns, flat.numel(), (1, 4, "source"), (1, 7, "channel"))          # [S][P][B]
     if tuple(gains.shape) != (S, B) or not gains.is_contiguous() or gains.device != dev:
         raise _lib.SepkernError("mix_channels: gains is dynamic_mix's contiguous (S, B) = (%d, %d) tensor on the samples' device" % (S, B))
-    total = sum(ns)
-    if out is None:
-        out = torch.empty(P * total, dtype=torch.float32, device=dev)
-    _chk(out)
-    if out.dim() != 1 or not out.is_contiguous() or out.numel() < P * total:
-        raise _lib.SepkernError("mix_channels: out must be a contiguous 1-D float32 tensor of P * sum(nsamp) samples")
-    starts, at = [], 0
-    for n in ns:
-        starts.append(at)
-        at += n
-    d64 = _i64(offs + [p * total + st for p in range(P) for st in starts], dev)
-    d_ns = torch.tensor(ns, dtype=torch.int32, device=dev)
+    out = _out("mix_channels", out, P * total, flat)
+    d64, d_ns = _i64(offs + [p * total + st for p in range(P) for st in starts], dev), _i32(ns, dev)
     with _timed("mix_channels_kernel", repeat * float(total) * P * (S + 1) * 4):
         for _ in range(repeat):
             _lib.call("sk_mix_channels", _ptr(flat), _ptr(d64), _ptr(d_ns), B, S, P, _ptr(gains), int(bool(quantize)), _ptr(out),
@@ -627,46 +639,22 @@ def noise_factors(mics, rate, device=None, repeat=1):
     return L
 
 
-def _noise_offsets(who, flat, offs, ns, lo, hi):
-    """offs[c][u] -> (C, the flat list), checked against the buffer."""
-    offs = [[int(o) for o in row] for row in offs]
-    Cn, B = len(offs), len(ns)
-    if not lo <= Cn <= hi or any(len(row) != B for row in offs):
-        raise _lib.SepkernError("%s needs %d..%d lists of %d offsets (got %d)" % (who, lo, hi, B, Cn))
-    if any(o < 0 or o + n > flat.numel() for row in offs for o, n in zip(row, ns)):
-        raise _lib.SepkernError("%s: a signal runs past its buffer" % who)
-    return Cn, [o for row in offs for o in row]
-
-
 def diffuse_noise(flat, chan_offs, nsamp, L, out=None, repeat=1):
     """A diffuse noise field from C independent noise signals per mixture in one launch (sk_diffuse_noise; sepkern/noise.py
     diffuse defines the result).  flat: ONE 1-D CUDA tensor of samples, float32 or int16 PCM; chan_offs[c][u]: the offset of
     mixture u's signal c (nsamp[u] samples); L: noise_factors' (B, 257, C (C + 1) / 2) tensor.
     -> out_flat float32, channel-major, the mixtures of every channel back to back in the order given: C sum(nsamp) samples.
     out: a float32 buffer of that size to write into."""
-    pcm16 = flat.dtype == torch.int16
-    _chk(flat, torch.int16 if pcm16 else torch.float32)
+    pcm16 = _samples("diffuse_noise", flat)
     _chk(L)
-    ns = [int(n) for n in nsamp]
+    ns, starts, total = _lengths("diffuse_noise", nsamp, 1, "mixture")
     B, dev = len(ns), flat.device
-    if flat.dim() != 1 or not flat.is_contiguous() or B == 0 or min(ns) < 1:
-        raise _lib.SepkernError("diffuse_noise needs one contiguous 1-D tensor of samples and at least one mixture of at least one sample")
-    Cn, offs = _noise_offsets("diffuse_noise", flat, chan_offs, ns, 2, 8)
+    offs, Cn = _offsets("diffuse_noise", chan_offs, ns, flat.numel(), (2, 8, "channel"))
     if tuple(L.shape) != (B, 257, Cn * (Cn + 1) // 2) or not L.is_contiguous() or L.device != dev:
         raise _lib.SepkernError("diffuse_noise: L is noise_factors' contiguous (B, 257, C (C + 1) / 2) = (%d, 257, %d) tensor on the samples' device"
                                 % (B, Cn * (Cn + 1) // 2))
-    total = sum(ns)
-    if out is None:
-        out = torch.empty(Cn * total, dtype=torch.float32, device=dev)
-    _chk(out)
-    if out.dim() != 1 or not out.is_contiguous() or out.numel() < Cn * total:
-        raise _lib.SepkernError("diffuse_noise: out must be a contiguous 1-D float32 tensor of C * sum(nsamp) samples")
-    starts, at = [], 0
-    for n in ns:
-        starts.append(at)
-        at += n
-    d64 = _i64(offs + [c * total + st for c in range(Cn) for st in starts], dev)
-    d_ns = torch.tensor(ns, dtype=torch.int32, device=dev)
+    out = _out("diffuse_noise", out, Cn * total, flat)
+    d64, d_ns = _i64(offs + [c * total + st for c in range(Cn) for st in starts], dev), _i32(ns, dev)
     # 5 N log2 N per 512-point transform, 2 C per frame, and 4 flops per bin and factor entry
     frames = sum(-(-n // 128) + 3 for n in ns)
     with _timed("diffuse_noise_kernel", repeat * frames * (5.0 * 512 * 9 * 2 * Cn + 4.0 * 257 * Cn * (Cn + 1) / 2)):
@@ -681,23 +669,20 @@ def add_noise(sig, sig_offs, noise, noise_offs, nsamp, amp, quantize=False, repe
     add_noise states the rule).  sig: ONE 1-D CUDA float32 tensor, sig_offs[c][u] the offset of channel c of mixture u (nsamp[u]
     samples), the reference channel first; noise / noise_offs: the same for the noise, float32 or int16 PCM; amp: B linear
     amplitudes, 10^(-snr / 20).  -> the B gains a (float32 tensor): a = amp sqrt(P_mix / P_noise) on the reference channel."""
-    pcm16 = noise.dtype == torch.int16
-    _chk(sig)
-    _chk(noise, torch.int16 if pcm16 else torch.float32)
-    ns = [int(n) for n in nsamp]
+    _samples("add_noise", sig, "signals", pcm=False)
+    pcm16 = _samples("add_noise", noise, "noise")
+    if noise.device != sig.device:
+        raise _lib.SepkernError("add_noise needs the signals and the noise on one device")
+    ns, _, total = _lengths("add_noise", nsamp, 1, "mixture")
     B, dev = len(ns), sig.device
-    if sig.dim() != 1 or noise.dim() != 1 or not sig.is_contiguous() or not noise.is_contiguous() or noise.device != dev or B == 0 or min(ns) < 1:
-        raise _lib.SepkernError("add_noise needs two contiguous 1-D tensors on one device and at least one mixture of at least one sample")
-    Cn, so = _noise_offsets("add_noise", sig, sig_offs, ns, 1, 8)
-    Cv, no = _noise_offsets("add_noise", noise, noise_offs, ns, 1, 8)
+    so, Cn = _offsets("add_noise", sig_offs, ns, sig.numel(), (1, 8, "channel"))
+    no, Cv = _offsets("add_noise", noise_offs, ns, noise.numel(), (1, 8, "noise channel"))
     amp = [float(a) for a in amp]
     if Cv != Cn or len(amp) != B:
         raise _lib.SepkernError("add_noise needs one noise signal per channel (%d, got %d) and one amplitude per mixture" % (Cn, Cv))
-    d64 = _i64(so + no, dev)
-    d_ns = torch.tensor(ns, dtype=torch.int32, device=dev)
+    d64, d_ns = _i64(so + no, dev), _i32(ns, dev)
     d_amp = torch.tensor(amp, dtype=torch.float32, device=dev)
     gains = torch.empty(B, dtype=torch.float32, device=dev)
-    total = sum(ns)
     with _timed("add_noise_kernel", repeat * float(total) * (8 + (2 if pcm16 else 4) + Cn * (8 + (2 if pcm16 else 4)))):
         for _ in range(repeat):
             _lib.call("sk_add_noise", _ptr(sig), _ptr(d64), _ptr(noise), int(pcm16), _ptr(d64[Cn * B:]), _ptr(d_ns), B, Cn, _ptr(d_amp),
@@ -1428,30 +1413,11 @@ def stft_psa(flat, sig_offs, nsamp, S, pk=None, clamp=False, out=None, repeat=1)
     With pk (the batch's Packing, length-sorted: no perm) both are packed rows (Rp, 257), rows R.. zero; without it, utterance u
     is the block of T_u = 1 + nsamp[u] // 128 rows that starts at row sum_{v<u} T_v (frame-major (T_u, 257)).
     out = (mix (>= rows, ld), targets (S, >= rows, ld)) float32 with unit column stride is written in place."""
-    pcm16 = flat.dtype == torch.int16
-    _chk(flat, torch.int16 if pcm16 else torch.float32)
-    ns = [int(n) for n in nsamp]
+    pcm16 = _samples("stft_psa", flat)
+    ns = _lengths("stft_psa", nsamp, what="utterance")[0]
     B, F, dev = len(ns), 257, flat.device
-    sig_offs = [[int(o) for o in offs] for offs in sig_offs]
-    if flat.dim() != 1 or not flat.is_contiguous() or B == 0:
-        raise _lib.SepkernError("stft_psa needs one contiguous 1-D tensor of samples and at least one utterance")
-    if len(sig_offs) != S + 1 or any(len(o) != B for o in sig_offs):
-        raise _lib.SepkernError("stft_psa needs S + 1 = %d lists of %d signal offsets (mixture first)" % (S + 1, B))
-    if any(o < 0 or o + n > flat.numel() for offs in sig_offs for o, n in zip(offs, ns)):
-        raise _lib.SepkernError("stft_psa: a signal runs past the sample buffer")
-    Ts = [1 + n // 128 for n in ns]
-    if pk is not None:
-        if pk.perm is not None:
-            raise _lib.SepkernError("stft_psa needs a length-sorted batch (Packing without perm)")
-        if pk.B != B or [int(t) for t in pk.lens_host] != Ts:
-            raise _lib.SepkernError("stft_psa: the Packing's frame counts are not those of the signals")
-        rows, rows_p, bases = pk.R, pk.Rp, None
-    else:
-        bases, rows = [], 0
-        for T in Ts:
-            bases.append(rows)
-            rows += T
-        rows_p = rows
+    offs, _ = _offsets("stft_psa", sig_offs, ns, flat.numel(), (S + 1, S + 1, "signal (the mixture, then the S sources)"))
+    Ts, rows, rows_p, bases = _row_layout("stft_psa", ns, pk)
     if out is None:
         mix = torch.empty(rows_p, F, dtype=torch.float32, device=dev)
         tgt = torch.empty(max(S, 1), rows_p, F, dtype=torch.float32, device=dev)
@@ -1467,9 +1433,7 @@ def stft_psa(flat, sig_offs, nsamp, S, pk=None, clamp=False, out=None, repeat=1)
         raise _lib.SepkernError("stft_psa: out must be (mix (>= rows, ld), targets (S, >= rows, ld)) with one row stride")
     ld = int(mix.stride(0)) if mix.shape[0] > 1 else int(mix.shape[1])
     ws = torch.empty(rows * F, 2, dtype=torch.float32, device=dev)       # the mixture's complex bins on their way to the contractions
-    # descriptor arrays must outlive the (asynchronous) launch call: keep references until it returns
-    d64 = _i64([o for offs in sig_offs for o in offs] + (bases or []), dev)
-    d_ns = torch.tensor(ns, dtype=torch.int32, device=dev)
+    d64, d_ns = _i64(offs + (bases or []), dev), _i32(ns, dev)
     # algorithmic bytes per frame: 128 new samples of each of the S + 1 signals in, their 257 values out
     with _timed("stft_psa_kernel", repeat * float(sum(Ts)) * (S + 1) * (128 * (2 if pcm16 else 4) + 257 * 4)):
         for _ in range(repeat):
@@ -1492,32 +1456,13 @@ def stft_ipd(flat, sig_offs, nsamp, pk=None, out=None, want_mix=True, ws=None, r
     out = (rows (>= R, ld >= width) float32 with unit column stride, mix (>= R, 257) contiguous or None) is written in place.
     ws: the work rows, a float32 tensor of at least R * 257 * 2 elements (default: allocated here)."""
     from . import ipd as _ipd
-    pcm16 = flat.dtype == torch.int16
-    _chk(flat, torch.int16 if pcm16 else torch.float32)
-    ns = [int(n) for n in nsamp]
+    pcm16 = _samples("stft_ipd", flat)
+    ns = _lengths("stft_ipd", nsamp, what="utterance")[0]
     B, F, dev = len(ns), 257, flat.device
-    sig_offs = [[int(o) for o in offs] for offs in sig_offs]
-    P = len(sig_offs) - 1
-    if flat.dim() != 1 or not flat.is_contiguous() or B == 0:
-        raise _lib.SepkernError("stft_ipd needs one contiguous 1-D tensor of samples and at least one utterance")
-    if not 1 <= P <= _ipd.MAX_PAIRS or any(len(o) != B for o in sig_offs):
-        raise _lib.SepkernError("stft_ipd needs 1 + P lists (P in 1..%d) of %d signal offsets, the reference channel first" % (_ipd.MAX_PAIRS, B))
-    if any(o < 0 or o + n > flat.numel() for offs in sig_offs for o, n in zip(offs, ns)):
-        raise _lib.SepkernError("stft_ipd: a signal runs past the sample buffer")
-    Ts = [1 + n // 128 for n in ns]
+    offs, nsig = _offsets("stft_ipd", sig_offs, ns, flat.numel(), (2, 1 + _ipd.MAX_PAIRS, "channel (the reference first)"))
+    P = nsig - 1
+    Ts, nrows, rows_p, bases = _row_layout("stft_ipd", ns, pk)
     width = _ipd.in_dim(P)
-    if pk is not None:
-        if pk.perm is not None:
-            raise _lib.SepkernError("stft_ipd needs a length-sorted batch (Packing without perm)")
-        if pk.B != B or [int(t) for t in pk.lens_host] != Ts:
-            raise _lib.SepkernError("stft_ipd: the Packing's frame counts are not those of the signals")
-        nrows, rows_p, bases = pk.R, pk.Rp, None
-    else:
-        bases, nrows = [], 0
-        for T in Ts:
-            bases.append(nrows)
-            nrows += T
-        rows_p = nrows
     if out is None:
         rows = torch.empty(rows_p, _ipd.padded_dim(P), dtype=torch.float32, device=dev)
         mix = torch.empty(rows_p, F, dtype=torch.float32, device=dev) if want_mix else None
@@ -1539,9 +1484,7 @@ def stft_ipd(flat, sig_offs, nsamp, pk=None, out=None, want_mix=True, ws=None, r
     _chk(ws)
     if not ws.is_contiguous() or ws.numel() < nrows * F * 2:
         raise _lib.SepkernError("stft_ipd: ws must be a contiguous float32 tensor of at least %d elements" % (nrows * F * 2))
-    # descriptor arrays must outlive the (asynchronous) launch call: keep references until it returns
-    d64 = _i64([o for offs in sig_offs for o in offs] + (bases or []), dev)
-    d_ns = torch.tensor(ns, dtype=torch.int32, device=dev)
+    d64, d_ns = _i64(offs + (bases or []), dev), _i32(ns, dev)
     # algorithmic bytes per frame: 128 new samples of each of the 1 + P signals in; 257 (1 + 2P) features (+ 257 of mix) out
     nbytes = (1 + P) * 128 * (2 if pcm16 else 4) + (width + (F if mix is not None else 0)) * 4
     with _timed("stft_ipd_kernel", repeat * float(sum(Ts)) * nbytes):

@@ -155,7 +155,7 @@ def separate_recording(model, pcm, sample_rate, window_frames=400, hop_frames=20
             if pcm.dtype == torch.int16:
                 pcm, _ = ops.pcm_to_rate(pcm, [pcm.numel()], [int(sample_rate)], int(working_rate))
             else:
-                pcm, _ = ops.resample_batch(pcm, [pcm.numel()], int(sample_rate), int(working_rate))
+                pcm, _ = ops.resample_batch(pcm.contiguous(), [pcm.numel()], int(sample_rate), int(working_rate))
         mixc = ops.stft_batch([pcm], want_complex=True)[0]          # (T, 257) complex64 rows of the whole recording
     X = None
     if wpe:
